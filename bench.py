@@ -16,11 +16,19 @@ same per-GPU workload ALONE (the other ranks idle at a barrier) and prints it as
 `--gather` times, separately from the render, the collection of all ranks' pixels on rank 0 over RCCL
 ("report the gathered variant separately").
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, ...).  `--dump-outputs DIR` then also writes what the last timed step computed -- pixels and the
+three gradients -- as DIR/<name>.npy (float32; a fixed, seeded sample of each array when their data exceed 60 MiB
+together, so that the files stay under 64 MB).
+`--full` adds everything else below, each measured in runs of its own after the timed steps.
+
+Extra objects on the JSON line with --full:
   roofline     -- the dominant kernel (by summed HIP-event time over the timed steps) against the HBM
                   roofline: achieved = that kernel's algorithmic bytes per launch / its mean duration.
   cpu_baseline -- the CPU oracle ("port" of the reference's algorithm; the reference op itself is
                   GPU-only) timed on this host's cores on a bounded sample of the same workload.
+  ...          -- eager / graph launch calibration, event-timed regions, the autograd paths, the K3-256 and
+                  K3-2048 legs and, at N > 1, the one-GPU scaling reference.
 """
 import argparse
 import json
@@ -61,6 +69,33 @@ def kernel_algorithmic_bytes(P, V, F, C):
     }
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # the arrays' data: with the .npy headers the files stay under 64 MB
+DUMP_NAMES = ('pixels', 'grad_background', 'grad_vertices', 'grad_vertex_colors')
+
+
+def dump_outputs(out_dir, last):
+    """Writes what the last timed step handed back -- (pixels, (grad_background, grad_vertices, grad_vertex_colors, _)) --
+    as out_dir/<name>.npy in float32.  When the arrays exceed DUMP_BUDGET_BYTES together, each is replaced by the same
+    share of its elements, taken in order at indices drawn with a fixed seed (np.random.default_rng(0)), so that two
+    runs with the same arguments write comparable files."""
+    assert last is not None, '--dump-outputs needs at least one step'
+    px, grads = last
+    arrays = dict(zip(DUMP_NAMES, (px,) + tuple(grads[:3])))
+    torch.cuda.synchronize()
+    host = {k: a.detach().float().cpu().numpy() for k, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = int(a.size * (DUMP_BUDGET_BYTES / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    print('bench: wrote %s to %s%s' % (', '.join(n + '.npy' for n in host), out_dir,
+                                      ' (seeded samples: outputs exceed %d MB)' % (DUMP_BUDGET_BYTES >> 20) if total > DUMP_BUDGET_BYTES else ''),
+          file=sys.stderr)
+
+
 def _free_port():
     import socket
     with socket.socket() as s_:
@@ -76,7 +111,7 @@ def main():
     ap.add_argument('--scenes-per-gpu', type=int, default=1,
                     help='scenes rendered per rank and step (default 1 at every N: K3 itself per GPU; 8 on 8 GPUs = K4)')
     ap.add_argument('--gather', action='store_true',
-                    help='also time gather_batch of every rank\'s pixels to rank 0 (outside the render timing; N > 1)')
+                    help='with --full: also time gather_batch of every rank\'s pixels to rank 0 (outside the render timing; N > 1)')
     ap.add_argument('--traffic', default='auto', choices=['auto', 'measure', 'file', 'off'],
                     help='roofline.traffic: measured in this run with rocprofv3 --pmc passes (auto: when rocprofv3 is on PATH and N = 1), '
                          'or read from profiles/pmc_traffic.json if its source stamp matches the tree')
@@ -92,6 +127,11 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the short K3-256 / K3-2048 legs')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU baseline time budget')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: launch calibration, event-timed regions, autograd paths, '
+                         'the K3-256 / K3-2048 legs, the N > 1 scaling reference, per-kernel roofline and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (pixels and the three gradients of rank 0) as DIR/<name>.npy')
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start N ranks on this node ourselves (one process per GPU,
@@ -173,7 +213,8 @@ def main():
         # ... and its launch clears the DENSE grad_vertices [B,V,4] / grad_vertex_colors [B,V,C] that the backward call adds into
         # and returns: the RasteriseGrad op's contract outputs (csrc/rasterise_grad_egl.cpp:381-391), no copy-out launch
         px, state = ops._op_rasterise(bg, v, vc, f, H, W, C, flags=flags, keep_state=True, dense_grads=not args.state_outputs)
-        return ops._op_rasterise_grad(v, f, px, g, H, W, C, flags=flags, state=state, state_outputs=True if args.state_outputs else 'dense')
+        grads = ops._op_rasterise_grad(v, f, px, g, H, W, C, flags=flags, state=state, state_outputs=True if args.state_outputs else 'dense')
+        return px, grads
 
     def barrier():
         if distributed:
@@ -202,9 +243,11 @@ def main():
     # Graph capture at N > 1 over RCCL is skipped unless asked for (--launch graph | auto): the eager path is the headline
     # either way, the graph figures are reported by the N = 1 run, and capturing while RCCL's watchdog thread polls its
     # events is a known source of "operation not permitted when stream is capturing" -- not a risk to take on a scaling run.
+    # A plain run captures the graph only when it times it (--launch graph | auto); --full also reports the other way.
     want_graph = (not distributed) or share_gpu or args.launch != 'eager'
-    graph_replay = None
-    if want_graph:
+    capture = args.launch != 'eager' or (args.full and want_graph)
+    graph_replay, graph_out = None, None
+    if capture:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -216,14 +259,17 @@ def main():
         with torch.cuda.graph(graph, **({'capture_error_mode': 'thread_local'} if distributed else {})):
             graph_out = step()
         graph_replay = graph.replay
-    # both ways are timed (a short region each, after a warm-up) and reported; the headline follows --launch
-    for _ in range(5):
-        step()
-        if graph_replay:
-            graph_replay()
+    # both ways are timed (a short region each, after a warm-up) and reported with --full or when --launch auto has to
+    # choose; the headline follows --launch
+    calib = None
     n_cal = max(20, min(args.steps, 100))
-    calib = {'eager_ms_per_step': timed(step, n_cal) * 1e3,
-             'graph_ms_per_step': timed(graph_replay, n_cal) * 1e3 if graph_replay else None, 'steps': n_cal}
+    if args.full or args.launch == 'auto':
+        for _ in range(5):
+            step()
+            if graph_replay:
+                graph_replay()
+        calib = {'eager_ms_per_step': timed(step, n_cal) * 1e3,
+                 'graph_ms_per_step': timed(graph_replay, n_cal) * 1e3 if graph_replay else None, 'steps': n_cal}
     if args.launch == 'auto':
         use_graph = calib['graph_ms_per_step'] < calib['eager_ms_per_step']
         if distributed:  # every rank takes rank 0's choice
@@ -234,14 +280,26 @@ def main():
         use_graph = args.launch == 'graph'
     run = graph_replay if use_graph else step
 
+    # Without the calibration, as many untimed steps as it issues (5 + n_cal each way) come first and, as it does, end in a
+    # synchronize: the timed steps of every run start from the same warm GPU and empty queue, as they always have (with
+    # only the W warm-up steps 200 timed steps read ~4 % slower; without the synchronize 20 timed steps do).
+    if calib is None:
+        for _ in range(2 * (5 + n_cal)):
+            run()
+        torch.cuda.synchronize()
+    last = None
     for _ in range(args.warmup):
-        run()
+        last = run()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     barrier()
     elapsed = time.perf_counter() - t0
+    if use_graph:
+        last = graph_out   # a replay refills the buffers the capture returned
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     if distributed:
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -249,6 +307,33 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     total_pixels = world * spg * P
     value = total_pixels / (elapsed / args.steps) / 1e6
+    step_bytes = algorithmic_bytes(P, V, F, C) * spg
+    headline = {
+        'metric': 'forward+backward Mpixels/s at 1024x1024x4ch, 10k-tri mesh' if args.config == 'K3'
+                  else 'forward+backward Mpixels/s (%s)' % args.config,
+        'value': value, 'unit': 'Mpixels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f32 (f64 edge functions)', 'data': 'synthetic',
+        'config': {'workload': '%s: rand_mesh F=%d at %dx%dx%d, %d scene(s) per GPU, forward+backward'
+                               % (args.config, F, H, W, C, spg),
+                   'outputs': 'strided views of the state\'s interleaved accumulators (--state-outputs)' if args.state_outputs else
+                              'dense grad_background [B,H,W,C], grad_vertices [B,V,4], grad_vertex_colors [B,V,C] (the op\'s contract outputs; '
+                              'cleared inside the forward launch, no copy-out launch)',
+                   'scenes_per_gpu': spg, 'parallelism': 'batch-sharded x%d, no collective' % world + (' (DIRT_BENCH_SHARE_GPU: all ranks on ONE GPU over gloo, control-flow test only)' if share_gpu else ''),
+                   'launch': 'one captured hipGraph replayed per step' if use_graph else 'eager (Python wrapper + C ABI per step)'},
+        'ranks_seen': ranks_seen,
+        'roofline_step': {'algorithmic_bytes': step_bytes, 'achieved': step_bytes / (ms_per_step * 1e-3) / 1e9,
+                          'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                          'frac': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                          'frac_of_measured_copy_peak': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_COPY_GBPS},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps between a HIP-event pair ON THE STREAM the kernels are launched on (torch's current
     #      stream: the wrapper passes torch.cuda.current_stream().cuda_stream to the C ABI), no synchronisation between the
@@ -509,21 +594,8 @@ def main():
             cpu_baseline['reference_kernel_backward'] = {'error': str(e)[:120]}
 
     if rank == 0:
-        step_bytes = algorithmic_bytes(P, V, F, C) * spg
-        out = {
-            'metric': 'forward+backward Mpixels/s at 1024x1024x4ch, 10k-tri mesh' if args.config == 'K3'
-                      else 'forward+backward Mpixels/s (%s)' % args.config,
-            'value': value, 'unit': 'Mpixels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f32 (f64 edge functions)', 'data': 'synthetic',
-            'config': {'workload': '%s: rand_mesh F=%d at %dx%dx%d, %d scene(s) per GPU, forward+backward'
-                                   % (args.config, F, H, W, C, spg),
-                       'outputs': 'strided views of the state\'s interleaved accumulators (--state-outputs)' if args.state_outputs else
-                                  'dense grad_background [B,H,W,C], grad_vertices [B,V,4], grad_vertex_colors [B,V,C] (the op\'s contract outputs; '
-                                  'cleared inside the forward launch, no copy-out launch)',
-                       'scenes_per_gpu': spg, 'parallelism': 'batch-sharded x%d, no collective' % world + (' (DIRT_BENCH_SHARE_GPU: all ranks on ONE GPU over gloo, control-flow test only)' if share_gpu else ''),
-                       'launch': 'one captured hipGraph replayed per step' if use_graph else 'eager (Python wrapper + C ABI per step)'},
-            'ranks_seen': ranks_seen,
+        out = dict(headline)
+        out.update({
             'ms_per_step_events_median': ms_per_step_events,
             'value_events_median': total_pixels / ms_per_step_events / 1e3,
             'timing': 'ms_per_step / value: wall clock over the K steps between barrier + synchronize (the contract); '
@@ -541,13 +613,9 @@ def main():
             'scaling_reference': scaling_reference,
             'gather': gather,
             'roofline': roofline,
-            'roofline_step': {'algorithmic_bytes': step_bytes, 'achieved': step_bytes / (ms_per_step * 1e-3) / 1e9,
-                              'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                              'frac': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                              'frac_of_measured_copy_peak': step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_COPY_GBPS},
             'kernels': kernels,
             'cpu_baseline': cpu_baseline,
-        }
+        })
         print(json.dumps(out))
     if distributed:
         dist.barrier()

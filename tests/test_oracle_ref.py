@@ -7,9 +7,10 @@ the channel-group loop of dirt/rasterise_ops.py:132-177.  With DIRT_ORACLE_FLAG_
 adds in float32 in the order one thread of that kernel does, so the two must agree BIT FOR BIT; in its
 default mode (double accumulators, any order) the oracle must sit within float32 summation error of it.
 
-Where /root/reference is absent and no prebuilt library travelled, the live comparisons skip and the
-committed vectors tests/golden/ref_grads.npz (written here by `python -m tests.golden.make_golden --ref`)
-stand in for the reference.
+Where the reference's sources are absent and no prebuilt library travelled, the comparisons with its kernels run
+against their recorded results (tests/golden/ref_recorded/, `python -m tests.golden.ref_calls`), the committed vectors
+tests/golden/ref_grads.npz (written here by `python -m tests.golden.make_golden --ref`) stand in for the reference as
+well, and the tests that execute the reference's own Python files skip.
 """
 import os
 
@@ -17,7 +18,7 @@ import numpy as np
 import pytest
 
 from tests import scenes
-from tests.golden import make_golden
+from tests.golden import make_golden, ref_calls
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 OUTPUTS = ('grad_background', 'grad_vertices', 'grad_vertex_colors', 'debug_thingy')
@@ -25,10 +26,19 @@ OUTPUTS = ('grad_background', 'grad_vertices', 'grad_vertex_colors', 'debug_thin
 
 @pytest.fixture(scope='module')
 def ref(oracle):
+    """The reference's kernels (oracle/ref.py); where they cannot be built, their recorded results (tests/golden/ref_calls.py)."""
     from oracle import ref as _ref
     if not _ref.available():
-        pytest.skip('oracle/_ref is not built and /root/reference is absent')
-    return _ref
+        if not ref_calls.recorded():
+            pytest.skip('oracle/_ref is not built, the reference sources are absent and no calls are recorded')
+        yield ref_calls.Replay()
+        return
+    if os.environ.get(ref_calls.RECORD_ENV):   # python -m tests.golden.ref_calls
+        recorder = ref_calls.Recorder(_ref)
+        yield recorder
+        recorder.save()
+        return
+    yield _ref
 
 
 def _batch(s):

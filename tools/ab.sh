@@ -10,7 +10,7 @@ for v in "$@"; do
     timeout 600 python -m pytest tests/test_gpu_configs.py tests/test_gpu_parity.py -q -x -m gpu -k "${CHECK_K:-K3 or hostile or c5 or square or shapes}" 2>&1 | tail -3
   fi
   for cfg in $CONFIGS; do
-    python bench.py $BENCH_ARGS --config $cfg --steps ${STEPS:-200} --warmup 50 --no-cpu-baseline --traffic off --launch eager 2>&1 | python -c "
+    python bench.py --full $BENCH_ARGS --config $cfg --steps ${STEPS:-200} --warmup 50 --no-cpu-baseline --traffic off --launch eager 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ TAG=${1:-r04}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BENCH="python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-other-configs --traffic off"
+BENCH="python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-other-configs --traffic off"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 RUN="python tools/prof_run.py K3 5"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $OUT/pmc_sq -o pmc -- $RUN > /dev/null 2>&1
@@ -15,14 +15,14 @@ rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACT
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- $RUN > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- $RUN > /dev/null 2>&1
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_l2 -o pmc -- $RUN > /dev/null 2>&1
-# the default bench line (in-run traffic measurement, CPU baseline), then the other configurations
-python bench.py > $OUT/bench.json 2> $OUT/bench.log
+# the full bench line (in-run traffic measurement, CPU baseline), then the other configurations
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.log
 for cfg in K3-256 K3-2048 K5; do
-  python bench.py --config $cfg --steps 100 --warmup 20 --no-cpu-baseline > $OUT/bench_$cfg.json 2>> $OUT/bench.log
+  python bench.py --full --config $cfg --steps 100 --warmup 20 --no-cpu-baseline > $OUT/bench_$cfg.json 2>> $OUT/bench.log
 done
-python bench.py --scenes-per-gpu 8 --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_K3x8.json 2>> $OUT/bench.log
-for cfg in K3-3ch K3-1ch; do python bench.py --config $cfg --steps 100 --warmup 20 --no-cpu-baseline --traffic off > $OUT/bench_$cfg.json 2>> $OUT/bench.log; done
-python bench.py --scenes-per-gpu 64 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_K4x1.json 2>> $OUT/bench.log
+python bench.py --full --scenes-per-gpu 8 --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_K3x8.json 2>> $OUT/bench.log
+for cfg in K3-3ch K3-1ch; do python bench.py --full --config $cfg --steps 100 --warmup 20 --no-cpu-baseline --traffic off > $OUT/bench_$cfg.json 2>> $OUT/bench.log; done
+python bench.py --full --scenes-per-gpu 64 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_K4x1.json 2>> $OUT/bench.log
 # kernel trace of the small-frame step (the one-pixel-per-lane gradient kernel) and of K5
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_K3-256 -o trace -- python tools/prof_run.py K3-256 50 > /dev/null 2>&1
 RUN5="python tools/prof_run.py K5 3"
@@ -41,7 +41,7 @@ if [ -f tools/_bin/libdirt_hip_trace.so ]; then
     DIRT_AMD_LIBRARY=$PWD/tools/_bin/libdirt_hip_trace.so timeout 300 python tools/trace_stream.py K3
     DIRT_AMD_LIBRARY=$PWD/tools/_bin/libdirt_hip_trace.so timeout 300 python tools/trace_grad.py K3 | head -24; } > $OUT/traces.log 2>&1
 fi
-for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --traffic off 2>/dev/null | grep '^{' > $OUT/bench_driver_cmd_$i.json; done
+for i in 1 2 3; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --traffic off 2>/dev/null | grep '^{' > $OUT/bench_driver_cmd_$i.json; done
 timeout 300 python tools/step_ramp2.py 20 > $OUT/step_ramp.log 2>&1
 { timeout 500 python tests/fuzz_parity.py 400 601; timeout 300 python tests/fuzz_parity.py 240 602 hostile; timeout 200 python tools/check_stream.py 150 603; } > $OUT/fuzz.log 2>&1
 ls -R $OUT | head -80

@@ -85,7 +85,7 @@ def main():
         if os.path.exists(f) and open(f).read().strip():
             drv.append(json.loads(open(f).read().strip().splitlines()[-1]))
     if drv:
-        json.dump({'command': 'python bench.py --gpus 1 --steps 20 --warmup 5 (three runs on one box; --no-cpu-baseline --traffic off)',
+        json.dump({'command': 'python bench.py --full --gpus 1 --steps 20 --warmup 5 (three runs on one box; --no-cpu-baseline --traffic off)',
                    'ms_per_step': [d['ms_per_step'] for d in drv], 'ms_per_step_events_median': [d['ms_per_step_events_median'] for d in drv],
                    'value': [d['value'] for d in drv]}, open(os.path.join(dst, tag + '_bench_driver_command.json'), 'w'), indent=1)
     print(open(os.path.join(dst, tag + '_kernel_stats.csv')).read())
