@@ -26,13 +26,16 @@ struct TexParams {
     float* grad_uvs;        // n pairs, `guv_stride` floats apart; or nullptr
 };
 
+// tf.clip_by_value(x, 0, 1) = minimum(maximum(x, 0), 1), which keeps a NaN (fminf / fmaxf would return the bound instead)
+__device__ __forceinline__ float clip01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
 // samples/textured.py:16-26: (u, v) -> fractional (row, column) index
 __device__ __forceinline__ void uv_to_index(float u, float v, int Ht, int Wt, bool clamp_mode, float& row, float& col, float& drow_dv,
                                             float& dcol_du)
 {
     if (clamp_mode) {
-        row = fminf(fmaxf(v, 0.f), 1.f) * (float)Ht;
-        col = fminf(fmaxf(u, 0.f), 1.f) * (float)Wt;
+        row = clip01(v) * (float)Ht;
+        col = clip01(u) * (float)Wt;
         drow_dv = (v >= 0.f && v <= 1.f) ? (float)Ht : 0.f;   // the gradient of clip_by_value
         dcol_du = (u >= 0.f && u <= 1.f) ? (float)Wt : 0.f;
     } else {
@@ -61,6 +64,10 @@ __device__ __forceinline__ void store_ch(float* __restrict__ p, const float (&v)
     else p[ch0] = v[0];
 }
 
+// A float index -> texel index in [0, n - 1] as min(max((int)x, 0), n - 1), with a NaN index (a NaN coordinate) taking 0:
+// converting a NaN to int is undefined in C++, so the rule is written out here instead of being left to the compiler
+__device__ __forceinline__ int texel_index(float x, int n) { return x >= 1.f ? min((int)fminf(x, (float)n), n - 1) : 0; }
+
 // The four texels of a bilinear look-up (samples/textured.py:36-60) and their weights
 struct Taps {
     int r0, r1, c0, c1;
@@ -71,8 +78,8 @@ __device__ __forceinline__ Taps bilinear_taps(float row, float col, int Ht, int 
     Taps t;
     const float fr0 = floorf(row), fc0 = floorf(col);
     t.fr = row - fr0; t.fc = col - fc0;   // frac_indices[..., :1] (row), [..., 1:] (column)
-    t.r0 = min(max((int)fr0, 0), Ht - 1); t.r1 = min(t.r0 + 1, Ht - 1);
-    t.c0 = min(max((int)fc0, 0), Wt - 1); t.c1 = min(t.c0 + 1, Wt - 1);
+    t.r0 = texel_index(fr0, Ht); t.r1 = min(t.r0 + 1, Ht - 1);
+    t.c0 = texel_index(fc0, Wt); t.c1 = min(t.c0 + 1, Wt - 1);
     t.wc0 = 1.f - t.fc; t.wr0 = 1.f - t.fr;
     return t;
 }
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(256) void texture_forward_kernel(TexParams p)
         uv_to_index(u, v, p.Ht, p.Wt, clamp_mode, row, col, drow_dv, dcol_du);
         float* __restrict__ out = p.out + i * Ct;
         if (nearest) {   // samples/textured.py:31-33: the indices truncated
-            const int r = min(max((int)row, 0), p.Ht - 1), c = min(max((int)col, 0), p.Wt - 1);
+            const int r = texel_index(row, p.Ht), c = texel_index(col, p.Wt);
             const float* __restrict__ t = p.texture + ((size_t)r * p.Wt + c) * Ct;
             for (int ch = 0; ch < (CT ? 1 : Ct); ++ch) { float q[NV]; load_ch<CT>(t, Ct, q, ch); store_ch<CT>(out, q, ch); }
             continue;
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
     uv_to_index(u, v, p.Ht, p.Wt, clamp_mode, row, col, drow_dv, dcol_du);
     Taps k = bilinear_taps(row, col, p.Ht, p.Wt);
     if (nearest) {   // one tap, weight 1 (samples/textured.py:31-33: the indices truncated)
-        k.r0 = k.r1 = min(max((int)row, 0), p.Ht - 1); k.c0 = k.c1 = min(max((int)col, 0), p.Wt - 1);
+        k.r0 = k.r1 = texel_index(row, p.Ht); k.c0 = k.c1 = texel_index(col, p.Wt);
         k.fr = 0.f; k.fc = 0.f; k.wr0 = 1.f; k.wc0 = 1.f;
     }
     __syncthreads();
