@@ -42,7 +42,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_rasterise_backward', 'dirt_rasterise_visibility', 'dirt_state_grad_buffers', 'dirt_profile_count',
            'dirt_profile_name',
            'dirt_profile_read', 'dirt_profile_reset', 'dirt_texture_sample_forward', 'dirt_texture_sample_backward',
-           'dirt_texture_sample_backward_image', 'dirt_texture_last_error')
+           'dirt_texture_sample_backward_image', 'dirt_texture_last_error', 'dirt_texture_mip_levels', 'dirt_texture_mip_build',
+           'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -95,6 +96,18 @@ def load():
         lib.dirt_texture_sample_backward_image.argtypes = [fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, u, vp]
         lib.dirt_texture_sample_backward_image.restype = i
     lib.dirt_texture_last_error.restype = ctypes.c_char_p
+    if hasattr(lib, 'dirt_texture_mip_levels') or not override:   # trilinear look-up (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_texture_mip_levels.argtypes = [i, i, i, i, ctypes.POINTER(ll)]
+        lib.dirt_texture_mip_levels.restype = i
+        lib.dirt_texture_mip_build.argtypes = [fp, fp, i, i, i, i, vp]
+        lib.dirt_texture_mip_build.restype = i
+        lib.dirt_texture_mip_collapse.argtypes = [fp, fp, i, i, i, i, vp]
+        lib.dirt_texture_mip_collapse.restype = i
+        lib.dirt_texture_sample_mip_forward.argtypes = [fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_sample_mip_forward.restype = i
+        lib.dirt_texture_sample_mip_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_sample_mip_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

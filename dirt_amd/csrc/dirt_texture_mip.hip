@@ -1,0 +1,585 @@
+// dirt_texture_mip.hip -- trilinear (mipmapped) texture look-up of a deferred shader, and its gradient.
+//
+// Extends the fused look-up of dirt_texture.hip (the reference's samples/textured.py:16-61: `uvs_to_pixel_indices` then a
+// bilinear `sample_texture`) with a mip pyramid and a level of detail taken from the screen-space footprint of (u, v).
+// The specification (DESIGN.md §7 restates it; tests/mip_reference.py implements it in numpy):
+//
+//  1. Pyramid.  Level 0 is the texture [Ht, Wt, Ct].  Level k+1 exists while level k is not 1 x 1, each dimension of level
+//     k is even or 1, and k+1 <= max_level (when given).  Each dimension halves; a dimension of size 1 stays 1.  A texel of
+//     level k+1 is the mean of its 2 x 2 block, ((t00 + t01) + (t10 + t11)) * 0.25, or of its 2 x 1 block, (a + b) * 0.5,
+//     in float32.  All levels live in one packed buffer, level after level, each [H_k, W_k, Ct]; H_k = max(Ht >> k, 1).
+//  2. Index at level k.  The level-0 fractional index (row, col) is uv_to_index's (repeat / clamp, scaled by Ht, Wt).  Per
+//     axis, with s = size_0 / size_k: index_k = max((index_0 - (s - 1) * 0.5) / s, 0) (texel footprints stay aligned across
+//     levels under the reference's convention of no half-texel shift; the max keeps bilinear_taps inside its domain), and
+//     index_0 itself at k = 0.  Then the bilinear taps at level k's size.  (max is written x < 0 ? 0 : x: a NaN stays NaN.)
+//  3. LOD.  Either given per look-up (lambda = lod + lod_bias), or from an image of look-ups [..., H, W, 2] (stacked images
+//     never share neighbours): x-difference = uv(r, c+1) - uv(r, c) if that pixel exists and is valid, else
+//     uv(r, c) - uv(r, c-1) if that one is, else 0; the y-difference likewise along rows; `valid` = mask != 0 (every pixel
+//     without a mask); repeat mode wraps each difference to d - rint(d).  rho = max(|(du_x Wt, dv_x Ht)|, |(du_y Wt, dv_y Ht)|)
+//     and lambda = log2(rho) + lod_bias; a pixel whose own mask is 0 takes lambda = 0.
+//  4. Blend.  lambda clamped to [0, L - 1] (NaN -> 0); l = floor(lambda), f = lambda - l;
+//     out = (1 - f) * S_l + f * S_{l+1} with S_l the bilinear sample of level l; where f == 0 only S_l is read and written
+//     (so lambda <= 0 gives the bilinear look-up of dirt_texture.hip bit for bit).
+//  5. Gradients.  To the texture: every level's share is summed into a pyramid-shaped scratch buffer, which one launch
+//     collapses to level 0 (each base texel sums its ancestors top down: acc = g_{L-1}; acc = g_k + acc * factor_{k+1},
+//     factor 1/4 for a 2 x 2 block, 1/2 for a 2 x 1 one).  To (u, v): through both levels' bilinear weights, the 1/s of
+//     index_k included, clamp mode's zero outside [0, 1] as before; lambda is held constant (no gradient flows through the
+//     finite-difference footprint).  To lod: S_{l+1} - S_l where lambda lies strictly inside (0, L - 1) before the clamp,
+//     else 0.  To the mask: none.
+//
+// Kernels: the pyramid in one launch of 32 x 32-texel blocks reduced through levels 1-5 in LDS, plus one single-workgroup
+// launch for the levels above; the forward one look-up per lane (its (u, v) neighbours read through L1 / L2); the backward
+// on 16 x 16-pixel tiles that sum into an LDS patch per touched level (at most two adjacent levels) and fall back to float
+// atomics into the scratch pyramid where the footprint does not fit; then the collapse.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/dirt_hip.h"
+#include "dirt_texture_common.h"
+
+namespace dirt {
+
+constexpr int MIP_MAX = 32;        // levels of a pyramid (a dimension of 2^31 halves 31 times)
+constexpr int MIP_TILE_LEVELS = 5; // levels reduced in LDS by the block kernel (a 32 x 32 block -> 1 x 1)
+constexpr int MIP_PATCH = 1600;    // texels of a tile's patches (both levels) held in LDS
+
+struct MipParams {
+    const float* pyr;        // packed pyramid (level 0 = the texture)
+    const float* uvs;        // rows x cols pairs (u, v), `uv_stride` floats apart
+    const float* lod;        // rows x cols levels of detail, or nullptr (footprint)
+    const float* mask;       // rows x cols, `mask_stride` floats apart, or nullptr (every pixel valid)
+    long long rows, cols;    // the look-ups as an image grid (stacked images: `image_rows` rows each)
+    int image_rows, Ht, Wt, Ct, L, uv_stride, guv_stride, mask_stride;
+    float lod_bias;
+    unsigned flags;
+    float* out;              // [n, Ct]
+    const float* grad_out;   // [n, Ct]
+    float* grad_pyr;         // packed pyramid-shaped scratch (cleared by the caller of the kernel)
+    float* grad_uvs;         // pairs `guv_stride` apart, or nullptr
+    float* grad_lod;         // n, or nullptr
+    long long off[MIP_MAX];  // float offset of each level in the packed buffers
+};
+
+__host__ __device__ __forceinline__ int mip_dim(int n0, int k) { const int d = n0 >> k; return d > 1 ? d : 1; }
+
+// the index of a level-0 fractional index at level k, per axis (spec 2), and its derivative with respect to the level-0 index
+__device__ __forceinline__ float mip_index(float idx0, int n0, int nk, float& d)
+{
+    const float s = (float)n0 / (float)nk;             // a power of two: the division and 1 / s are exact
+    const float x = (idx0 - (s - 1.f) * 0.5f) * (1.f / s);
+    d = x < 0.f ? 0.f : 1.f / s;
+    return x < 0.f ? 0.f : x;
+}
+
+__device__ __forceinline__ bool mip_valid(const MipParams& p, long long j) { return !p.mask || p.mask[j * p.mask_stride] != 0.f; }
+
+__device__ __forceinline__ void mip_uv(const MipParams& p, long long j, float& u, float& v)
+{
+    u = p.uvs[j * p.uv_stride]; v = p.uvs[j * p.uv_stride + 1];
+}
+
+// lambda of look-up i, before the clamp (spec 3)
+__device__ __forceinline__ float mip_lambda(const MipParams& p, long long i, float u, float v, bool clamp_mode)
+{
+    if (p.lod) return p.lod[i] + p.lod_bias;
+    if (!mip_valid(p, i)) return 0.f;
+    long long py, px, r;   // grid row and column, row inside the image (32-bit divisions where the grid allows)
+    if (i <= 0x7fffffffll && p.cols <= 0x7fffffffll) {
+        const unsigned q = (unsigned)i / (unsigned)p.cols;
+        py = q; px = (long long)((unsigned)i - q * (unsigned)p.cols); r = q % (unsigned)p.image_rows;
+    } else {
+        py = i / p.cols; px = i - py * p.cols; r = py % p.image_rows;
+    }
+    float dux = 0.f, dvx = 0.f, duy = 0.f, dvy = 0.f, un, vn;
+    if (px + 1 < p.cols && mip_valid(p, i + 1)) { mip_uv(p, i + 1, un, vn); dux = un - u; dvx = vn - v; }
+    else if (px >= 1 && mip_valid(p, i - 1)) { mip_uv(p, i - 1, un, vn); dux = u - un; dvx = v - vn; }
+    if (r + 1 < p.image_rows && mip_valid(p, i + p.cols)) { mip_uv(p, i + p.cols, un, vn); duy = un - u; dvy = vn - v; }
+    else if (r >= 1 && mip_valid(p, i - p.cols)) { mip_uv(p, i - p.cols, un, vn); duy = u - un; dvy = v - vn; }
+    if (!clamp_mode) { dux -= rintf(dux); dvx -= rintf(dvx); duy -= rintf(duy); dvy -= rintf(dvy); }
+    const float ax = dux * (float)p.Wt, bx = dvx * (float)p.Ht, ay = duy * (float)p.Wt, by = dvy * (float)p.Ht;
+    const float rx = sqrtf(ax * ax + bx * bx), ry = sqrtf(ay * ay + by * by);
+    return log2f(fmaxf(rx, ry)) + p.lod_bias;
+}
+
+// clamp to [0, L - 1] (NaN -> 0), split into level and fraction (spec 4)
+__device__ __forceinline__ void mip_split(float lam, int L, int& l, float& f)
+{
+    const float top = (float)(L - 1);
+    const float c = lam > 0.f ? (lam < top ? lam : top) : 0.f;
+    const float fl = floorf(c);
+    l = (int)fl; f = c - fl;
+}
+
+// ---- pyramid build: a workgroup takes a block of th x tw base texels (32 x 32 where the pyramid goes that far) and reduces it
+// through levels 1..kt in LDS, writing level 0 (the copy) and every level it makes; channels in passes of four.
+__device__ __forceinline__ float mip_reduce(const float* __restrict__ src, int sw, int r, int c, bool hr, bool hc, int j)
+{
+    const int r0 = hr ? 2 * r : r, c0 = hc ? 2 * c : c;
+    const float t00 = src[(r0 * sw + c0) * 4 + j];
+    if (hr && hc) {
+        const float t01 = src[(r0 * sw + c0 + 1) * 4 + j], t10 = src[((r0 + 1) * sw + c0) * 4 + j], t11 = src[((r0 + 1) * sw + c0 + 1) * 4 + j];
+        return ((t00 + t01) + (t10 + t11)) * 0.25f;
+    }
+    const float t1 = hr ? src[((r0 + 1) * sw + c0) * 4 + j] : src[(r0 * sw + c0 + 1) * 4 + j];
+    return (t00 + t1) * 0.5f;
+}
+
+__global__ __launch_bounds__(256) void mip_build_blocks_kernel(const float* __restrict__ tex, float* __restrict__ pyr, MipParams p, int kt,
+                                                               int tiles_x)
+{
+    __shared__ float s_a[32 * 32 * 4];
+    __shared__ float s_b[16 * 16 * 4];
+    const int tid = threadIdx.x, Ct = p.Ct;
+    const int Hk_t = mip_dim(p.Ht, kt), Wk_t = mip_dim(p.Wt, kt);
+    const int th = p.Ht / Hk_t, tw = p.Wt / Wk_t;   // the block of base texels (<= 32 x 32)
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    for (int c0 = 0; c0 < Ct; c0 += 4) {
+        const int nc = min(4, Ct - c0);
+        for (int e = tid; e < th * tw * nc; e += 256) {   // consecutive lanes on consecutive floats of a texture row
+            const int rr = e / (tw * nc), rest = e - rr * tw * nc, cc = rest / nc, j = rest - cc * nc;
+            const size_t g = ((size_t)(ty * th + rr) * p.Wt + (tx * tw + cc)) * Ct + c0 + j;
+            const float x = tex[g];
+            pyr[g] = x;
+            s_a[(rr * tw + cc) * 4 + j] = x;
+        }
+        __syncthreads();
+        int sh = th, sw = tw;
+        for (int k = 1; k <= kt; ++k) {
+            const bool hr = mip_dim(p.Ht, k - 1) > 1, hc = mip_dim(p.Wt, k - 1) > 1;
+            const int dh = hr ? sh / 2 : sh, dw = hc ? sw / 2 : sw;
+            const float* src = (k & 1) ? s_a : s_b;
+            float* dst = (k & 1) ? s_b : s_a;
+            const int Wk = mip_dim(p.Wt, k);
+            for (int e = tid; e < dh * dw * nc; e += 256) {
+                const int rr = e / (dw * nc), rest = e - rr * dw * nc, cc = rest / nc, j = rest - cc * nc;
+                const float x = mip_reduce(src, sw, rr, cc, hr, hc, j);
+                dst[(rr * dw + cc) * 4 + j] = x;
+                pyr[p.off[k] + ((size_t)(ty * dh + rr) * Wk + (tx * dw + cc)) * Ct + c0 + j] = x;
+            }
+            __syncthreads();
+            sh = dh; sw = dw;
+        }
+    }
+}
+
+// the levels above kt: one workgroup, level after level from the packed buffer (a level kt of up to 64 x 64 texels for a
+// 2048 x 2048 texture)
+__global__ __launch_bounds__(1024) void mip_build_top_kernel(float* __restrict__ pyr, MipParams p, int kt)
+{
+    const int Ct = p.Ct;
+    for (int k = kt + 1; k < p.L; ++k) {
+        const bool hr = mip_dim(p.Ht, k - 1) > 1, hc = mip_dim(p.Wt, k - 1) > 1;
+        const int Hk = mip_dim(p.Ht, k), Wk = mip_dim(p.Wt, k), Ws = mip_dim(p.Wt, k - 1);
+        const float* __restrict__ src = pyr + p.off[k - 1];
+        float* __restrict__ dst = pyr + p.off[k];
+        for (int e = threadIdx.x; e < Hk * Wk * Ct; e += blockDim.x) {
+            const int t = e / Ct, j = e - t * Ct, r = t / Wk, c = t - r * Wk;
+            const int r0 = hr ? 2 * r : r, c0 = hc ? 2 * c : c;
+            const float t00 = src[((size_t)r0 * Ws + c0) * Ct + j];
+            float x;
+            if (hr && hc) {
+                const float t01 = src[((size_t)r0 * Ws + c0 + 1) * Ct + j], t10 = src[((size_t)(r0 + 1) * Ws + c0) * Ct + j];
+                const float t11 = src[((size_t)(r0 + 1) * Ws + c0 + 1) * Ct + j];
+                x = ((t00 + t01) + (t10 + t11)) * 0.25f;
+            } else {
+                const float t1 = hr ? src[((size_t)(r0 + 1) * Ws + c0) * Ct + j] : src[((size_t)r0 * Ws + c0 + 1) * Ct + j];
+                x = (t00 + t1) * 0.5f;
+            }
+            dst[e] = x;
+        }
+        __threadfence();
+        __syncthreads();
+    }
+}
+
+// ---- collapse: dL/dtexture[r, c] = sum over levels k of dL/dlevel_k[ancestor] * (the product of the factors below k), top down
+__global__ __launch_bounds__(256) void mip_collapse_kernel(const float* __restrict__ gp, float* __restrict__ gt, MipParams p)
+{
+    const int Ct = p.Ct;
+    const long long n = (long long)p.Ht * p.Wt * Ct;
+    const int lgh = 31 - __clz(p.Ht), lgw = 31 - __clz(p.Wt);
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const long long t = e / Ct;
+        const int j = (int)(e - t * Ct);
+        const int r = (int)(t / p.Wt), c = (int)(t - (long long)r * p.Wt);
+        float acc = 0.f;
+        for (int k = p.L - 1; k >= 0; --k) {
+            const int rk = r >> min(k, lgh), ck = c >> min(k, lgw);
+            const float g = gp[p.off[k] + ((size_t)rk * mip_dim(p.Wt, k) + ck) * Ct + j];
+            if (k == p.L - 1) { acc = g; continue; }
+            const float factor = (mip_dim(p.Ht, k) > 1 && mip_dim(p.Wt, k) > 1) ? 0.25f : 0.5f;   // level k+1's block
+            acc = g + acc * factor;
+        }
+        gt[e] = acc;
+    }
+}
+
+// the bilinear sample of one level, the arithmetic of texture_forward_kernel
+template <int CT>
+__device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk, const Taps& k, int Ct, int ch, float (&o)[CT ? CT : 1])
+{
+    constexpr int NV = CT ? CT : 1;
+    float a[NV], b[NV], c[NV], d[NV];
+    load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c0) * Ct, Ct, a, ch); load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c1) * Ct, Ct, b, ch);
+    load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c0) * Ct, Ct, c, ch); load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c1) * Ct, Ct, d, ch);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const float ta = (a[j] * k.wc0) * k.wr0, tb = (b[j] * k.fc) * k.wr0, tc = (c[j] * k.wc0) * k.fr, td = (d[j] * k.fc) * k.fr;
+        o[j] = ((ta + tb) + tc) + td;
+    }
+}
+
+// the taps of level l for a level-0 index (and the derivatives of the level's index)
+__device__ __forceinline__ Taps mip_taps(const MipParams& p, int l, float row, float col, float& drow, float& dcol)
+{
+    if (l == 0) { drow = 1.f; dcol = 1.f; return bilinear_taps(row, col, p.Ht, p.Wt); }
+    const int Hk = mip_dim(p.Ht, l), Wk = mip_dim(p.Wt, l);
+    const float rk = mip_index(row, p.Ht, Hk, drow), ck = mip_index(col, p.Wt, Wk, dcol);
+    return bilinear_taps(rk, ck, Hk, Wk);
+}
+
+// ---- forward: one look-up per lane
+template <int CT>
+__global__ __launch_bounds__(256) void mip_forward_kernel(MipParams p)
+{
+    const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0;
+    const int Ct = CT ? CT : p.Ct;
+    constexpr int NV = CT ? CT : 1;
+    const long long n = p.rows * p.cols;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float u, v;
+        mip_uv(p, i, u, v);
+        float row, col, drow_dv, dcol_du;
+        uv_to_index(u, v, p.Ht, p.Wt, clamp_mode, row, col, drow_dv, dcol_du);
+        int l; float f;
+        mip_split(mip_lambda(p, i, u, v, clamp_mode), p.L, l, f);
+        float dr, dc;
+        const Taps k0 = mip_taps(p, l, row, col, dr, dc);
+        const float* __restrict__ lv0 = p.pyr + p.off[l];
+        const int W0 = mip_dim(p.Wt, l);
+        float* __restrict__ out = p.out + i * Ct;
+        if (f == 0.f) {
+            for (int ch = 0; ch < (CT ? 1 : Ct); ++ch) { float o[NV]; mip_sample<CT>(lv0, W0, k0, Ct, ch, o); store_ch<CT>(out, o, ch); }
+            continue;
+        }
+        const Taps k1 = mip_taps(p, l + 1, row, col, dr, dc);
+        const float* __restrict__ lv1 = p.pyr + p.off[l + 1];
+        const int W1 = mip_dim(p.Wt, l + 1);
+        const float g = 1.f - f;
+        for (int ch = 0; ch < (CT ? 1 : Ct); ++ch) {
+            float a[NV], b[NV], o[NV];
+            mip_sample<CT>(lv0, W0, k0, Ct, ch, a); mip_sample<CT>(lv1, W1, k1, Ct, ch, b);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) o[j] = g * a[j] + f * b[j];
+            store_ch<CT>(out, o, ch);
+        }
+    }
+}
+
+// ---- backward: the 16 x 16-tile scheme of texture_backward_kernel with one LDS patch per touched level.  A lane's look-up
+// has up to two tap sets: level l with weight 1 - f and level l + 1 with weight f (when f != 0).  Where the tile's sets span at
+// most two adjacent levels and both bounding boxes fit MIP_PATCH texels together, each set sums into its level's patch and
+// every patch texel goes to the scratch pyramid once; otherwise the sets scatter float atomics straight into it.
+template <int CT>
+__global__ __launch_bounds__(256) void mip_backward_kernel(MipParams p, int tw, int th, int tiles_x)
+{
+    constexpr int NV = CT ? CT : 1;
+    constexpr int LCT = CT ? CT : 4;
+    __shared__ float s_acc[MIP_PATCH * LCT];
+    __shared__ int s_box[10];   // lmin, lmax, then rmin, rmax, cmin, cmax of the two levels' taps
+    const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0;
+    const int Ct = CT ? CT : p.Ct;
+    const int tid = threadIdx.x;
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const long long px = (long long)tile_x * tw + tid % tw, py = (long long)tile_y * th + tid / tw;
+    const bool active = px < p.cols && py < p.rows;
+    const long long i = active ? py * p.cols + px : 0;
+    if (tid == 0) {
+        s_box[0] = 0x7fffffff; s_box[1] = -1;
+        for (int s = 0; s < 2; ++s) { s_box[2 + 4 * s] = 0x7fffffff; s_box[3 + 4 * s] = -1; s_box[4 + 4 * s] = 0x7fffffff; s_box[5 + 4 * s] = -1; }
+    }
+    float u = 0.f, v = 0.f;
+    if (active) mip_uv(p, i, u, v);
+    float row, col, drow_dv, dcol_du;
+    uv_to_index(u, v, p.Ht, p.Wt, clamp_mode, row, col, drow_dv, dcol_du);
+    float lam = 0.f;
+    if (active) lam = mip_lambda(p, i, u, v, clamp_mode);
+    int l; float f;
+    mip_split(lam, p.L, l, f);
+    const bool inside = lam > 0.f && lam < (float)(p.L - 1);        // d out / d lambda is S_{l+1} - S_l here, 0 where clamped
+    const bool want_lod = p.grad_lod && inside;
+    const bool two = f != 0.f;                                       // the second set carries weight
+    const bool read1 = two || want_lod;                              // ... or is read for the lod gradient only
+    float dr0, dc0, dr1 = 0.f, dc1 = 0.f;
+    const Taps k0 = mip_taps(p, l, row, col, dr0, dc0);
+    Taps k1 = k0;
+    if (read1) k1 = mip_taps(p, l + 1, row, col, dr1, dc1);
+    __syncthreads();
+    if (active) { atomicMin(&s_box[0], l); atomicMax(&s_box[1], two ? l + 1 : l); }
+    __syncthreads();
+    const int lmin = s_box[0];
+    const bool span = s_box[1] - lmin <= 1;
+    if (active && span) {
+        int* b0 = &s_box[2 + 4 * (l - lmin)];
+        atomicMin(&b0[0], k0.r0); atomicMax(&b0[1], k0.r1); atomicMin(&b0[2], k0.c0); atomicMax(&b0[3], k0.c1);
+        if (two) {
+            int* b1 = &s_box[2 + 4 * (l + 1 - lmin)];
+            atomicMin(&b1[0], k1.r0); atomicMax(&b1[1], k1.r1); atomicMin(&b1[2], k1.c0); atomicMax(&b1[3], k1.c1);
+        }
+    }
+    __syncthreads();
+    int pr0[2], pc0[2], pw[2], pbase[2];
+    int used = 0;
+    for (int s = 0; s < 2; ++s) {
+        const int bh = s_box[3 + 4 * s] - s_box[2 + 4 * s] + 1, bw = s_box[5 + 4 * s] - s_box[4 + 4 * s] + 1;
+        pr0[s] = s_box[2 + 4 * s]; pc0[s] = s_box[4 + 4 * s];
+        pw[s] = bh > 0 && bw > 0 ? bw : 0;
+        pbase[s] = used;
+        if (bh > 0 && bw > 0) used += (long long)bh * bw > MIP_PATCH ? MIP_PATCH + 1 : bh * bw;
+    }
+    const bool patch = span && used > 0 && used <= MIP_PATCH;   // (workgroup-uniform)
+    const float w0 = 1.f - f;
+    const float* __restrict__ lv0 = p.pyr + p.off[l];
+    const float* __restrict__ lv1 = p.pyr + p.off[read1 ? l + 1 : l];
+    float* __restrict__ gv0 = p.grad_pyr + p.off[l];
+    float* __restrict__ gv1 = p.grad_pyr + p.off[two ? l + 1 : l];
+    const int W0 = mip_dim(p.Wt, l), W1 = mip_dim(p.Wt, read1 ? l + 1 : l);
+    const int s0 = l - lmin, s1 = l + 1 - lmin;
+    float d_fr0 = 0.f, d_fc0 = 0.f, d_fr1 = 0.f, d_fc1 = 0.f, d_lod = 0.f;
+    const float* __restrict__ gout = p.grad_out + i * Ct;
+    for (int c0 = 0; c0 < Ct; c0 += LCT) {
+        const int nc = CT ? CT : min(LCT, Ct - c0);
+        if (patch) {
+            for (int e = tid; e < used * LCT; e += 256) s_acc[e] = 0.f;
+            __syncthreads();
+        }
+        if (active) {
+            float g[LCT];
+            if constexpr (CT != 0) { float q[NV]; load_ch<CT>(gout, Ct, q); for (int j = 0; j < NV; ++j) g[j] = q[j]; }
+            else { for (int j = 0; j < LCT; ++j) g[j] = j < nc ? gout[c0 + j] : 0.f; }
+            for (int set = 0; set < 2; ++set) {
+                if (set == 1 && !read1) break;
+                const Taps& k = set ? k1 : k0;
+                const float* __restrict__ lv = set ? lv1 : lv0;
+                float* __restrict__ gv = set ? gv1 : gv0;
+                const int Wk = set ? W1 : W0;
+                const float w = set ? f : w0;
+                const bool scatter = set == 0 || two;
+                const int ps = set ? s1 : s0;
+                const float w_tl = (k.wc0 * k.wr0) * w, w_tr = (k.fc * k.wr0) * w, w_bl = (k.wc0 * k.fr) * w, w_br = (k.fc * k.fr) * w;
+                const size_t o_tl = ((size_t)k.r0 * Wk + k.c0) * Ct + c0, o_tr = ((size_t)k.r0 * Wk + k.c1) * Ct + c0;
+                const size_t o_bl = ((size_t)k.r1 * Wk + k.c0) * Ct + c0, o_br = ((size_t)k.r1 * Wk + k.c1) * Ct + c0;
+                int l_tl = 0, l_tr = 0, l_bl = 0, l_br = 0;
+                if (patch && scatter) {
+                    const int b = pbase[ps], r0 = pr0[ps], cc0 = pc0[ps], bw = pw[ps];
+                    l_tl = (b + (k.r0 - r0) * bw + (k.c0 - cc0)) * LCT; l_tr = (b + (k.r0 - r0) * bw + (k.c1 - cc0)) * LCT;
+                    l_bl = (b + (k.r1 - r0) * bw + (k.c0 - cc0)) * LCT; l_br = (b + (k.r1 - r0) * bw + (k.c1 - cc0)) * LCT;
+                }
+#pragma unroll
+                for (int j = 0; j < LCT; ++j) {
+                    if (j >= nc) break;
+                    const float t_tl = lv[o_tl + j], t_tr = lv[o_tr + j], t_bl = lv[o_bl + j], t_br = lv[o_br + j];
+                    const float e_fr = g[j] * ((t_bl - t_tl) * k.wc0 + (t_br - t_tr) * k.fc);
+                    const float e_fc = g[j] * ((t_tr - t_tl) * k.wr0 + (t_br - t_bl) * k.fr);
+                    const float smp = ((t_tl * k.wc0) * k.wr0 + (t_tr * k.fc) * k.wr0) + ((t_bl * k.wc0) * k.fr + (t_br * k.fc) * k.fr);
+                    if (set) { d_fr1 += e_fr; d_fc1 += e_fc; d_lod += g[j] * smp; }
+                    else { d_fr0 += e_fr; d_fc0 += e_fc; d_lod -= g[j] * smp; }
+                    if (!scatter) continue;
+                    if (patch) {
+                        atomicAdd(&s_acc[l_tl + j], g[j] * w_tl); atomicAdd(&s_acc[l_tr + j], g[j] * w_tr);
+                        atomicAdd(&s_acc[l_bl + j], g[j] * w_bl); atomicAdd(&s_acc[l_br + j], g[j] * w_br);
+                    } else {
+                        atomicAdd(&gv[o_tl + j], g[j] * w_tl); atomicAdd(&gv[o_tr + j], g[j] * w_tr);
+                        atomicAdd(&gv[o_bl + j], g[j] * w_bl); atomicAdd(&gv[o_br + j], g[j] * w_br);
+                    }
+                }
+            }
+        }
+        if (patch) {
+            __syncthreads();
+            for (int e = tid; e < used * LCT; e += 256) {
+                const float val = s_acc[e];
+                const int j = e % LCT, t = e / LCT;
+                if (val != 0.f && j < nc) {
+                    const int s = t >= pbase[1] && pw[1] > 0 ? 1 : 0;
+                    const int lt = t - pbase[s], r = lt / pw[s], c = lt - r * pw[s];
+                    const int lev = lmin + s;
+                    atomicAdd(&p.grad_pyr[p.off[lev] + ((size_t)(pr0[s] + r) * mip_dim(p.Wt, lev) + (pc0[s] + c)) * Ct + c0 + j], val);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (!active) return;
+    if (p.grad_uvs) {   // floor() has zero gradient: d frac / d index_k = 1, d index_k / d index_0 = 1 / s (0 where the max clamps)
+        const float gu = (d_fc0 * dc0) * w0 + (two ? (d_fc1 * dc1) * f : 0.f);
+        const float gvv = (d_fr0 * dr0) * w0 + (two ? (d_fr1 * dr1) * f : 0.f);
+        p.grad_uvs[i * p.guv_stride] = gu * dcol_du;
+        p.grad_uvs[i * p.guv_stride + 1] = gvv * drow_dv;
+    }
+    if (p.grad_lod) p.grad_lod[i] = want_lod ? d_lod : 0.f;
+}
+
+int mip_level_count(int Ht, int Wt, int max_level)
+{
+    int L = 1;
+    int h = Ht, w = Wt;
+    while (L < MIP_MAX && !(h == 1 && w == 1) && (h == 1 || h % 2 == 0) && (w == 1 || w % 2 == 0) && (max_level < 0 || L <= max_level)) {
+        h = h > 1 ? h / 2 : 1; w = w > 1 ? w / 2 : 1; ++L;
+    }
+    return L;
+}
+
+void mip_offsets(MipParams& p)
+{
+    long long o = 0;
+    for (int k = 0; k < MIP_MAX; ++k) {
+        p.off[k] = o;
+        if (k < p.L) o += (long long)mip_dim(p.Ht, k) * mip_dim(p.Wt, k) * p.Ct;
+    }
+}
+
+}  // namespace dirt
+
+extern "C" {
+
+static char* mip_err() { return const_cast<char*>(dirt_texture_last_error()); }   // dirt_texture.hip's thread-local message
+#define MIP_FAIL(...) do { snprintf(mip_err(), 256, __VA_ARGS__); return DIRT_E_INVALID_ARGUMENT; } while (0)
+
+int dirt_texture_mip_levels(int Ht, int Wt, int Ct, int max_level, long long* pyramid_floats)
+{
+    if (Ht <= 0 || Wt <= 0 || Ct <= 0) MIP_FAIL("dirt_texture_mip_levels: bad sizes (Ht=%d Wt=%d Ct=%d)", Ht, Wt, Ct);
+    dirt::MipParams p{};
+    p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.L = dirt::mip_level_count(Ht, Wt, max_level);
+    dirt::mip_offsets(p);
+    if (pyramid_floats) *pyramid_floats = p.L < dirt::MIP_MAX ? p.off[p.L] : p.off[p.L - 1] + (long long)dirt::mip_dim(Ht, p.L - 1) * dirt::mip_dim(Wt, p.L - 1) * Ct;
+    mip_err()[0] = 0;
+    return p.L;
+}
+
+static int mip_check(const char* who, int Ht, int Wt, int Ct, int levels, dirt::MipParams& p)
+{
+    if (Ht <= 0 || Wt <= 0 || Ct <= 0) MIP_FAIL("%s: bad sizes (Ht=%d Wt=%d Ct=%d)", who, Ht, Wt, Ct);
+    if (levels < 1 || levels > dirt::mip_level_count(Ht, Wt, -1))
+        MIP_FAIL("%s: %d levels, a %d x %d texture has 1..%d", who, levels, Ht, Wt, dirt::mip_level_count(Ht, Wt, -1));
+    p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.L = levels;
+    dirt::mip_offsets(p);
+    return DIRT_OK;
+}
+
+static int mip_hip(const char* who, hipError_t e)
+{
+    if (e != hipSuccess) { snprintf(mip_err(), 256, "%s: %s", who, hipGetErrorString(e)); return DIRT_E_HIP; }
+    mip_err()[0] = 0;
+    return DIRT_OK;
+}
+
+int dirt_texture_mip_build(const float* texture, float* pyramid, int Ht, int Wt, int Ct, int levels, void* stream)
+{
+    const char* who = "dirt_texture_mip_build";
+    dirt::MipParams p{};
+    int rc = mip_check(who, Ht, Wt, Ct, levels, p);
+    if (rc) return rc;
+    if (!texture || !pyramid) MIP_FAIL("%s: texture / pyramid is NULL", who);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (levels == 1) return mip_hip(who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct, hipMemcpyDeviceToDevice, s));
+    const int kt = min(levels - 1, dirt::MIP_TILE_LEVELS);
+    const int tiles_y = dirt::mip_dim(Ht, kt), tiles_x = dirt::mip_dim(Wt, kt);
+    if ((long long)tiles_x * tiles_y > 0x7fffffffll) MIP_FAIL("%s: texture too large", who);
+    hipLaunchKernelGGL(dirt::mip_build_blocks_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
+    if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel, dim3(1), dim3(1024), 0, s, pyramid, p, kt);
+    return mip_hip(who, hipGetLastError());
+}
+
+int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
+{
+    const char* who = "dirt_texture_mip_collapse";
+    dirt::MipParams p{};
+    int rc = mip_check(who, Ht, Wt, Ct, levels, p);
+    if (rc) return rc;
+    if (!grad_pyramid || !grad_texture) MIP_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
+    const long long n = (long long)Ht * Wt * Ct;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(dirt::mip_collapse_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), grad_pyramid, grad_texture, p);
+    return mip_hip(who, hipGetLastError());
+}
+
+static int mip_sample_check(const char* who, const float* pyramid, const float* uvs, const float* lod, long long rows, long long cols,
+                            int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride, const float* mask,
+                            dirt::MipParams& p)
+{
+    int rc = mip_check(who, Ht, Wt, Ct, levels, p);
+    if (rc) return rc;
+    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) MIP_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
+    if (image_rows < 1 || (rows > 0 && rows % image_rows)) MIP_FAIL("%s: image_rows=%d does not divide rows=%lld", who, image_rows, rows);
+    if (uv_stride < 2) MIP_FAIL("%s: uv_stride < 2", who);
+    if (mask && mask_stride < 1) MIP_FAIL("%s: mask_stride < 1", who);
+    if (rows * cols > 0 && (!pyramid || !uvs)) MIP_FAIL("%s: pyramid / uvs is NULL", who);
+    p.pyr = pyramid; p.uvs = uvs; p.lod = lod; p.mask = lod ? nullptr : mask; p.rows = rows; p.cols = cols; p.image_rows = image_rows;
+    p.uv_stride = uv_stride; p.mask_stride = mask_stride;
+    return DIRT_OK;
+}
+
+int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, long long rows,
+                                    long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride,
+                                    float lod_bias, unsigned flags, void* stream)
+{
+    const char* who = "dirt_texture_sample_mip_forward";
+    dirt::MipParams p{};
+    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
+    if (rc) return rc;
+    if (flags & DIRT_TEX_NEAREST) MIP_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
+    const long long n = rows * cols;
+    if (n > 0 && !out) MIP_FAIL("%s: out is NULL", who);
+    if (n == 0) { mip_err()[0] = 0; return DIRT_OK; }
+    p.lod_bias = lod_bias; p.flags = flags; p.out = out;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    if (Ct == 4 && a16) hipLaunchKernelGGL(dirt::mip_forward_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else if (Ct == 3) hipLaunchKernelGGL(dirt::mip_forward_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else if (Ct == 1) hipLaunchKernelGGL(dirt::mip_forward_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(dirt::mip_forward_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    return mip_hip(who, hipGetLastError());
+}
+
+int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
+                                     float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, long long rows, long long cols,
+                                     int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
+                                     float lod_bias, unsigned flags, void* stream)
+{
+    const char* who = "dirt_texture_sample_mip_backward";
+    dirt::MipParams p{};
+    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
+    if (rc) return rc;
+    if (flags & DIRT_TEX_NEAREST) MIP_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
+    if (!grad_pyramid || !grad_texture) MIP_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
+    const long long n = rows * cols;
+    if (n > 0 && !grad_out) MIP_FAIL("%s: grad_out is NULL", who);
+    if (grad_uvs && grad_uv_stride < 2) MIP_FAIL("%s: grad_uv_stride < 2", who);
+    if (grad_lod && !lod) MIP_FAIL("%s: grad_lod needs lod", who);
+    p.lod_bias = lod_bias; p.flags = flags; p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod;
+    p.guv_stride = grad_uv_stride;
+    const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
+    const long long tiles_x = (cols + tw - 1) / tw, tiles_y = (rows + th - 1) / th;
+    if (tiles_x * tiles_y > 0x7fffffffll) MIP_FAIL("%s: pixel grid too large", who);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long pyr_floats = p.off[levels - 1] + (long long)dirt::mip_dim(Ht, levels - 1) * dirt::mip_dim(Wt, levels - 1) * Ct;
+    hipError_t e = hipMemsetAsync(grad_pyramid, 0, sizeof(float) * (size_t)pyr_floats, s);
+    if (e != hipSuccess) return mip_hip(who, e);
+    if (n > 0) {
+        const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
+        const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
+        if (Ct == 4 && a16) hipLaunchKernelGGL(dirt::mip_backward_kernel<4>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        else if (Ct == 3) hipLaunchKernelGGL(dirt::mip_backward_kernel<3>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        else if (Ct == 1) hipLaunchKernelGGL(dirt::mip_backward_kernel<1>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        else hipLaunchKernelGGL(dirt::mip_backward_kernel<0>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        e = hipGetLastError();
+        if (e != hipSuccess) return mip_hip(who, e);
+    }
+    return dirt_texture_mip_collapse(grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
+}
+
+}  // extern "C"

@@ -4,7 +4,12 @@
 mode), filter)` and one for its gradient (include/dirt_hip.h: dirt_texture_sample_forward / _backward), reading the
 (u, v) pairs in place from a G-buffer slice.  `uvs_to_pixel_indices` and `sample_texture` are the reference's two
 functions over torch tensors (same names and arguments), kept for scripts that call them separately; both routes give
-the same values bit for bit."""
+the same values bit for bit.
+
+`filter='trilinear'` samples a mip pyramid (`mip_pyramid`) at a level of detail given per look-up or taken from the
+screen-space footprint of the (u, v) image (dirt_texture_mip.hip; specification in DESIGN.md §7)."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -109,10 +114,20 @@ class _SampleTextureUV(torch.autograd.Function):
         return grad_texture, grad_uvs, None
 
 
-def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear'):
+def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear', *, lod=None, lod_bias=0.0, mask=None, max_level=None):
     """Fused `sample_texture(texture, uvs_to_pixel_indices(uvs, texture.shape[:2], mode), filter)`
     (samples/textured.py:16-61, as its shader_fn uses them, :116-141): texture [Ht, Wt, C] float32, uvs [*, 2] with
-    (0, 0) at the top-left of the image -> [*, C].  Differentiable with respect to the texture and the coordinates."""
+    (0, 0) at the top-left of the image -> [*, C].  Differentiable with respect to the texture and the coordinates.
+
+    filter='trilinear' blends bilinear samples of two adjacent levels of the texture's mip pyramid.  The
+    level of detail is `lod` + `lod_bias` when `lod` (shaped like uvs[..., 0]) is given, else log2 of the screen-space
+    footprint of (u, v) + `lod_bias`, which needs `uvs` as images [..., H, W, 2]; `mask` [..., H, W] (e.g. gbuffer[..., 0],
+    read in place) marks the pixels whose (u, v) count as neighbours.  `max_level` caps the pyramid.  Also differentiable
+    with respect to `lod`; the footprint's level is held constant.  The four keyword arguments apply to 'trilinear' only."""
+    if filter == 'trilinear':
+        return _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level)
+    if lod is not None or lod_bias != 0.0 or mask is not None or max_level is not None:
+        raise ValueError("lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
     flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode] | {'bilinear': 0, 'nearest': _lib.TEX_NEAREST}[filter]
     if texture.dim() != 3:
         raise ValueError('sample_texture_uv expects texture to be 3D [height, width, channels], got shape %s' % (tuple(texture.shape),))
@@ -121,3 +136,165 @@ def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear'):
     if texture.device != uvs.device:
         raise ValueError('texture and uvs must be on the same device (%s vs %s)' % (texture.device, uvs.device))
     return _SampleTextureUV.apply(texture.to(torch.float32), uvs.to(torch.float32), flags)
+
+
+# ---- mip pyramid and trilinear look-up (dirt_texture_mip.hip) ----------------------------------------------------------
+
+def _mip_geometry(ht, wt, ct, max_level):
+    """-> (level count, packed floats, [(offset, H_k, W_k)] per level) of the pyramid of an ht x wt x ct texture."""
+    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
+        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+    lib = _lib.load()
+    floats = ctypes.c_longlong(0)
+    levels = lib.dirt_texture_mip_levels(ht, wt, ct, -1 if max_level is None else max_level, ctypes.byref(floats))
+    if levels < 1:
+        raise ValueError(lib.dirt_texture_last_error().decode())
+    geo, off = [], 0
+    for k in range(levels):
+        h, w = max(ht >> k, 1), max(wt >> k, 1)
+        geo.append((off, h, w))
+        off += h * w * ct
+    assert off == floats.value
+    return levels, floats.value, geo
+
+
+def _check_texture(texture, who):
+    if texture.dim() != 3:
+        raise ValueError('%s expects texture to be 3D [height, width, channels], got shape %s' % (who, tuple(texture.shape)))
+    if not texture.is_cuda:
+        raise RuntimeError('dirt_amd.texture.%s runs on an MI355X only; there is no CPU fallback' % who)
+
+
+class _MipPyramid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, texture, levels, floats):
+        lib = _lib.load()
+        texture = texture.contiguous()
+        ht, wt, ct = (int(d) for d in texture.shape)
+        pyr = torch.empty(floats, dtype=torch.float32, device=texture.device)
+        with _ops._on_device(texture.device):
+            rc = lib.dirt_texture_mip_build(texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(texture.device))
+        if rc:
+            raise ValueError(lib.dirt_texture_last_error().decode())
+        ctx.meta = (ht, wt, ct, levels)
+        return pyr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_pyr):
+        lib = _lib.load()
+        ht, wt, ct, levels = ctx.meta
+        grad_pyr = grad_pyr.contiguous().to(torch.float32)
+        grad_texture = torch.empty((ht, wt, ct), dtype=torch.float32, device=grad_pyr.device)
+        with _ops._on_device(grad_pyr.device):
+            rc = lib.dirt_texture_mip_collapse(grad_pyr.data_ptr(), grad_texture.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(grad_pyr.device))
+        if rc:
+            raise ValueError(lib.dirt_texture_last_error().decode())
+        return grad_texture, None, None
+
+
+def mip_pyramid(texture, max_level=None):
+    """texture [Ht, Wt, C] -> [level 0, level 1, ...]: each level [max(Ht >> k, 1), max(Wt >> k, 1), C] the 2 x 2 (or 2 x 1)
+    means of the one below, while every dimension is even or 1 and up to `max_level`.  The levels are views
+    into one packed buffer (level 0 a copy of the texture); differentiable with respect to the texture."""
+    _check_texture(texture, 'mip_pyramid')
+    ht, wt, ct = (int(d) for d in texture.shape)
+    levels, floats, geo = _mip_geometry(ht, wt, ct, max_level)
+    packed = _MipPyramid.apply(texture.to(torch.float32), levels, floats)
+    return [packed[o:o + h * w * ct].view(h, w, ct) for (o, h, w) in geo]
+
+
+def _scalars_in_place(x):
+    """(tensor to pass, element stride between consecutive values) for a float32 tensor whose elements lie a constant stride
+    apart in row-major order (a slice `gbuffer[..., 0]` of a contiguous G-buffer); anything else is made contiguous float32."""
+    if x.dtype == torch.float32 and x.dim() >= 1:
+        step = x.stride(-1)
+        ok = step >= 1
+        expect = step
+        for d in range(x.dim() - 1, -1, -1):
+            if x.shape[d] != 1 and x.stride(d) != expect:
+                ok = False
+                break
+            expect *= x.shape[d]
+        if ok:
+            return x, step
+    return x.to(torch.float32).contiguous(), 1
+
+
+class _SampleTextureMip(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, texture, uvs, lod, mask, flags, lod_bias, max_level):
+        lib = _lib.load()
+        texture = texture.contiguous()
+        ht, wt, ct = (int(d) for d in texture.shape)
+        levels, floats, _ = _mip_geometry(ht, wt, ct, max_level)
+        src, stride = _pairs_in_place(uvs)
+        n = uvs.numel() // 2
+        cols = int(uvs.shape[-2]) if uvs.dim() >= 3 else n
+        rows = n // cols if cols else 0
+        image_rows = int(uvs.shape[-3]) if lod is None and rows else 1
+        lod_t = lod.to(torch.float32).contiguous() if lod is not None else None
+        mask_t, mask_stride = _scalars_in_place(mask) if mask is not None else (None, 1)
+        pyr = torch.empty(floats, dtype=torch.float32, device=texture.device)
+        out = torch.empty(tuple(uvs.shape[:-1]) + (ct,), dtype=torch.float32, device=texture.device)
+        stream = _ops._stream_handle(texture.device)
+        with _ops._on_device(texture.device):
+            rc = lib.dirt_texture_mip_build(texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels, stream)
+            if not rc:
+                rc = lib.dirt_texture_sample_mip_forward(pyr.data_ptr(), src.data_ptr(), lod_t.data_ptr() if lod_t is not None else None,
+                                                         mask_t.data_ptr() if mask_t is not None else None, out.data_ptr(), rows, cols,
+                                                         image_rows, ht, wt, ct, levels, stride, mask_stride, float(lod_bias), flags, stream)
+        if rc:
+            raise ValueError(lib.dirt_texture_last_error().decode())
+        ctx.save_for_backward(pyr, src, lod_t, mask_t)
+        ctx.meta = (stride, mask_stride, flags, float(lod_bias), tuple(uvs.shape), rows, cols, image_rows, ht, wt, ct, levels, floats)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        pyr, src, lod_t, mask_t = ctx.saved_tensors
+        stride, mask_stride, flags, lod_bias, uv_shape, rows, cols, image_rows, ht, wt, ct, levels, floats = ctx.meta
+        dev = pyr.device
+        grad_out = grad_out.contiguous().to(torch.float32)
+        scratch = torch.empty(floats, dtype=torch.float32, device=dev)    # the pyramid-shaped gradient, cleared by the call
+        grad_texture = torch.empty((ht, wt, ct), dtype=torch.float32, device=dev)
+        grad_uvs = torch.empty(uv_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        grad_lod = torch.empty(uv_shape[:-1], dtype=torch.float32, device=dev) if lod_t is not None and ctx.needs_input_grad[2] else None
+        with _ops._on_device(dev):
+            rc = lib.dirt_texture_sample_mip_backward(pyr.data_ptr(), src.data_ptr(), lod_t.data_ptr() if lod_t is not None else None,
+                                                      mask_t.data_ptr() if mask_t is not None else None, grad_out.data_ptr(), scratch.data_ptr(),
+                                                      grad_texture.data_ptr(), grad_uvs.data_ptr() if grad_uvs is not None else None,
+                                                      grad_lod.data_ptr() if grad_lod is not None else None, rows, cols, image_rows,
+                                                      ht, wt, ct, levels, stride, 2, mask_stride, lod_bias, flags, _ops._stream_handle(dev))
+        if rc:
+            raise ValueError(lib.dirt_texture_last_error().decode())
+        return grad_texture, grad_uvs, grad_lod, None, None, None, None
+
+
+def _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level):
+    flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode]
+    if texture.dim() != 3:
+        raise ValueError('sample_texture_uv expects texture to be 3D [height, width, channels], got shape %s' % (tuple(texture.shape),))
+    if uvs.dim() < 1 or uvs.shape[-1] != 2:
+        raise ValueError('sample_texture_uv expects uvs of shape [..., 2], got %s' % (tuple(uvs.shape),))
+    if texture.device != uvs.device:
+        raise ValueError('texture and uvs must be on the same device (%s vs %s)' % (texture.device, uvs.device))
+    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
+        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+    for name, x in (('lod', lod), ('mask', mask)):
+        if x is None:
+            continue
+        if not isinstance(x, torch.Tensor) or tuple(x.shape) != tuple(uvs.shape[:-1]):
+            raise ValueError('%s must be a tensor shaped like uvs[..., 0] %s, got %s' % (name, tuple(uvs.shape[:-1]), tuple(getattr(x, 'shape', ()))))
+        if x.device != uvs.device:
+            raise ValueError('%s and uvs must be on the same device (%s vs %s)' % (name, x.device, uvs.device))
+    if lod is None and uvs.dim() < 3:
+        raise ValueError("filter='trilinear' without lod takes the level of detail from neighbouring pixels: uvs must be images "
+                         "[..., H, W, 2], got %s" % (tuple(uvs.shape),))
+    if lod is not None and mask is not None:
+        raise ValueError('mask marks the neighbours of the footprint level of detail; it does not apply with an explicit lod')
+    if not (texture.is_cuda and uvs.is_cuda):
+        raise RuntimeError('dirt_amd.texture.sample_texture_uv runs on an MI355X only; there is no CPU fallback')
+    return _SampleTextureMip.apply(texture.to(torch.float32), uvs.to(torch.float32), lod, mask, flags, float(lod_bias), max_level)

@@ -219,7 +219,7 @@ int dirt_state_grad_buffers(void *workspace, size_t workspace_bytes, int B, int 
  *   uv_stride = C and the pointer at the u channel; out [n,Ct].
  * Backward: grad_out [n,Ct] -> grad_texture [Ht,Wt,Ct] (cleared by the call, then accumulated with float atomics) and
  * grad_uvs (n pairs `grad_uv_stride` apart; may be NULL).
- * dirt_texture_last_error(): thread-local description of the last failure of these two calls.
+ * dirt_texture_last_error(): thread-local description of the last failure of these calls (and of the trilinear ones below).
  */
 #define DIRT_TEX_CLAMP 1u   /* mode 'clamp' instead of 'repeat' (samples/textured.py:21-24) */
 #define DIRT_TEX_NEAREST 2u /* mode 'nearest' instead of 'bilinear' (samples/textured.py:31-33) */
@@ -237,6 +237,41 @@ int dirt_texture_sample_backward_image(const float *texture, const float *uvs, c
                                        float *grad_uvs, long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride,
                                        int grad_uv_stride, unsigned flags, void *stream);
 const char *dirt_texture_last_error(void);
+
+/*
+ * Trilinear (mipmapped) texture look-up.  Extends the bilinear look-up above (samples/textured.py:16-61) with a mip
+ * pyramid and a level of detail (LOD) from the screen-space footprint of (u, v); specification in
+ * dirt_amd/csrc/dirt_texture_mip.hip and DESIGN.md §7.  The pyramid is one packed buffer: level k [max(Ht >> k, 1),
+ * max(Wt >> k, 1), Ct] after level k - 1, level 0 a copy of the texture.  All calls return 0 or DIRT_E_*; failures are
+ * described by dirt_texture_last_error().  The library keeps no device state: pyramids and scratch belong to the caller.
+ *
+ * dirt_texture_mip_levels: the level count of an Ht x Wt texture (levels halve while each dimension is even or 1, up to
+ * `max_level`, < 0: no limit; samples/textured.py:16-61 has one level) as the return value (>= 1), and the packed
+ * pyramid's size in floats in *pyramid_floats (may be NULL).
+ */
+int dirt_texture_mip_levels(int Ht, int Wt, int Ct, int max_level, long long *pyramid_floats);
+/* The pyramid of `texture` [Ht,Wt,Ct] (the texture of samples/textured.py:16-61) into `pyramid` (pyramid_floats floats):
+ * 2 x 2 (or 2 x 1) means in float32; one launch for levels 0-5, one more for any above. */
+int dirt_texture_mip_build(const float *texture, float *pyramid, int Ht, int Wt, int Ct, int levels, void *stream);
+/* The gradient of dirt_texture_mip_build (samples/textured.py:16-61's texture gradient through the pyramid):
+ * grad_pyramid (packed) -> grad_texture [Ht,Wt,Ct], fully written, in one launch. */
+int dirt_texture_mip_collapse(const float *grad_pyramid, float *grad_texture, int Ht, int Wt, int Ct, int levels, void *stream);
+/* The trilinear look-up (extends samples/textured.py:16-61): rows x cols look-ups, row-major, stacked images of
+ * `image_rows` rows each (a flat list: rows = image_rows = 1); (u, v) pairs `uv_stride` floats apart, read in place.
+ * `lod` (rows x cols floats) gives lambda = lod + lod_bias; NULL takes lambda from the footprint of neighbouring look-ups
+ * of the same image, skipping pixels whose `mask` (rows x cols, `mask_stride` floats apart; NULL: all valid) is 0.
+ * flags: DIRT_TEX_CLAMP. */
+int dirt_texture_sample_mip_forward(const float *pyramid, const float *uvs, const float *lod, const float *mask, float *out,
+                                    long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels,
+                                    int uv_stride, int mask_stride, float lod_bias, unsigned flags, void *stream);
+/* Its gradient (extends samples/textured.py:16-61's): grad_out [rows*cols,Ct] -> grad_texture [Ht,Wt,Ct] (fully written),
+ * grad_uvs (pairs `grad_uv_stride` apart; may be NULL) and grad_lod (rows*cols; may be NULL, needs `lod`).
+ * `grad_pyramid` is caller-owned scratch of pyramid_floats floats (cleared by the call); lambda is held constant. */
+int dirt_texture_sample_mip_backward(const float *pyramid, const float *uvs, const float *lod, const float *mask,
+                                     const float *grad_out, float *grad_pyramid, float *grad_texture, float *grad_uvs,
+                                     float *grad_lod, long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct,
+                                     int levels, int uv_stride, int grad_uv_stride, int mask_stride, float lod_bias,
+                                     unsigned flags, void *stream);
 
 /*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
