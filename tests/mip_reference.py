@@ -194,14 +194,16 @@ def grad(texture, uvs, grad_out, mode='repeat', lod=None, lod_bias=0.0, mask=Non
     n = len(uv2)
     d_u, d_v, m_u, m_v = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
     sval, smag = [], []
+    two = f != 0   # spec 4: where f == 0 only S_l is read and written (a NaN look-up must not put NaN * 0 into level l + 1)
     for s, (lv, wl) in enumerate(((lev, 1.0 - f), (np.minimum(lev + 1, L - 1), f))):
         look = _Look(pyr, lv, idx[:, 0], idx[:, 1], np.float32)
         fr, fc = look.fr.astype(np.float64), look.fc.astype(np.float64)
         taps = ((look.r0, look.c0, (1 - fc) * (1 - fr)), (look.r0, look.c1, fc * (1 - fr)), (look.r1, look.c0, (1 - fc) * fr), (look.r1, look.c1, fc * fr))
+        sc = slice(None) if s == 0 else two
         for (r, c, w) in taps:
-            fi = look.flat(r, c, ct)
-            np.add.at(gp, fi, g * (w * wl)[:, None])
-            np.add.at(mp, fi, np.abs(g * (w * wl)[:, None]))
+            fi = look.flat(r, c, ct)[sc]
+            np.add.at(gp, fi, (g * (w * wl)[:, None])[sc])
+            np.add.at(mp, fi, np.abs(g * (w * wl)[:, None])[sc])
         t = [packed[look.flat(r, c, ct)] for (r, c, _) in taps]   # tl, tr, bl, br
         tl, tr, bl, br = t
         d_fr = (g * ((bl - tl) * (1 - fc)[:, None] + (br - tr) * fc[:, None])).sum(-1)
@@ -209,8 +211,12 @@ def grad(texture, uvs, grad_out, mode='repeat', lod=None, lod_bias=0.0, mask=Non
         a = np.abs
         mf_r = (a(g) * ((a(bl) + a(tl)) * (1 - fc)[:, None] + (a(br) + a(tr)) * fc[:, None])).sum(-1)
         mf_c = (a(g) * ((a(tr) + a(tl)) * (1 - fr)[:, None] + (a(br) + a(bl)) * fr[:, None])).sum(-1)
-        d_v += d_fr * look.drow * wl; d_u += d_fc * look.dcol * wl
-        m_v += mf_r * look.drow * a(wl); m_u += mf_c * look.dcol * a(wl)
+        if s == 0:
+            d_v += d_fr * look.drow * wl; d_u += d_fc * look.dcol * wl
+            m_v += mf_r * look.drow * a(wl); m_u += mf_c * look.dcol * a(wl)
+        else:   # level l + 1 adds to (u, v) only where it carries weight, as it is scattered only there
+            d_v += np.where(two, d_fr * look.drow * wl, 0.0); d_u += np.where(two, d_fc * look.dcol * wl, 0.0)
+            m_v += np.where(two, mf_r * look.drow * a(wl), 0.0); m_u += np.where(two, mf_c * look.dcol * a(wl), 0.0)
         sval.append(sum(tt * ww[:, None] for tt, (_, _, ww) in zip(t, taps)))
         smag.append(sum(a(tt) * ww[:, None] for tt, (_, _, ww) in zip(t, taps)))
     u, v = uv2[:, 0], uv2[:, 1]
