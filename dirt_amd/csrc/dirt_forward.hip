@@ -445,11 +445,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
                 if (box.i_max >= rx0 && box.i_min <= rx0 + 15 && box.r_max >= ry0 && box.r_min <= ry0 + RH - 1) {
                     const uint32_t rowbits = (bx0 == 0 ? 1u : 0u) | (bx1 == 1 ? 2u : 0u);
                     mym4 = (by0 == 0 ? rowbits : 0u) | (NBY == 2 && by1 == 1 ? rowbits << 2 : 0u);
-#ifndef DIRT_NO_BLOCK_CULL
                     // ... minus the blocks the TRIANGLE misses although its box touches them (cull_blocks, dirt_raster_common.h;
                     // face-local record: offsets from the top-left sample of the face's box)
                     mym4 = cull_blocks<NB, NBY>(s_rec[idx], mym4, (float)(rx0 - (int)box.i_min), (float)((int)box.r_min - ry0));
-#endif
                 }
             }
             unsigned long long m = __builtin_amdgcn_ballot_w64(mym4 != 0);
@@ -625,14 +623,8 @@ hipError_t launch_raster_v2(const RasterParams& p_in, int B, bool visibility_onl
     }
     // half-size waves (eight per workgroup) where (nearly) every workgroup of the launch is resident at once -- four 512-thread
     // workgroups per compute unit --: such a launch ends with its heaviest wave (profiles/EXPERIMENTS.md round 6)
-#ifdef DIRT_V2_NO_W8
-    const bool w8 = false;
-#elif defined(DIRT_V2_W8_ALWAYS)   // (A/B build)
-    const bool w8 = !visibility_only;
-#else
     const bool pinned8 = (p.flags & (DIRT_FLAG_TILES_LARGE | DIRT_FLAG_TILES_SMALL)) == (DIRT_FLAG_TILES_LARGE | DIRT_FLAG_TILES_SMALL);
     const bool w8 = !visibility_only && (pinned8 || ((size_t)grid.x * grid.y <= 2048 && !(p.flags & DIRT_FLAG_TILES_LARGE)));   // (measured: 1024 tiles -2 us, 2048 -1.5, 4096 and more +5...10)
-#endif
 #define V2_ARGS p.cells, p.nchunk, p.tiles_x, p.tiles_y, p.tiles_x_magic, p.grid.shift, p.grid.bins_x, p.grid.big, p.grid.cell_chunk_stride, p
     if (visibility_only) hipLaunchKernelGGL((raster_kernel_v2<1, 4>), grid, dim3(RTHREADS), 0, stream, V2_ARGS);
     else if (w8 && p.C == 4) hipLaunchKernelGGL((raster_kernel_v2<0, 4, 8>), grid, dim3(512), 0, stream, V2_ARGS);

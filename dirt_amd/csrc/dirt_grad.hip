@@ -33,26 +33,12 @@
 #include "dirt_grad_common.h"
 #include "../../include/dirt_hip.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace dirt {
 
-// Preprocessor switches: none is defined for the product library (dirt_amd/build.py).  They exist so that the A/B and
-// knock-out figures of profiles/EXPERIMENTS.md can be reproduced (tools/variants.sh builds a library per flag set,
-// tools/ab.sh times it):  DIRT_TRACE (per-wave phase timestamps, tools/trace_grad.py);  DIRT_GRAD_NO_ATOMICS,
-// DIRT_KO_LOADS / _PIX / _G / _GBK / _LOOP (knock-outs: wrong results by design);  DIRT_GBK_COALESCED=0, DIRT_NO_WIDE6,
-// DIRT_NO_TWO3 (the previous form of a change that was kept: same results, slower).
-#ifndef DIRT_GBK_COALESCED
-#define DIRT_GBK_COALESCED 1
-#endif
-#ifndef DIRT_ALIAS_INBOX
-#define DIRT_ALIAS_INBOX 1
-#endif
-#ifndef DIRT_TWO3_WAVES
-#define DIRT_TWO3_WAVES (DIRT_ALIAS_INBOX ? 4 : 3)   // waves per SIMD the {3,3} many-channel shape is register-allocated for
-#endif
+// Preprocessor switch: DIRT_TRACE, per-wave phase timestamps (s_memtime) for tools/trace_grad.py.  Only the tracing build of
+// the library defines it (tools/build_tools.sh); the product library (dirt_amd/build.py) never does.
 #ifdef DIRT_TRACE
-// Per-wave phase timestamps (s_memtime) for tools/trace_grad.py; compiled only into the tracing build of the library.
 __device__ long long* g_trace_grad = nullptr;
 extern "C" void dirt_debug_set_trace_grad(void* p)
 {
@@ -77,9 +63,10 @@ constexpr int VS = 36;                  // state tile row stride (float2): colum
 constexpr int IS = 34;                  // inbox row stride (float2 cells): cell (ty + 1) * 34 + tx + 2 for ty in -1..8, tx in -1..32
 constexpr int ICELLS = 10 * IS + 4;     // ... of a wave's 32 x 8 region and the one-pixel ring around it (a multiple of 2: 16-byte cells pairs)
 constexpr int RING = 2 * 34 + 2 * 8;    // ring cells: what the wave's pixels sent to pixels of other waves
+constexpr int TWO3_WAVES = 4;           // waves per SIMD the {3,3} many-channel shape is register-allocated for
 
 // grad_kernel<CSPEC, STRIDED>: a workgroup works on CSPEC = 1, 3, 4 or 6 channels (4 = a 3-channel group and a single;
-// 6 = two 3-channel groups, STRIDED only: three workgroups per compute unit, but every 64-byte pixel of a many-channel
+// 6 = two 3-channel groups, STRIDED only: four workgroups per compute unit, but every 64-byte pixel of a many-channel
 // image is fetched by half as many passes) of one tile.  Not STRIDED: that is the image's channel count, a compile-time constant (4: with 16-byte aligned pixel
 // tensors).  STRIDED: any channel count, cut into PASSES of whole channel groups (dirt/rasterise_ops.py:148-152): the
 // launch covers p.npasses passes of this shape, starting at channel p.c_first, and a workgroup takes one (tile, pass)
@@ -95,7 +82,7 @@ constexpr int RING = 2 * 34 + 2 * 8;    // ring cells: what the wave's pixels se
 // workgroup barrier, 11 KB of LDS and twelve registers less -- one workgroup more per compute unit, which pays when the grid
 // takes several rounds (launch_grad).
 template <int CSPEC, bool STRIDED, bool DEBUG, bool ROWS = false, bool AI = false>
-__global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 4)) void grad_kernel(GradParams p)
+__global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) void grad_kernel(GradParams p)
 {
     static_assert(CSPEC == 1 || CSPEC == 3 || CSPEC == 4 || (CSPEC == 6 && STRIDED), "pass shapes");
     constexpr int NPLANES = CSPEC;
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
     // responses (a workgroup barrier there): 50 -> 39 KB of LDS and twelve registers less, so that FOUR workgroups share a
     // compute unit instead of three for the many-channel frames, whose gradient is bound by memory requests in flight
     static_assert(!AI || (CSPEC == 4 && !STRIDED && !DEBUG && !ROWS), "the aliased form exists for the plain 4-channel kernel (and the {3,3} shape)");
-    constexpr bool ALIAS_INBOX = DIRT_ALIAS_INBOX && (CSPEC == 6 || AI);
+    constexpr bool ALIAS_INBOX = CSPEC == 6 || AI;
     __shared__ __align__(16) float2 s_inbox_own[ALIAS_INBOX ? 1 : GTHREADS / 64][ALIAS_INBOX ? 1 : ICELLS];
     // (the ring cells' factors are parked in the wave's OWN inbox once gather_positions has read it: cell 0 of the 64 lanes,
     // [component: b0 b1 b2 fx fy fw][lane], then cell 1 of lanes 0 .. 19: 504 floats of the inbox's 688)
@@ -146,11 +133,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
     const bool aligned16 = (!STRIDED && CSPEC == 4) ? true : (p.pixels_aligned16 != 0 && (cbase & 3) == 0);
     // ({3,3} passes of frames whose pixels are 16-byte aligned, C % 4 == 0: a pass starts at channel 6 i, i.e. at byte 0 or 8
     // of a 16-byte unit, and a last pass with a single (C % 3 == 1) at a multiple of 4 channels -- a lone last triple does not occur)
-#ifdef DIRT_NO_WIDE6
-    const bool wide6 = false;
-#else
     const bool wide6 = CSPEC == 6 && p.pixels_aligned16 != 0 && (C & 3) == 0;
-#endif
     int tile_col, tile_row;
     tile_xy(tile, p.tiles_x, p.tiles_x_magic, tile_col, tile_row);
     const int x0 = tile_col * GT, y0 = tile_row * GT;
@@ -211,11 +194,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
 #pragma unroll
         for (int k = 0; k < PITEMS; ++k) {
             const int cy = min(max(y0 - 1 + st_row + PROWS * k, 0), H - 1);
-#if defined(DIRT_KO_LOADS) || defined(DIRT_KO_PIX)
-            const uint32_t off = 0u * ((uint32_t)(cy - row0) * row_bytes + st_xoff);
-#else
             const uint32_t off = (uint32_t)(cy - row0) * row_bytes + st_xoff;
-#endif
             if (nch == 4 && (C & 3) == 0 && aligned16) {
                 const float4 q = ld_off<float4>(pixels_t, off);
                 v[k][0] = q.x; v[k][1] = q.y; v[k][2] = q.z; v[k][3] = q.w;
@@ -404,11 +383,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
                 }
             }
         }
-#ifdef DIRT_KO_RING   // (knock-out build, timing only: ring cells' contributions dropped -- what the loop costs without their registers)
-        pend[4] = NONE; pend[5] = NONE;
-#else
         pend[4] = (uint32_t)lkey[0]; pend[5] = (uint32_t)lkey[1];
-#endif
         // the row's next face: the smallest pending key of its 16 lanes (an all-lanes minimum by four DPP rotations)
         auto next_face = [&]() {
             uint32_t K = min(min(min(pend[0], pend[1]), min(pend[2], pend[3])), min(pend[4], pend[5]));
@@ -451,7 +426,6 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
                     if (FWS) accw[k] = j == 0 ? bm * fpw[j] : fmaf(bm, fpw[j], accw[k]);
                 }
             }
-#ifndef DIRT_KO_RING
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const lanemask mm = __builtin_amdgcn_ballot_w64(pend[4 + e] == K) & live;
@@ -476,7 +450,6 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
                     }
                 }
             }
-#endif
             GCOUNT(1, 1);
             const uint32_t K_next = next_face();
             float acc[NR];
@@ -512,11 +485,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
             }
 #pragma unroll
             for (int e = 0; e < NROLES; ++e) {
-#ifdef DIRT_GRAD_NO_ATOMICS   // measurement builds only (what the atomics cost: profiles/README.md); never defined for the product library
-                if (role_valid[e] && total[e] == 1.2345e-30f && vsel[e] == -12345)   // (never true; keeps the operands alive)
-#else
                 if (role_valid[e] && total[e] != 0.f)
-#endif
                     // (written as a GLOBAL atomic: behind the asm barrier above the compiler no longer knows the pointer's
                     // address space and emits flat_atomic_add_f32, which is issued to the LDS and the memory pipeline alike
                     // and counts on both wait counters)
@@ -597,11 +566,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
         float g[4][NCH];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-#if defined(DIRT_KO_LOADS) || defined(DIRT_KO_G)
-            const uint32_t off = 0u;
-#else
             const uint32_t off = in_px[j] ? own_off + (uint32_t)j * pixel_bytes : 0u;  // outside the frame: any valid address
-#endif
             bool wide = false;
             if constexpr (NCH == 4) {
                 if (single_on && (C & 3) == 0 && aligned16) {
@@ -762,12 +727,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
                         }
                     }
                 }
-#ifdef DIRT_SCHARR_PAIRS   // (A/B build: two channels' taps in flight)
-                if ((ch & 1) || ch == NCH - 1) __builtin_amdgcn_sched_barrier(0);
-#elif defined(DIRT_SCHARR_FREE)
-#else
                 __builtin_amdgcn_sched_barrier(0);  // one channel's taps at a time
-#endif
             }
         }
         GMARK();  // 4 Scharr done
@@ -843,7 +803,6 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
                 return;
             }
         }
-#if DIRT_GBK_COALESCED
         // 4-channel frames: the wave's 32 x 8 pixels in a lane <-> pixel LINEAR mapping (lane l: column l % 32, rows
         // l / 32 + 2 k), so that every store instruction writes 1 KB of whole lines -- a strip owner's float4 stores are
         // 16 bytes of every 64.  grad_pixels is read a second time for it (the lines are this workgroup's own, a few
@@ -870,7 +829,6 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
             }
             return;
         }
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!in_px[j]) continue;
@@ -972,12 +930,8 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
         float lb[2][3], lf[2][3];
         gather_positions(fpos_xy, fpos_w, lkey, lb, lf);
         GMARK();  // 6 face loop starts
-#ifndef DIRT_KO_LOOP
         face_loop(integral_constant<int, NCH>{}, g, key, covered, fpos_xy, fpos_w, lkey, lb, lf);
-#endif
-#ifndef DIRT_KO_GBK
         store_background();
-#endif
     };
 
     run_pass(integral_constant<int, CSPEC>{}, integral_constant<int, CSPEC == 1 ? 1 : 3>{});
@@ -992,33 +946,25 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? DIRT_TWO3_WAVES : (AI ? 5 : 
 #endif
 }
 
-hipError_t launch_grad(const GradParams& p_in, hipStream_t stream)
+// The gradient pass's shape (pick_grad_shape); launch_grad launches it.
+enum class GradShape {
+    SMALL,          // one pixel per lane on 16 x 16 tiles (dirt_grad_small.hip)
+    PX2,            // two pixels per lane on 32 x 16 tiles (dirt_grad_px2.hip)
+    ROWS,           // four pixels per lane (grad_kernel), 1 / 3 / 4 channels: every DPP row walks its own faces
+    PAIRS,          // ... the two rows of a pair work on one face
+    PAIRS_ALIASED,  // ... 4 channels, the per-wave inbox aliased onto the pixel planes (grad_kernel's AI)
+    STRIDED,        // ... any other channel count: passes of whole channel groups, the rows of a pair on one face
+};
+
+// The pin flags (DIRT_FLAG_GRAD_*) override the measured rules, each only where its kernel exists: ROWS or PAIRS rule out SMALL
+// and PX2, SMALL is decided before PX2, and PX4 rules out PX2 only.  DIRT_FLAG_GRAD_STREAM is a reserved bit: ignored.
+static GradShape pick_grad_shape(const GradParams& p, unsigned ntiles)
 {
-    if (p_in.B == 0) return hipSuccess;
-    GradParams p = p_in;
-    p.tiles_x = (p.W + GT - 1) / GT;
-    p.tiles_y = (p.H + GT - 1) / GT;
-    p.tiles_x_magic = tile_magic(p.tiles_x);
-    p.inv_w = 1.f / (float)p.W; p.inv_h = 1.f / (float)p.H;   // (IEEE divisions, as the kernel's own would be)
-    p.pixels_aligned16 = ((reinterpret_cast<uintptr_t>(p.pixels) | reinterpret_cast<uintptr_t>(p.grad_pixels) |
-                           reinterpret_cast<uintptr_t>(p.grad_background)) & 15u) == 0 ? 1 : 0;
-#ifdef DIRT_TRACE
-    const size_t dyn_lds = getenv("DIRT_TRACE_DYN_LDS") ? (size_t)atoi(getenv("DIRT_TRACE_DYN_LDS")) : 0;  // occupancy experiments
-#else
-    const size_t dyn_lds = 0;
-#endif
-    const dim3 block(GTHREADS);
-    const unsigned ntiles = (unsigned)(p.tiles_x * p.tiles_y);
-#define DIRT_LAUNCH_GRAD(SHAPE_, STRIDED_)                                                                       \
-    do {                                                                                                        \
-        const dim3 grid(ntiles * (unsigned)p.npasses, (unsigned)p.B);                                           \
-        if (p.debug_thingy && p.c_first == 0)                                                                   \
-            hipLaunchKernelGGL((grad_kernel<SHAPE_, STRIDED_, true>), grid, block, dyn_lds, stream, p);         \
-        else if (!STRIDED_ && rows)                                                                             \
-            hipLaunchKernelGGL((grad_kernel<SHAPE_, false, false, true>), grid, block, dyn_lds, stream, p);     \
-        else                                                                                                    \
-            hipLaunchKernelGGL((grad_kernel<SHAPE_, STRIDED_, false>), grid, block, dyn_lds, stream, p);        \
-    } while (0)
+    const unsigned pin = p.flags;
+    const bool pin_rows_pairs = (pin & (DIRT_FLAG_GRAD_ROWS | DIRT_FLAG_GRAD_PAIRS)) != 0;
+    const long long wgs32 = (long long)ntiles * p.B;                             // workgroups of 32 x 32 tiles
+    const long long density = ntiles ? (long long)p.F / (long long)ntiles : 0;   // faces per 32 x 32 tile
+    const bool few_tiles = wgs32 <= 256;                                         // at most one workgroup per compute unit
     // Which shape (measured on MI355X, gradient kernel in us; faces per 32 x 32 tile = F / tiles):
     //                       tiles  faces/tile   px1    rows   pairs
     //   K3-256  (10k faces)    64     156       10.6   20.7   26.1
@@ -1029,98 +975,105 @@ hipError_t launch_grad(const GradParams& p_in, hipStream_t stream)
     // The one-pixel-per-lane kernel (dirt_grad_small.hip: four times the waves, a handful of faces per 4 x 4 block) pays
     // where a small frame is DENSE in faces; with few large faces its per-block atomics all land on the same vertices.
     // Every row its own face (more atomics, fewer iterations) pays for moderately dense small frames; pairs otherwise.
-    const long long density = ntiles ? (long long)p.F / (long long)ntiles : 0;   // faces per 32 x 32 tile
-    const bool few_tiles = (long long)ntiles * p.B <= 256;                       // at most one workgroup per compute unit
-    {
-        const bool small_ok = p.C == 1 || p.C == 3 || p.C == 4;   // (many-channel G-buffers keep the strided passes below)
-        bool small = small_ok && few_tiles && density >= 96;
-        if (p.flags & DIRT_FLAG_GRAD_SMALL) small = small_ok;
-        if (p.flags & (DIRT_FLAG_GRAD_ROWS | DIRT_FLAG_GRAD_PAIRS)) small = false;
-        if (small) return launch_grad_small(p, stream);
-    }
-    {
-        // The streaming kernel (dirt_grad_stream.hip, round 6): the 4-pixel kernel's decomposition and face loop with wave-private
-        // tiles filled by LDS-DMA, slice 1's loads in flight under slice 0's compute.  4 channels, whole 32 x 32 tiles.
-        // Measured (round 6, profiles/EXPERIMENTS.md): parity-green, and SLOWER than the 4-pixel kernel at every size tried (K3 30.3
-        // against 27.1 us raw, K3-2048 68.8 / 64.7, eight scenes per launch 153 / 152): VMEM issue blocks the wave while the
-        // memory pipeline is backed up, so slice 1's requests do not travel under slice 0's compute.  Opt-in only.
-        bool streamk = false;
-        if (p.flags & DIRT_FLAG_GRAD_STREAM) streamk = grad_stream_eligible(p);
-        if (p.flags & (DIRT_FLAG_GRAD_ROWS | DIRT_FLAG_GRAD_PAIRS | DIRT_FLAG_GRAD_PX4 | DIRT_FLAG_GRAD_PX2 | DIRT_FLAG_GRAD_SMALL)) streamk = false;
-        if (streamk) return launch_grad_stream(p, stream);
-    }
-    {
-        // Two pixels per lane (dirt_grad_px2.hip: 32 x 16 tiles, twice the waves at half the chain each, 5-7 workgroups per
-        // compute unit).  Measured on MI355X (round 5, gradient kernel in us, HIP events, 10 000 faces, dense outputs):
-        //                          32x32 tiles    px2     4-pixel kernel
-        //   K3-768  (4 ch)             576        20.8        24.0       the 4-pixel grid leaves compute units with 2 or 3 workgroups
-        //   K3      (4 ch)            1024        27.1        26.4       one full round of the 4-pixel kernel: nothing to gain
-        //   K3-3ch                    1024        22.2        23.1       (64 VGPRs: seven workgroups per compute unit)
-        //   K3-1ch                    1024        20.6        18.9
-        //   K3-2048 (4 ch)            4096        72.9        68.2       rounds overlap by themselves; px2's extra atomics and instructions cost
-        //   K5-3ch  (50 000 faces)    4096        62.2        66.5       3 channels: eight workgroups per compute unit
-        // Rule: more than one workgroup per compute unit but less than a full round of the 4-pixel kernel; 3 channels: every such frame.
-        const bool px2_ok = p.C == 1 || p.C == 3 || (p.C == 4 && p.pixels_aligned16);
-        const long long wgs32 = (long long)ntiles * p.B;
-        bool px2 = px2_ok && !few_tiles && (wgs32 < 1024 || p.C == 3);
-        if (p.flags & DIRT_FLAG_GRAD_PX2) px2 = px2_ok;
-        if (p.flags & (DIRT_FLAG_GRAD_ROWS | DIRT_FLAG_GRAD_PAIRS | DIRT_FLAG_GRAD_PX4)) px2 = false;
-        if (px2) return launch_grad_px2(p, stream);
-    }
-    bool rows = few_tiles && density >= 48;
-    if (p.flags & DIRT_FLAG_GRAD_ROWS) rows = true;
-    if (p.flags & DIRT_FLAG_GRAD_PAIRS) rows = false;
-    p.c_first = 0; p.npasses = 1; p.gbk_split = -1; p.last_second = 0;
-    // the common channel counts: kernels in which the channel count is a compile-time constant
-    if (p.C == 4 && p.pixels_aligned16) {
-        // Grids of several rounds (eight scenes of K3 in one launch: 8192 workgroups): the aliased-inbox form, five workgroups per
-        // compute unit instead of four -- K3 x 8 gradient 157.7 -> 147.7 us, K3-2048 66.4 -> 65.9; a single round pays only for its
-        // extra barrier (K3: 26.4 -> 27.8), so one scene of up to 2047 tiles keeps the plain form.
-        if (DIRT_ALIAS_INBOX && !rows && !p.debug_thingy && (long long)ntiles * p.B >= 2048)
-            hipLaunchKernelGGL((grad_kernel<4, false, false, false, true>), dim3(ntiles, (unsigned)p.B), block, dyn_lds, stream, p);
-        else
-            DIRT_LAUNCH_GRAD(4, false);
-    }
-    else if (p.C == 3) DIRT_LAUNCH_GRAD(3, false);
-    else if (p.C == 1) DIRT_LAUNCH_GRAD(1, false);
-    else {
-        // any other channel count: passes of whole channel groups (groups of 3 while >= 3 channels remain, then singles,
-        // dirt/rasterise_ops.py:148-152).  Every 3-channel pass goes out in ONE launch -- of the {3,1} body when a single
-        // follows the triples: its last pass carries that single, the others switch the single's parts off -- so that the
-        // passes of a tile meet in the L2 (a second single, C % 3 == 2, is a launch of its own).
-        // From 6 channels on the triples go out in PAIRS (the {3,3} shape: one staging of the tile, one walk over its faces
-        // and one fetch of every 64-byte pixel for two groups), an odd last triple -- with the single that follows it, if
-        // any -- as the last pass of the same launch, so that all passes of a tile meet in the L2 (a launch of its own for
-        // the last four channels of K5 read both 268 MB tensors a second time); a second single (C % 3 == 2), or the
-        // singles behind an even number of triples, are a launch of the {1} shape.
-        const int groups3 = p.C / 3, singles = p.C % 3;
-        // grad_background: written by the FIRST launch's passes, all channels, whole lines (store_background), where the
-        // pixels are 16-byte aligned; otherwise every pass stores its own channels
-        const bool gbk_shared = (p.C & 3) == 0 && p.pixels_aligned16 != 0;
-        bool gbk_done = false;
+    const bool small_ok = p.C == 1 || p.C == 3 || p.C == 4;   // (many-channel G-buffers keep the strided passes)
+    if (small_ok && !pin_rows_pairs && ((pin & DIRT_FLAG_GRAD_SMALL) || (few_tiles && density >= 96))) return GradShape::SMALL;
+    // Two pixels per lane (dirt_grad_px2.hip: 32 x 16 tiles, twice the waves at half the chain each, 5-7 workgroups per
+    // compute unit).  Measured on MI355X (round 5, gradient kernel in us, HIP events, 10 000 faces, dense outputs):
+    //                          32x32 tiles    px2     4-pixel kernel
+    //   K3-768  (4 ch)             576        20.8        24.0       the 4-pixel grid leaves compute units with 2 or 3 workgroups
+    //   K3      (4 ch)            1024        27.1        26.4       one full round of the 4-pixel kernel: nothing to gain
+    //   K3-3ch                    1024        22.2        23.1       (64 VGPRs: seven workgroups per compute unit)
+    //   K3-1ch                    1024        20.6        18.9
+    //   K3-2048 (4 ch)            4096        72.9        68.2       rounds overlap by themselves; px2's extra atomics and instructions cost
+    //   K5-3ch  (50 000 faces)    4096        62.2        66.5       3 channels: eight workgroups per compute unit
+    // Rule: more than one workgroup per compute unit but less than a full round of the 4-pixel kernel; 3 channels: every such frame.
+    const bool fixed_c = p.C == 1 || p.C == 3 || (p.C == 4 && p.pixels_aligned16);   // compile-time channel counts of px2 and grad_kernel
+    if (fixed_c && !pin_rows_pairs && !(pin & DIRT_FLAG_GRAD_PX4) && ((pin & DIRT_FLAG_GRAD_PX2) || (!few_tiles && (wgs32 < 1024 || p.C == 3))))
+        return GradShape::PX2;
+    if (!fixed_c) return GradShape::STRIDED;
+    if (!(pin & DIRT_FLAG_GRAD_PAIRS) && ((pin & DIRT_FLAG_GRAD_ROWS) || (few_tiles && density >= 48))) return GradShape::ROWS;
+    // Grids of several rounds (eight scenes of K3 in one launch: 8192 workgroups): the aliased-inbox form, five workgroups per
+    // compute unit instead of four -- K3 x 8 gradient 157.7 -> 147.7 us, K3-2048 66.4 -> 65.9; a single round pays only for its
+    // extra barrier (K3: 26.4 -> 27.8), so one scene of up to 2047 tiles keeps the plain form.
+    if (p.C == 4 && !p.debug_thingy && wgs32 >= 2048) return GradShape::PAIRS_ALIASED;
+    return GradShape::PAIRS;
+}
+
+// One launch of grad_kernel: p.npasses passes of every tile.  The debug output (written by the pairs form) comes from the
+// launch that starts at channel 0.
+template <int CSPEC, bool STRIDED, bool ROWS = false, bool AI = false>
+static void launch_grad_px4(const GradParams& p, unsigned ntiles, hipStream_t stream)
+{
+    const dim3 grid(ntiles * (unsigned)p.npasses, (unsigned)p.B), block(GTHREADS);
+    if (p.debug_thingy && p.c_first == 0)
+        hipLaunchKernelGGL((grad_kernel<CSPEC, STRIDED, true>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((grad_kernel<CSPEC, STRIDED, false, ROWS, AI>), grid, block, 0, stream, p);
+}
+
+// The kernels in which the channel count (1, 3, 4) is a compile-time constant: one pass.
+template <bool ROWS>
+static void launch_grad_fixed(const GradParams& p, unsigned ntiles, hipStream_t stream)
+{
+    if (p.C == 4) launch_grad_px4<4, false, ROWS>(p, ntiles, stream);
+    else if (p.C == 3) launch_grad_px4<3, false, ROWS>(p, ntiles, stream);
+    else launch_grad_px4<1, false, ROWS>(p, ntiles, stream);
+}
+
+// Any other channel count: passes of whole channel groups (groups of 3 while >= 3 channels remain, then singles,
+// dirt/rasterise_ops.py:148-152).  Every 3-channel pass goes out in ONE launch -- of the {3,1} body when a single
+// follows the triples: its last pass carries that single, the others switch the single's parts off -- so that the
+// passes of a tile meet in the L2 (a second single, C % 3 == 2, is a launch of its own).
+// From 6 channels on the triples go out in PAIRS (the {3,3} shape: one staging of the tile, one walk over its faces
+// and one fetch of every 64-byte pixel for two groups), an odd last triple -- with the single that follows it, if
+// any -- as the last pass of the same launch, so that all passes of a tile meet in the L2 (a launch of its own for
+// the last four channels of K5 read both 268 MB tensors a second time); a second single (C % 3 == 2), or the
+// singles behind an even number of triples, are a launch of the {1} shape.
+static void launch_grad_strided(GradParams p, unsigned ntiles, hipStream_t stream)
+{
+    const int groups3 = p.C / 3, singles = p.C % 3;
+    // grad_background: written by the FIRST launch's passes, all channels, whole lines (store_background), where the
+    // pixels are 16-byte aligned; otherwise every pass stores its own channels
+    const bool gbk_shared = (p.C & 3) == 0 && p.pixels_aligned16 != 0;
+    bool gbk_done = false;
 #define DIRT_GBK_PLAN() do { p.gbk_split = !gbk_shared ? -1 : (gbk_done ? 0 : p.npasses); gbk_done = true; } while (0)
-        bool two3 = groups3 >= 2;
-#ifdef DIRT_NO_TWO3
-        two3 = false;
-#endif
-        if (two3) {
-            const bool odd = (groups3 & 1) != 0;
-            p.c_first = 0; p.npasses = (groups3 + 1) / 2; p.last_second = !odd ? 0 : (singles >= 1 ? 1 : 2); DIRT_GBK_PLAN();
-            if (p.debug_thingy) hipLaunchKernelGGL((grad_kernel<6, true, true>), dim3(ntiles * (unsigned)p.npasses, (unsigned)p.B), block, dyn_lds, stream, p);
-            else hipLaunchKernelGGL((grad_kernel<6, true, false>), dim3(ntiles * (unsigned)p.npasses, (unsigned)p.B), block, dyn_lds, stream, p);
-            const int rest = singles - (odd && singles >= 1 ? 1 : 0);   // singles not yet done
-            if (rest >= 1) { p.c_first = p.C - rest; p.npasses = rest; DIRT_GBK_PLAN(); DIRT_LAUNCH_GRAD(1, true); }
-        } else if (groups3 >= 1 && singles >= 1) {
-            p.c_first = 0; p.npasses = groups3; DIRT_GBK_PLAN(); DIRT_LAUNCH_GRAD(4, true);
-            if (singles == 2) { p.c_first = 3 * groups3 + 1; p.npasses = 1; DIRT_GBK_PLAN(); DIRT_LAUNCH_GRAD(1, true); }
-        } else if (groups3 >= 1) {
-            p.c_first = 0; p.npasses = groups3; DIRT_GBK_PLAN(); DIRT_LAUNCH_GRAD(3, true);
-        } else {
-            p.c_first = 0; p.npasses = singles; DIRT_GBK_PLAN(); DIRT_LAUNCH_GRAD(1, true);
-        }
-#undef DIRT_GBK_PLAN
+    if (groups3 >= 2) {
+        const bool odd = (groups3 & 1) != 0;
+        p.c_first = 0; p.npasses = (groups3 + 1) / 2; p.last_second = !odd ? 0 : (singles >= 1 ? 1 : 2); DIRT_GBK_PLAN();
+        launch_grad_px4<6, true>(p, ntiles, stream);
+        const int rest = singles - (odd && singles >= 1 ? 1 : 0);   // singles not yet done
+        if (rest >= 1) { p.c_first = p.C - rest; p.npasses = rest; DIRT_GBK_PLAN(); launch_grad_px4<1, true>(p, ntiles, stream); }
+    } else if (groups3 >= 1 && singles >= 1) {
+        p.c_first = 0; p.npasses = groups3; DIRT_GBK_PLAN(); launch_grad_px4<4, true>(p, ntiles, stream);
+        if (singles == 2) { p.c_first = 3 * groups3 + 1; p.npasses = 1; DIRT_GBK_PLAN(); launch_grad_px4<1, true>(p, ntiles, stream); }
+    } else if (groups3 >= 1) {
+        p.c_first = 0; p.npasses = groups3; DIRT_GBK_PLAN(); launch_grad_px4<3, true>(p, ntiles, stream);
+    } else {
+        p.c_first = 0; p.npasses = singles; DIRT_GBK_PLAN(); launch_grad_px4<1, true>(p, ntiles, stream);
     }
-#undef DIRT_LAUNCH_GRAD
+#undef DIRT_GBK_PLAN
+}
+
+hipError_t launch_grad(const GradParams& p_in, hipStream_t stream)
+{
+    if (p_in.B == 0) return hipSuccess;
+    GradParams p = p_in;
+    p.tiles_x = (p.W + GT - 1) / GT;
+    p.tiles_y = (p.H + GT - 1) / GT;
+    p.tiles_x_magic = tile_magic(p.tiles_x);
+    p.inv_w = 1.f / (float)p.W; p.inv_h = 1.f / (float)p.H;   // (IEEE divisions, as the kernel's own would be)
+    p.pixels_aligned16 = ((reinterpret_cast<uintptr_t>(p.pixels) | reinterpret_cast<uintptr_t>(p.grad_pixels) |
+                           reinterpret_cast<uintptr_t>(p.grad_background)) & 15u) == 0 ? 1 : 0;
+    p.c_first = 0; p.npasses = 1; p.gbk_split = -1; p.last_second = 0;   // one pass (launch_grad_strided plans its own)
+    const unsigned ntiles = (unsigned)(p.tiles_x * p.tiles_y);
+    switch (pick_grad_shape(p, ntiles)) {
+    case GradShape::SMALL: return launch_grad_small(p, stream);
+    case GradShape::PX2: return launch_grad_px2(p, stream);
+    case GradShape::ROWS: launch_grad_fixed<true>(p, ntiles, stream); break;
+    case GradShape::PAIRS: launch_grad_fixed<false>(p, ntiles, stream); break;
+    case GradShape::PAIRS_ALIASED: launch_grad_px4<4, false, false, true>(p, ntiles, stream); break;
+    case GradShape::STRIDED: launch_grad_strided(p, ntiles, stream); break;
+    }
     return hipGetLastError();
 }
 

@@ -111,11 +111,7 @@ struct GradParams {
 BinGrid make_bin_grid(int H, int W, int nchunk, bool masked, int min_shift = 5);
 int raster_tile_choice(int H, int W, int B, unsigned flags);   // 32 or 16: the forward / visibility kernels' tile (dirt_forward.hip)
 void chunking(int F, int& nchunk, int& chunk_faces);
-#ifdef DIRT_NO_MASKED_DIR   // (A/B builds: rounds 1-4's start / count directory for every mesh)
-inline bool directory_is_masked(int) { return false; }
-#else
 inline bool directory_is_masked(int chunk_faces) { return chunk_faces == 64; }   // one face per lane of a one-wave set-up workgroup
-#endif
 hipError_t launch_zero(void* b, size_t b_bytes, void* c, size_t c_bytes, hipStream_t stream);
 hipError_t launch_unpack(const float* acc_gv, const float* acc_gvc, int acc_stride, float* gv, float* gvc, int C, size_t rows, hipStream_t stream);
 hipError_t launch_geometry(const GeomParams& g, hipStream_t stream);
@@ -126,7 +122,5 @@ hipError_t launch_raster_v2(const RasterParams& p, int B, bool visibility_only, 
 hipError_t launch_grad(const GradParams& p, hipStream_t stream);
 hipError_t launch_grad_small(const GradParams& p, hipStream_t stream);  // dirt_grad_small.hip; p as filled by launch_grad
 hipError_t launch_grad_px2(const GradParams& p, hipStream_t stream);    // dirt_grad_px2.hip (two pixels per lane, 32 x 16 tiles); p as filled by launch_grad
-bool grad_stream_eligible(const GradParams& p);                         // dirt_grad_stream.hip (4 channels, whole 32 x 32 tiles: loads streamed by LDS-DMA under the compute)
-hipError_t launch_grad_stream(const GradParams& p, hipStream_t stream); // ... p as filled by launch_grad
 
 }  // namespace dirt

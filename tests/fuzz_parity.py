@@ -4,7 +4,8 @@ and visibility bit for bit, gradients per element within 5e-6 (parity.TIGHT_TOL;
 places: tests/parity.py).  A fixed-seed slice of it runs under pytest (tests/test_gpu_configs.py); as a script it is open-ended (a time budget).
 Two opt-in modes draw their own cases: `big` -- meshes of 16 385 to 250 000 faces, where the forward pipeline switches to the
 start / count bin directory (forward, visibility and gradients checked; slice: tests/test_gpu_large_meshes.py) -- and `stream` --
-the streaming gradient kernel, DIRT_FLAG_GRAD_STREAM (slice: tests/test_gpu_grad_stream.py; tools/check_stream.py).
+4-channel frames whose sides are multiples of 32, with the reserved bit DIRT_FLAG_GRAD_STREAM set, which must change nothing
+(slice: tests/test_gpu_grad_stream.py).
 usage: python tests/fuzz_parity.py [seconds] [seed] [hostile|big|stream]   (`hostile`: mostly hostile geometry, larger frames)"""
 import os
 import sys
@@ -82,8 +83,9 @@ STREAM_SIDES = (32, 64, 96, 128, 160, 192, 256, 320)
 
 
 def _draw_stream(rng, sizes=STREAM_SIDES):
-    """One case of the streaming-kernel sweep (DIRT_FLAG_GRAD_STREAM): sides that are multiples of 32, 4 channels, every mesh
-    kind, batches, quirk Q1 both ways, with and without the forward's state."""
+    """One case of the `stream` sweep: the reserved bit DIRT_FLAG_GRAD_STREAM set (accepted and ignored: the library's own
+    kernel choice runs) on frames whose sides are multiples of 32, 4 channels, every mesh kind, batches, quirk Q1 both ways,
+    with and without the forward's state."""
     H, W, C = int(rng.choice(sizes)), int(rng.choice(sizes)), 4
     kind = rng.choice(['split', 'shared', 'hostile', 'tiny'])
     seed_ = int(rng.integers(0, 1 << 30))
@@ -110,7 +112,7 @@ _MAX_DIM = 16384   # DIRT_MAX_DIM (include/dirt_hip.h)
 def run(budget=None, max_cases=None, seed=0, hard=False, max_dim=None, failures=None, big=False, stream=False):
     """Random cases until `budget` seconds have passed or `max_cases` are done; returns the number of cases.
     `failures`: a list to collect mismatches in instead of raising at the first (the open-ended sweep).
-    `big`: meshes of 16 385 to 250 000 faces (_draw_big); `stream`: the streaming gradient kernel's sweep (_draw_stream)."""
+    `big`: meshes of 16 385 to 250 000 faces (_draw_big); `stream`: the reserved-bit sweep (_draw_stream)."""
     rng = np.random.default_rng(seed)
     dev = torch.device('cuda', 0)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)

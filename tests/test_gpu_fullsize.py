@@ -532,8 +532,6 @@ def test_library_picks_the_fastest_kernel_shape(gpu, config):
     grad_sets = [('auto', 0), ('pairs', _lib.FLAG_GRAD_PAIRS), ('rows', _lib.FLAG_GRAD_ROWS)]
     if C in (1, 3, 4):
         grad_sets += [('px2', _lib.FLAG_GRAD_PX2), ('small', _lib.FLAG_GRAD_SMALL)]
-    if C == 4:
-        grad_sets += [('stream', _lib.FLAG_GRAD_STREAM)]
     tile_sets = [('auto', 0), ('large', _lib.FLAG_TILES_LARGE), ('small', _lib.FLAG_TILES_SMALL),
                  ('large8', _lib.FLAG_TILES_LARGE | _lib.FLAG_TILES_SMALL)]   # (both bits: 32 x 32 tiles, eight half-size waves each)
     for attempt in range(2):

@@ -1,6 +1,7 @@
-"""GPU parity of the streaming gradient kernel (DIRT_FLAG_GRAD_STREAM, dirt_grad_stream.hip: 4 channels, whole 32 x 32 tiles,
-LDS-DMA staging, its own quirk-Q1 right-border fix-up alias_wrap_fixup_pair) against the CPU oracle, at parity.TIGHT_TOL per
-element; and where the flag is set but the kernel does not apply (grad_stream_eligible), the fall-back's results."""
+"""DIRT_FLAG_GRAD_STREAM is a reserved bit: the library accepts it and ignores it (the kernel it once selected was removed).
+Every case here sets it and checks the backward against the CPU oracle at parity.TIGHT_TOL per element, grad_background
+(and pixels) bit for bit, in all three output forms: that pins that the bit changes nothing.  The cases also cover the
+default kernel choice on K3, K3-2048, batches, shared faces, 80 000 faces, the quirk-Q1 right border and misaligned views."""
 import numpy as np
 import pytest
 import torch
@@ -48,8 +49,8 @@ def _check(gpu, oracle, s, H, W, C, what, q1_modes=(0, 1), forms=('stateless', '
 
 
 def test_stream_fuzz_slice(gpu, oracle):
-    """A fixed-seed slice of tests/fuzz_parity.py's `stream` mode (the generator of tools/check_stream.py): sides multiples of
-    32 up to 320, 4 channels, split / shared / hostile / tiny meshes, batches, Q1 both ways, with and without the state."""
+    """A fixed-seed slice of tests/fuzz_parity.py's `stream` mode (the reserved bit set): sides multiples of 32 up to 320,
+    4 channels, split / shared / hostile / tiny meshes, batches, Q1 both ways, with and without the state."""
     from tests import fuzz_parity
     assert fuzz_parity.run(max_cases=150, seed=4242, stream=True) == 150
 
@@ -80,16 +81,16 @@ def test_stream_shared_faces(gpu, oracle):
 
 @pytest.mark.parametrize('W', [32, 64, 96])
 def test_stream_right_border_alias_taps(gpu, oracle, W):
-    """Quirk Q1 at the right image border (as test_gpu_parity.py::test_right_border_alias_taps, with H and W multiples of 32 so
-    that the streaming kernel runs): the aliased channels of the last columns lie in the next row / scene / past the end,
-    which alias_wrap_fixup_pair re-reads; large faces so that many border pixels are interior and decide their axis."""
+    """Quirk Q1 at the right image border (as test_gpu_parity.py::test_right_border_alias_taps, with H and W multiples of 32 and
+    the reserved bit set): the aliased channels of the last columns lie in the next row / scene / past the end, which the
+    gradient kernels re-read; large faces so that many border pixels are interior and decide their axis."""
     H = 256
     s = scenes.batch_scene(120, H, W, 4, seeds=[181 + W, 182 + W], r_lo=0.05, r_hi=0.4)
     _check(gpu, oracle, s, H, W, 4, 'right border W=%d' % W, q1_modes=(0,), forms=('stateless', 'dense'))
 
 
 def test_stream_large_mesh(gpu, oracle):
-    """More than 65 536 faces (the set-up threads own several faces each): the streaming kernel on that state."""
+    """More than 65 536 faces (the set-up threads own several faces each): the backward on that state, the reserved bit set."""
     s = {k: (v[None] if isinstance(v, np.ndarray) else v) for k, v in scenes.rand_scene(80000, 320, 384, 4, 97, 0.001, 0.02).items()}
     _check(gpu, oracle, s, 320, 384, 4, '80 000 faces')
 
@@ -101,14 +102,15 @@ def test_stream_large_mesh(gpu, oracle):
     (128, 96, 4, True),      # the debug output
 ])
 def test_stream_flag_falls_back(gpu, oracle, H, W, C, debug):
-    """The flag set where the streaming kernel does not apply: another kernel runs, and its results are the oracle's."""
+    """The reserved bit set on frames of other shapes -- sides not multiples of 32, 3 channels, the debug output: the results
+    are the oracle's."""
     s = scenes.batch_scene(900, H, W, C, seeds=[41, 42], r_lo=0.01, r_hi=0.2)
     _check(gpu, oracle, s, H, W, C, 'fall-back %dx%dx%d debug=%s' % (H, W, C, debug), forms=('stateless', 'dense'), want_debug=debug)
 
 
 def test_stream_flag_with_misaligned_views(gpu, oracle):
     """`pixels` and `grad_pixels` that start one float into their buffers (not 16-byte aligned; the wrapper copies them, as
-    test_misaligned_views_are_accepted) and vertex / face views x[1:] of a batch, through the flagged backward."""
+    test_misaligned_views_are_accepted) and vertex / face views x[1:] of a batch, through the backward with the reserved bit."""
     s = scenes.batch_scene(60, 32, 32, 4, seeds=[1, 2, 3], r_lo=0.1, r_hi=0.5)
     t = {k: _t(s[k], gpu) for k in ('background', 'vertices', 'vertex_colors', 'faces', 'grad_pixels')}
     pbuf = torch.zeros(2 * 32 * 32 * 4 + 1, device=gpu)
