@@ -29,6 +29,11 @@ FLAG_GRAD_PX4 = 0x10000   # ... or the four-pixels-per-lane kernel where the lib
 FLAG_GRAD_STREAM = 0x20000  # reserved: accepted and ignored (it pinned an experimental kernel, since removed)
 TEX_CLAMP = 1
 TEX_NEAREST = 2
+SHADE_MAX_LIGHTS = 8
+SHADE_PARAM_HEAD, SHADE_PARAM_LIGHT = 9, 8   # floats of the parameter block: ambient, background, camera; then per light
+SHADE_KINDS = {'diffuse_directional': 0, 'specular_directional': 1, 'diffuse_point': 2}
+SHADE_CLAMP = 1
+SHADE_HAS_CAMERA = 2
 
 E_INVALID_ARGUMENT = -1
 E_TOO_MANY_VERTICES = -2
@@ -43,7 +48,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_profile_name',
            'dirt_profile_read', 'dirt_profile_reset', 'dirt_texture_sample_forward', 'dirt_texture_sample_backward',
            'dirt_texture_sample_backward_image', 'dirt_texture_last_error', 'dirt_texture_mip_levels', 'dirt_texture_mip_build',
-           'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward')
+           'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
+           'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -108,6 +114,14 @@ def load():
         lib.dirt_texture_sample_mip_forward.restype = i
         lib.dirt_texture_sample_mip_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, i, i, i, f32, u, vp]
         lib.dirt_texture_sample_mip_backward.restype = i
+    if hasattr(lib, 'dirt_shade_forward') or not override:   # fused G-buffer lighting (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_shade_scratch_bytes.argtypes = [ll, ll, i]
+        lib.dirt_shade_scratch_bytes.restype = sz
+        lib.dirt_shade_forward.argtypes = [fp, fp, fp, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
+        lib.dirt_shade_forward.restype = i
+        lib.dirt_shade_backward.argtypes = [fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
+        lib.dirt_shade_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -282,6 +282,18 @@ dirt::RasterParams raster_params(const Carved& c, const dirt::GeomParams& g, int
 
 }  // namespace
 
+namespace dirt {
+// dirt_last_error()'s text for the entry points that live in other translation units (dirt_shade.hip): returns `code`
+int set_last_error(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
+    va_end(ap);
+    return code;
+}
+}  // namespace dirt
+
 extern "C" {
 
 int dirt_abi_version(void) { return DIRT_ABI_VERSION; }

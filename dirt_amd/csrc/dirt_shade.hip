@@ -1,0 +1,488 @@
+// dirt_shade.hip -- the lighting step of a deferred shader, fused: one pass over the G-buffer forward, one backward.
+//
+// Replaces the torch composition every deferred shader starts from (the reference's samples/deferred.py:59-98): ambient +
+// the three reflectance models of dirt/lighting.py:175-344 evaluated per pixel, composited over a background colour through
+// the mask channel and clamped.  The specification (DESIGN.md §7b restates it; tests/shade_reference.py composes it from
+// dirt_amd/lighting.py in float64), per pixel with colour c, normal n, position p, mask m (1 without a mask channel):
+//
+//     lit = ambient * c + sum_i L_i(p, n, c)          out = clamp(lit * m + background * (1 - m), lo, hi)
+//
+//  L_i, with light vector d (a direction or a position), light colour k, and x = |cos| (double sided) or max(cos, 0):
+//     diffuse_directional  (dirt/lighting.py:175-218): cos = n . (-d);                                    L = (k c) x
+//     specular_directional (dirt/lighting.py:221-283): r = d + 2 (n . (-d)) n, t = camera - p,
+//                                                      cos = (t / |t| + 1e-12) . r;                       L = (k c) pow(x, s)
+//     diffuse_point        (dirt/lighting.py:286-344): e = p - d, cos = n . (e / (|e| + 1e-12));          L = (k c) x
+//  Nothing is renormalised.  Gradients are those of this composition under torch's conventions at the kinks: max(x, 0) and
+//  clamp pass the gradient at their edges, abs gives 0 at 0, pow(0, s) has gradient 0 to s and s pow(0, s - 1) to its base
+//  (0 for s > 1, 1 at s = 1), a zero-length vector's norm has gradient 0.
+//
+// The parameter block the kernels read is [scenes or 1, 9 + 8 lights] floats: ambient, background, camera position, then
+// per light {vector[3], colour[3], shininess, 0}.  Kind and sidedness of the lights are launch arguments.
+//
+// Kernels: the forward one pixel per lane.  The backward one pixel per lane, four pixels per lane in a row, on workgroups of
+// 1024 pixels that never span two scenes: it recomputes the forward, sends d gbuffer through an LDS tile so that every row
+// is written whole (zeros in the channels no attribute uses) with consecutive lanes on consecutive floats, and keeps the
+// parameter gradients in registers; these are summed over the wave with DPP adds, over the four waves in LDS, and leave the
+// workgroup as ONE row of partial sums in caller-owned scratch.  shade_reduce_kernel adds the rows in a fixed order: no
+// atomics, and the same bits on every run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/dirt_hip.h"
+#include "dirt_launch.h"
+
+namespace dirt {
+
+constexpr int SHADE_HEAD = DIRT_SHADE_PARAM_HEAD, SHADE_LIGHT = DIRT_SHADE_PARAM_LIGHT;
+constexpr int SHADE_BLOCK = 256;      // lanes of a workgroup, pixels of one of its passes
+constexpr int SHADE_ITER = 4;         // passes of a backward workgroup
+constexpr int SHADE_ROW = 11;         // floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], dm, 0
+
+struct ShadeParams {
+    const float* g;        // [scenes, pixels, Cg]
+    const float* prm;      // [scenes or 1, 9 + 8 nl]
+    float* out;            // [scenes, pixels, 3]
+    const float* gout;     // [scenes, pixels, 3]
+    float* gg;             // [scenes, pixels, Cg] or nullptr
+    float* partial;        // [scenes, blocks, 9 + 8 nl] or nullptr
+    long long pixels;      // of one scene
+    int Cg, oc, on, op, om, nl, pstride;   // channel offsets (op, om: -1 = absent); pstride: 0 = one block for every scene
+    unsigned kinds, dsided;               // two bits / one bit per light
+    int clamp;
+    float lo, hi;
+};
+
+struct V3 { float x, y, z; };   // three consecutive floats, 4-byte aligned: one 12-byte access
+
+__device__ __forceinline__ void load3(const float* __restrict__ p, float (&v)[3])
+{
+    const V3 t = *reinterpret_cast<const V3*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z;
+}
+
+__device__ __forceinline__ float dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+__device__ __forceinline__ float fold_cos(float c, bool ds) { return ds ? fabsf(c) : (c < 0.f ? 0.f : c); }
+
+// the geometry of one light at one pixel: the cosine, and what its gradient needs
+struct LightGeo {
+    float cosv;
+    float a[3];    // specular: the reflected direction r;  point: the incident direction e / (|e| + 1e-12)
+    float b[3];    // specular: v = t / |t| + 1e-12;        point: e
+    float t[3];    // specular: t
+    float ndl, len, inv;   // n . (-d); |t| or |e|; 1 / |t| or 1 / (|e| + 1e-12)
+};
+
+__device__ __forceinline__ void light_geometry(int kind, const float* __restrict__ L, const float (&cam)[3], const float (&n)[3],
+                                               const float (&p)[3], LightGeo& q)
+{
+    const float d[3] = {L[0], L[1], L[2]};
+    if (kind == DIRT_SHADE_DIFFUSE_DIRECTIONAL) {
+        const float tl[3] = {-d[0], -d[1], -d[2]};
+        q.cosv = dot3(n, tl);
+    } else if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL) {
+        const float tl[3] = {-d[0], -d[1], -d[2]};
+        q.ndl = dot3(n, tl);
+        const float k2 = 2.f * q.ndl;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { q.a[j] = d[j] + k2 * n[j]; q.t[j] = cam[j] - p[j]; }
+        q.len = sqrtf(dot3(q.t, q.t));
+        q.inv = 1.f / q.len;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q.b[j] = q.t[j] * q.inv + 1.e-12f;
+        q.cosv = dot3(q.b, q.a);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q.b[j] = p[j] - d[j];
+        q.len = sqrtf(dot3(q.b, q.b));
+        q.inv = 1.f / (q.len + 1.e-12f);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q.a[j] = q.b[j] * q.inv;
+        q.cosv = dot3(n, q.a);
+    }
+}
+
+// x or pow(x, s): the scalar factor of a light's term
+__device__ __forceinline__ float light_factor(int kind, float x, float s) { return kind == DIRT_SHADE_SPECULAR_DIRECTIONAL ? powf(x, s) : x; }
+
+__device__ __forceinline__ float clamp_out(const ShadeParams& P, float pre)
+{
+    if (!P.clamp) return pre;
+    return pre < P.lo ? P.lo : (pre > P.hi ? P.hi : pre);   // a NaN stays NaN, as torch.clamp leaves it
+}
+
+struct Pixel { float c[3], n[3], p[3], m; };
+
+__device__ __forceinline__ void load_pixel(const ShadeParams& P, const float* __restrict__ row, Pixel& px)
+{
+    load3(row + P.oc, px.c);
+    load3(row + P.on, px.n);
+    px.p[0] = px.p[1] = px.p[2] = 0.f;
+    if (P.op >= 0) load3(row + P.op, px.p);
+    px.m = P.om >= 0 ? row[P.om] : 1.f;
+}
+
+// ---- forward: one pixel per lane; the lights are a wave-uniform loop over the parameter block (scalar loads)
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeParams P)
+{
+    const long long i = (long long)blockIdx.x * SHADE_BLOCK + threadIdx.x;
+    if (i >= P.pixels) return;
+    const long long pix = (long long)blockIdx.y * P.pixels + i;
+    const float* __restrict__ prm = P.prm + (size_t)blockIdx.y * P.pstride;
+    Pixel px;
+    load_pixel(P, P.g + pix * P.Cg, px);
+    const float cam[3] = {prm[6], prm[7], prm[8]};
+    float lit[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) lit[j] = prm[j] * px.c[j];
+    for (int l = 0; l < P.nl; ++l) {
+        const float* __restrict__ L = prm + SHADE_HEAD + SHADE_LIGHT * l;
+        const int kind = (P.kinds >> (2 * l)) & 3;
+        LightGeo q;
+        light_geometry(kind, L, cam, px.n, px.p, q);
+        const float f = light_factor(kind, fold_cos(q.cosv, (P.dsided >> l) & 1), L[6]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) lit[j] += (L[3 + j] * px.c[j]) * f;
+    }
+    V3 o;
+    const float om = 1.f - px.m;
+    o.x = clamp_out(P, lit[0] * px.m + prm[3] * om);
+    o.y = clamp_out(P, lit[1] * px.m + prm[4] * om);
+    o.z = clamp_out(P, lit[2] * px.m + prm[5] * om);
+    *reinterpret_cast<V3*>(P.out + pix * 3) = o;
+}
+
+// ---- the sum of a value over the 64 lanes of a wave, in every lane: DPP adds inside the rows of 16, then the four rows
+template <int CTRL>
+__device__ __forceinline__ float shade_dpp(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v += shade_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += shade_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += shade_dpp<0x141>(v);   // row_half_mirror: the other quad of the eight
+    v += shade_dpp<0x140>(v);   // row_mirror: the other eight of the row
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return (r0 + r1) + (r2 + r3);
+}
+
+// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (10: the row's zero)
+__device__ __forceinline__ int shade_source(const ShadeParams& P, int ch)
+{
+    if ((unsigned)(ch - P.oc) < 3u) return ch - P.oc;
+    if ((unsigned)(ch - P.on) < 3u) return 3 + ch - P.on;
+    if (P.op >= 0 && (unsigned)(ch - P.op) < 3u) return 6 + ch - P.op;
+    if (ch == P.om) return 9;
+    return 10;
+}
+
+// ---- backward.  NL: the number of lights (the per-lane parameter sums are registers, indexed at compile time);
+// PARAMS: whether the parameter block wants its gradient; GBUF: whether the G-buffer does.
+template <int NL, bool PARAMS, bool GBUF>
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams P)
+{
+    constexpr int NP = SHADE_HEAD + SHADE_LIGHT * NL;
+    constexpr int NA = PARAMS ? NP : 1;
+    __shared__ float s_g[GBUF ? SHADE_BLOCK * SHADE_ROW : 1];
+    __shared__ unsigned char s_src[GBUF ? DIRT_SHADE_MAX_CHANNELS : 1];
+    __shared__ float s_part[PARAMS ? 4 * NP : 1];
+    const int tid = threadIdx.x;
+    const float* __restrict__ prm = P.prm + (size_t)blockIdx.y * P.pstride;
+    const float cam[3] = {prm[6], prm[7], prm[8]};
+    float acc[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) acc[k] = 0.f;
+    // the walk of the copy-out loop: element e = tid + 256 step of the tile is channel e % Cg of pixel e / Cg
+    const int Cg = P.Cg, step_px = SHADE_BLOCK / Cg, step_ch = SHADE_BLOCK % Cg;
+    const int px0 = tid / Cg, ch0 = tid % Cg;
+    if constexpr (GBUF) {
+        for (int ch = tid; ch < Cg; ch += SHADE_BLOCK) s_src[ch] = (unsigned char)shade_source(P, ch);
+        s_g[tid * SHADE_ROW + 10] = 0.f;
+    }
+    for (int it = 0; it < SHADE_ITER; ++it) {
+        const long long first = ((long long)blockIdx.x * SHADE_ITER + it) * SHADE_BLOCK;   // (uniform)
+        if (first >= P.pixels) break;
+        const int npx = (int)(P.pixels - first < SHADE_BLOCK ? P.pixels - first : SHADE_BLOCK);
+        const long long pix = (long long)blockIdx.y * P.pixels + first + tid;
+        if (tid < npx) {
+            Pixel px;
+            load_pixel(P, P.g + pix * Cg, px);
+            float go[3];
+            load3(P.gout + pix * 3, go);
+            // the forward again: every light's cosine and factor, and the value the clamp saw
+            float lit[3], cosv[NL ? NL : 1], fac[NL ? NL : 1];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) lit[j] = prm[j] * px.c[j];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const float* __restrict__ L = prm + SHADE_HEAD + SHADE_LIGHT * l;
+                const int kind = (P.kinds >> (2 * l)) & 3;
+                LightGeo q;
+                light_geometry(kind, L, cam, px.n, px.p, q);
+                cosv[l] = q.cosv;
+                fac[l] = light_factor(kind, fold_cos(q.cosv, (P.dsided >> l) & 1), L[6]);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) lit[j] += (L[3 + j] * px.c[j]) * fac[l];
+            }
+            const float om = 1.f - px.m;
+            float glit[3], gc[3], gn[3] = {0.f, 0.f, 0.f}, gp[3] = {0.f, 0.f, 0.f}, gm = 0.f, gmb = 0.f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float pre = lit[j] * px.m + prm[3 + j] * om;
+                const float gpre = (!P.clamp || (pre >= P.lo && pre <= P.hi)) ? go[j] : 0.f;   // closed at both edges; 0 at a NaN
+                glit[j] = gpre * px.m;
+                gm += gpre * lit[j];
+                gmb += gpre * prm[3 + j];
+                if constexpr (PARAMS) { acc[3 + j] += gpre * om; acc[j] += glit[j] * px.c[j]; }
+                gc[j] = glit[j] * prm[j];
+            }
+            gm -= gmb;   // d (background (1 - m)) / d m
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const float* __restrict__ L = prm + SHADE_HEAD + SHADE_LIGHT * l;
+                const int kind = (P.kinds >> (2 * l)) & 3;
+                const bool ds = (P.dsided >> l) & 1;
+                const int a0 = SHADE_HEAD + SHADE_LIGHT * l;
+                float gf = 0.f;   // to the scalar factor
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float t = glit[j] * fac[l];
+                    if constexpr (PARAMS) acc[a0 + 3 + j] += t * px.c[j];
+                    gc[j] += t * L[3 + j];
+                    gf += glit[j] * (L[3 + j] * px.c[j]);
+                }
+                const float x = fold_cos(cosv[l], ds);
+                float gx = gf;
+                if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL) {
+                    const float s = L[6];
+                    gx = s == 0.f ? 0.f : gf * (s * powf(x, s - 1.f));
+                    if constexpr (PARAMS) acc[a0 + 6] += (x == 0.f && s >= 0.f) ? 0.f : gf * (fac[l] * logf(x));
+                }
+                const float c0 = cosv[l];
+                const float gcos = ds ? gx * ((c0 > 0.f ? 1.f : 0.f) - (c0 < 0.f ? 1.f : 0.f)) : (c0 >= 0.f ? gx : 0.f);
+                LightGeo q;
+                light_geometry(kind, L, cam, px.n, px.p, q);
+                if (kind == DIRT_SHADE_DIFFUSE_DIRECTIONAL) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        gn[j] += gcos * -L[j];
+                        if constexpr (PARAMS) acc[a0 + j] -= gcos * px.n[j];
+                    }
+                } else if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL) {
+                    // cos = v . r;  v = t / |t| + 1e-12;  r = d + 2 (n . tl) n,  tl = -d
+                    float gr[3], gv[3];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) { gr[j] = gcos * q.b[j]; gv[j] = gcos * q.a[j]; }
+                    const float glen = -(dot3(gv, q.t) * q.inv) * q.inv;
+                    const float gl = q.len == 0.f ? 0.f : glen * q.inv;            // d |t| / d t = t / |t|, 0 at a zero vector
+                    const float gndl = 2.f * dot3(gr, px.n);
+                    const float k2 = 2.f * q.ndl;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const float gt = gv[j] * q.inv + q.t[j] * gl;
+                        if constexpr (PARAMS) acc[6 + j] += gt;
+                        gp[j] -= gt;
+                        gn[j] += k2 * gr[j] + gndl * -L[j];
+                        if constexpr (PARAMS) acc[a0 + j] += gr[j] - gndl * px.n[j];
+                    }
+                } else {
+                    // cos = n . u;  u = e / (|e| + 1e-12);  e = p - d
+                    float gu[3];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) { gn[j] += gcos * q.a[j]; gu[j] = gcos * px.n[j]; }
+                    const float glen = -(dot3(gu, q.b) * q.inv) * q.inv;
+                    const float gl = q.len == 0.f ? 0.f : glen / q.len;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const float ge = gu[j] * q.inv + q.b[j] * gl;
+                        gp[j] += ge;
+                        if constexpr (PARAMS) acc[a0 + j] -= ge;
+                    }
+                }
+            }
+            if constexpr (GBUF) {
+                float* __restrict__ r = s_g + tid * SHADE_ROW;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { r[j] = gc[j]; r[3 + j] = gn[j]; r[6 + j] = gp[j]; }
+                r[9] = gm;
+            }
+        }
+        if constexpr (GBUF) {
+            __syncthreads();
+            float* __restrict__ dst = P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg;
+            const int total = npx * Cg;
+            int pxi = px0, ch = ch0;
+            for (int e = tid; e < total; e += SHADE_BLOCK) {
+                dst[e] = s_g[pxi * SHADE_ROW + s_src[ch]];
+                pxi += step_px; ch += step_ch;
+                if (ch >= Cg) { ch -= Cg; ++pxi; }
+            }
+            __syncthreads();
+        }
+    }
+    if constexpr (PARAMS) {
+        const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const bool pad = k >= SHADE_HEAD && (k - SHADE_HEAD) % SHADE_LIGHT == SHADE_LIGHT - 1;
+            const float s = pad ? 0.f : wave_sum(acc[k]);
+            if (lane == 0) s_part[wave * NP + k] = s;
+        }
+        __syncthreads();
+        if (tid < NP) {
+            const float s = (s_part[tid] + s_part[NP + tid]) + (s_part[2 * NP + tid] + s_part[3 * NP + tid]);
+            P.partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NP + tid] = s;
+        }
+    }
+}
+
+// ---- the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a fixed order:
+// workgroup (k, b) sums value k; lane t takes rows t, t + 256, ..., then the 256 lanes fold in LDS
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_reduce_kernel(const float* __restrict__ partial, float* __restrict__ grad_params,
+                                                                   long long rows, int NP)
+{
+    __shared__ float s_sum[SHADE_BLOCK];
+    const int tid = threadIdx.x, k = blockIdx.x;
+    const float* __restrict__ base = partial + (size_t)blockIdx.y * rows * NP + k;
+    float s = 0.f;
+    for (long long r = tid; r < rows; r += SHADE_BLOCK) s += base[r * NP];
+    s_sum[tid] = s;
+    __syncthreads();
+    for (int h = SHADE_BLOCK / 2; h > 0; h >>= 1) {
+        if (tid < h) s_sum[tid] += s_sum[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) grad_params[(size_t)blockIdx.y * NP + k] = s_sum[0];
+}
+
+template <int NL>
+void shade_launch_backward(const ShadeParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
+{
+    if (params && gbuf) hipLaunchKernelGGL((shade_backward_kernel<NL, true, true>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    else if (params) hipLaunchKernelGGL((shade_backward_kernel<NL, true, false>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    else hipLaunchKernelGGL((shade_backward_kernel<NL, false, true>), grid, dim3(SHADE_BLOCK), 0, s, P);
+}
+
+}  // namespace dirt
+
+extern "C" {
+
+#define SHADE_FAIL(...) return dirt::set_last_error(DIRT_E_INVALID_ARGUMENT, __VA_ARGS__)
+#define SHADE_OK() dirt::set_last_error(DIRT_OK, "%s", "")
+
+static int shade_hip(const char* who, hipError_t e)
+{
+    if (e != hipSuccess) return dirt::set_last_error(DIRT_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SHADE_OK();
+}
+
+static long long shade_blocks(long long pixels) { return (pixels + dirt::SHADE_BLOCK * dirt::SHADE_ITER - 1) / (dirt::SHADE_BLOCK * dirt::SHADE_ITER); }
+
+static int shade_check(const char* who, long long scenes, long long pixels, int Cg, int off_colors, int off_normals, int off_positions,
+                       int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned flags, float lo, float hi,
+                       dirt::ShadeParams& P)
+{
+    if (scenes < 0 || pixels < 0) SHADE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
+    if (scenes > 65535) SHADE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
+    if (pixels > (1ll << 40)) SHADE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
+    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) SHADE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) SHADE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_MAX_LIGHTS);
+    if (param_scenes != 1 && param_scenes != scenes) SHADE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
+    const int off[4] = {off_colors, off_normals, off_positions, off_mask}, width[4] = {3, 3, 3, 1};
+    const char* const names[4] = {"colors", "normals", "positions", "mask"};
+    for (int a = 0; a < 4; ++a) {
+        if (off[a] == -1 && a >= 2) continue;
+        if (off[a] < 0 || off[a] + width[a] > Cg) SHADE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
+        for (int b = 0; b < a; ++b)
+            if (off[b] >= 0 && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
+                SHADE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
+    }
+    for (int l = 0; l < lights; ++l) {
+        const int kind = (light_kinds >> (2 * l)) & 3;
+        if (kind > DIRT_SHADE_DIFFUSE_POINT) SHADE_FAIL("%s: light %d has unknown kind %d", who, l, kind);
+        if (kind != DIRT_SHADE_DIFFUSE_DIRECTIONAL && off_positions < 0) SHADE_FAIL("%s: light %d needs positions, the G-buffer has none", who, l);
+        if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL && !(flags & DIRT_SHADE_HAS_CAMERA))
+            SHADE_FAIL("%s: light %d is specular and needs a camera position (DIRT_SHADE_HAS_CAMERA)", who, l);
+    }
+    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) SHADE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    P.pixels = pixels; P.Cg = Cg; P.oc = off_colors; P.on = off_normals; P.op = off_positions; P.om = off_mask; P.nl = lights;
+    P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
+    P.kinds = light_kinds; P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0; P.lo = lo; P.hi = hi;
+    return DIRT_OK;
+}
+
+size_t dirt_shade_scratch_bytes(long long scenes, long long pixels, int lights)
+{
+    if (scenes < 0 || scenes > 65535 || pixels < 0 || pixels > (1ll << 40) || lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) return 0;
+    return sizeof(float) * (size_t)scenes * (size_t)shade_blocks(pixels) * (size_t)(DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
+}
+
+int dirt_shade_forward(const float* gbuffer, const float* params, float* out, long long scenes, long long pixels, int Cg, int off_colors,
+                       int off_normals, int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds,
+                       unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
+{
+    const char* who = "dirt_shade_forward";
+    dirt::ShadeParams P{};
+    int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
+                         clamp_lo, clamp_hi, P);
+    if (rc) return rc;
+    if (scenes * pixels == 0) return SHADE_OK();
+    if (!gbuffer || !params || !out) SHADE_FAIL("%s: gbuffer / params / out is NULL", who);
+    if (pixels > 0x7fffffffll * dirt::SHADE_BLOCK) SHADE_FAIL("%s: too many pixels per scene", who);
+    P.g = gbuffer; P.prm = params; P.out = out; P.dsided = double_sided;
+    const dim3 grid((unsigned)((pixels + dirt::SHADE_BLOCK - 1) / dirt::SHADE_BLOCK), (unsigned)scenes);
+    hipLaunchKernelGGL(dirt::shade_forward_kernel, grid, dim3(dirt::SHADE_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
+    return shade_hip(who, hipGetLastError());
+}
+
+int dirt_shade_backward(const float* gbuffer, const float* params, const float* grad_out, float* grad_gbuffer, float* grad_params,
+                        void* scratch, size_t scratch_bytes, long long scenes, long long pixels, int Cg, int off_colors, int off_normals,
+                        int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned double_sided,
+                        float clamp_lo, float clamp_hi, unsigned flags, void* stream)
+{
+    const char* who = "dirt_shade_backward";
+    dirt::ShadeParams P{};
+    int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
+                         clamp_lo, clamp_hi, P);
+    if (rc) return rc;
+    if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params)) return SHADE_OK();
+    if (!gbuffer || !params || !grad_out) SHADE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
+    if (grad_params) {
+        const size_t need = dirt_shade_scratch_bytes(scenes, pixels, lights);
+        if (!scratch || scratch_bytes < need) SHADE_FAIL("%s: scratch is NULL or smaller than dirt_shade_scratch_bytes (%zu < %zu)", who, scratch_bytes, need);
+        if (reinterpret_cast<uintptr_t>(scratch) & 3u) SHADE_FAIL("%s: scratch is not 4-byte aligned", who);
+    }
+    const long long blocks = shade_blocks(pixels);
+    if (blocks > 0x7fffffffll) SHADE_FAIL("%s: too many pixels per scene", who);
+    P.g = gbuffer; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.partial = static_cast<float*>(scratch); P.dsided = double_sided;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)blocks, (unsigned)scenes);
+    const bool params_wanted = grad_params != nullptr, gbuf = grad_gbuffer != nullptr;
+    switch (lights) {
+    case 0: dirt::shade_launch_backward<0>(P, params_wanted, gbuf, grid, s); break;
+    case 1: dirt::shade_launch_backward<1>(P, params_wanted, gbuf, grid, s); break;
+    case 2: dirt::shade_launch_backward<2>(P, params_wanted, gbuf, grid, s); break;
+    case 3: dirt::shade_launch_backward<3>(P, params_wanted, gbuf, grid, s); break;
+    case 4: dirt::shade_launch_backward<4>(P, params_wanted, gbuf, grid, s); break;
+    case 5: dirt::shade_launch_backward<5>(P, params_wanted, gbuf, grid, s); break;
+    case 6: dirt::shade_launch_backward<6>(P, params_wanted, gbuf, grid, s); break;
+    case 7: dirt::shade_launch_backward<7>(P, params_wanted, gbuf, grid, s); break;
+    default: dirt::shade_launch_backward<8>(P, params_wanted, gbuf, grid, s); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return shade_hip(who, e);
+    if (params_wanted) {
+        const int NP = DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
+        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
+        hipLaunchKernelGGL(dirt::shade_reduce_kernel, dim3((unsigned)NP, (unsigned)param_scenes), dim3(dirt::SHADE_BLOCK), 0, s,
+                           static_cast<const float*>(scratch), grad_params, rows, NP);
+        e = hipGetLastError();
+    }
+    return shade_hip(who, e);
+}
+
+}  // extern "C"

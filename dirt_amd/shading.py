@@ -1,0 +1,231 @@
+"""Fused G-buffer lighting for deferred shaders: the shader of the reference's samples/deferred.py:59-98 (ambient + the
+reflectance models of dirt/lighting.py:175-344, composited over a background colour through the mask channel, clamped)
+as one HIP kernel forward and one backward (dirt_shade.hip; specification in DESIGN.md §7b).
+
+`shade_gbuffer` is usable directly and as the body of a `shader_fn` given to `rasterise_deferred`:
+
+    def shader_fn(gbuffer, view_matrix, light_direction):
+        return shade_gbuffer(gbuffer, [diffuse_directional_light(light_direction, (1., 0., 0.), double_sided=False)],
+                             colors=4, normals=7, positions=1, mask=0, ambient=(.2, .2, .2), background=(0., 0., .3))
+"""
+import numbers
+
+import torch
+
+from . import _lib
+from . import rasterise_ops as _ops
+
+_KINDS = _lib.SHADE_KINDS
+_NEEDS_POSITIONS = ('specular_directional', 'diffuse_point')
+
+
+def diffuse_directional_light(direction, color, double_sided=True):
+    """A light record for `shade_gbuffer`: `lighting.diffuse_directional` (dirt/lighting.py:175-218)."""
+    return ('diffuse_directional', direction, color, double_sided)
+
+
+def specular_directional_light(direction, color, shininess, double_sided=True):
+    """A light record for `shade_gbuffer`: `lighting.specular_directional` (dirt/lighting.py:221-283); needs `camera_position`."""
+    return ('specular_directional', direction, color, shininess, double_sided)
+
+
+def diffuse_point_light(position, color, double_sided=True):
+    """A light record for `shade_gbuffer`: `lighting.diffuse_point` (dirt/lighting.py:286-344)."""
+    return ('diffuse_point', position, color, double_sided)
+
+
+# (device, values) -> [1, P] tensor of the block's constant part, uploaded once per distinct set of python numbers.  Rows are
+# NEVER evicted: a captured HIP graph (GraphedStep) replays from the address of the row its warm-up allocated, and nothing else
+# keeps that row alive once the call has returned.  A row is at most 292 bytes; parameters that change from call to call are
+# meant to be tensors (which also makes them differentiable), not python numbers.
+_const_cache = {}
+
+
+def _const_block(device, values):
+    key = (str(device), values)
+    t = _const_cache.get(key)
+    if t is None:
+        t = _const_cache[key] = torch.tensor([values], dtype=torch.float32).to(device)
+    return t
+
+
+def _value(x, width, name, device, batch):
+    """A parameter as python floats (-> list) or as a float32 tensor [1 or batch, width] on `device`."""
+    if isinstance(x, torch.Tensor):
+        if x.device != device:
+            raise ValueError('%s is on %s, the G-buffer on %s' % (name, x.device, device))
+        shapes = [(width,), (batch, width)] if batch is not None else [(width,)]
+        if width == 1:
+            shapes = [(), (1,)] + ([(batch,), (batch, 1)] if batch is not None else [])
+        if tuple(x.shape) not in shapes:
+            raise ValueError('%s must have shape %s, got %s' % (name, ' or '.join(str(list(s)) for s in shapes), list(x.shape)))
+        return x.to(torch.float32).reshape(-1, width)
+    if width == 1:
+        if not isinstance(x, numbers.Real):
+            raise ValueError('%s must be a number or a tensor, got %r' % (name, x))
+        return [float(x)]
+    try:
+        vals = [float(v) for v in x]
+    except (TypeError, ValueError):
+        raise ValueError('%s must be %d numbers or a tensor, got %r' % (name, width, x))
+    if len(vals) != width:
+        raise ValueError('%s must be %d numbers, got %d' % (name, width, len(vals)))
+    return vals
+
+
+class _ShadeGBuffer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, block, meta):
+        lib = _lib.load()
+        scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = meta
+        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
+        block = block.contiguous()
+        if scenes * pixels:
+            with _ops._on_device(gbuffer.device):
+                rc = lib.dirt_shade_forward(gbuffer.data_ptr(), block.data_ptr(), out.data_ptr(), scenes, pixels, cg, *offsets,
+                                            int(block.shape[0]), nl, kinds, sided, lo, hi, flags, _ops._stream_handle(gbuffer.device))
+            _lib.check(rc)
+        ctx.save_for_backward(gbuffer, block)
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, block = ctx.saved_tensors
+        scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = ctx.meta
+        dev = gbuffer.device
+        want_g, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not scenes * pixels:
+            return (torch.zeros_like(gbuffer) if want_g else None, torch.zeros_like(block) if want_p else None, None)
+        grad_out = grad_out.to(torch.float32).contiguous()
+        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
+        grad_g = torch.empty_like(gbuffer) if want_g else None
+        grad_p = torch.empty_like(block) if want_p else None
+        nbytes = lib.dirt_shade_scratch_bytes(scenes, pixels, nl) if want_p else 0
+        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if want_p else None
+        with _ops._on_device(dev):
+            rc = lib.dirt_shade_backward(gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(),
+                                         grad_g.data_ptr() if want_g else None, grad_p.data_ptr() if want_p else None,
+                                         scratch.data_ptr() if want_p else None, nbytes, scenes, pixels, cg, *offsets,
+                                         int(block.shape[0]), nl, kinds, sided, lo, hi, flags, _ops._stream_handle(dev))
+        _lib.check(rc)
+        return grad_g, grad_p, None
+
+
+def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None, ambient=(0., 0., 0.), camera_position=None,
+                  background=(0., 0., 0.), clamp=(0., 1.)):
+    """Lights a G-buffer per pixel in one kernel (the shader of samples/deferred.py:59-98), differentiably.
+
+    gbuffer: float32 [H, W, Cg], [B, H, W, Cg] or a flat [N, Cg] on the GPU; a contiguous one is read in place.
+    colors, normals, positions, mask: the first channel of each attribute inside a pixel (3, 3, 3 and 1 channels; any
+        order, no overlap).  `positions` is needed only if a light needs it; mask=None: every pixel is covered.
+    lights: up to 8 records ('diffuse_directional', direction, color, double_sided),
+        ('specular_directional', direction, color, shininess, double_sided) (needs `camera_position`) or
+        ('diffuse_point', position, color, double_sided) -- the three models of `dirt_amd.lighting`, with their conventions
+        (nothing is renormalised); `diffuse_directional_light` etc. build them.
+    direction / position / color / ambient / camera_position / background: 3 numbers or a tensor [3], or [B, 3] with a
+        [B, H, W, Cg] G-buffer (one value per scene); shininess: a number, a 0-d tensor or [B].  Tensors must be on the
+        G-buffer's device, stay there (no host synchronisation: the call can be captured in a HIP graph) and are differentiable.
+    clamp: (lo, hi) or None.
+
+    Returns [..., 3]:  clamp(lit * m + background * (1 - m), lo, hi)  with  lit = ambient * c + sum of the lights' terms,
+    each what the function of the same name in `dirt_amd.lighting` returns with vertex_colors = vertex_reflectivities = c.
+    Gradients are those of torch's autograd for that composition, including at the kinks (max(x, 0) and clamp pass the
+    gradient at their edges, abs gives 0 at 0).  A shininess below 1 at a zero cosine (0 * inf in torch) is not defined."""
+    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
+        raise ValueError('shade_gbuffer expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    if not gbuffer.is_cuda:
+        raise RuntimeError('dirt_amd.shading.shade_gbuffer runs on an MI355X only; there is no CPU fallback')
+    lights = list(lights)
+    offsets, kinds, sided, lo, hi, flags, const, tensors = _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
+                                                                            camera_position, background, clamp)
+    dev, cg, batch, width = gbuffer.device, int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None, len(const)
+    block = _const_block(dev, tuple(const))
+    if tensors:
+        rows = max(int(t.shape[0]) for _, t in tensors)
+        pieces, cursor = [], 0
+        for start, t in sorted(tensors, key=lambda st: st[0]):
+            if start > cursor:
+                pieces.append(block[:, cursor:start].expand(rows, -1))
+            pieces.append(t.expand(rows, -1))
+            cursor = start + int(t.shape[1])
+        if cursor < width:
+            pieces.append(block[:, cursor:].expand(rows, -1))
+        block = torch.cat(pieces, dim=1)
+
+    g = gbuffer.to(torch.float32).contiguous()
+    scenes = batch if batch is not None else 1
+    pixels = g.numel() // (cg * scenes) if scenes else 0
+    meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
+    return _ShadeGBuffer.apply(g, block, meta)
+
+
+def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient, camera_position, background, clamp):
+    """Everything `shade_gbuffer` refuses with a ValueError, on the tensor's shape and device alone (no device work): ->
+    (channel offsets, light kinds, sidedness, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])])."""
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('shade_gbuffer expects a float32 gbuffer, got %s' % gbuffer.dtype)
+    dev = gbuffer.device
+    cg = int(gbuffer.shape[-1])
+    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    offsets, offsets_named = [], []
+    for name, off, width, required in (('colors', colors, 3, True), ('normals', normals, 3, True), ('positions', positions, 3, False),
+                                       ('mask', mask, 1, False)):
+        if off is None and not required:
+            offsets.append(-1)
+            continue
+        if isinstance(off, bool) or not isinstance(off, int):
+            raise ValueError('%s must be the index of a G-buffer channel, got %r' % (name, off))
+        if off < 0 or off + width > cg:
+            raise ValueError('%s at channel %d does not fit in the %d channels of the G-buffer' % (name, off, cg))
+        for other, o, w in offsets_named:
+            if off < o + w and o < off + width:
+                raise ValueError('%s (channel %d) overlaps %s (channel %d)' % (name, off, other, o))
+        offsets_named.append((name, off, width))
+        offsets.append(off)
+    if len(lights) > _lib.SHADE_MAX_LIGHTS:
+        raise ValueError('shade_gbuffer takes at most %d lights, got %d' % (_lib.SHADE_MAX_LIGHTS, len(lights)))
+    if clamp is not None:
+        try:
+            lo, hi = (float(v) for v in clamp)
+        except (TypeError, ValueError):
+            raise ValueError('clamp must be (lo, hi) or None, got %r' % (clamp,))
+        if not lo <= hi:
+            raise ValueError('clamp needs lo <= hi, got %r' % (clamp,))
+    else:
+        lo, hi = 0., 0.
+    flags = (_lib.SHADE_CLAMP if clamp is not None else 0) | (_lib.SHADE_HAS_CAMERA if camera_position is not None else 0)
+
+    # the parameter block: [1 or B, 9 + 8 lights]; python numbers go into a cached constant row, tensors are spliced in with
+    # one torch.cat whose autograd hands the block's gradient back to them
+    slots = [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
+             (6, _value(camera_position if camera_position is not None else (0., 0., 0.), 3, 'camera_position', dev, batch))]
+    kinds = sided = 0
+    for l, rec in enumerate(lights):
+        if not isinstance(rec, (tuple, list)) or not rec or rec[0] not in _KINDS:
+            raise ValueError('light %d: expected a record starting with one of %s, got %r' % (l, sorted(_KINDS), rec))
+        kind = rec[0]
+        if len(rec) != (5 if kind == 'specular_directional' else 4):
+            raise ValueError('light %d: a %s record has %d fields, got %d' % (l, kind, 5 if kind == 'specular_directional' else 4, len(rec)))
+        if kind in _NEEDS_POSITIONS and positions is None:
+            raise ValueError('light %d (%s) needs the `positions` channels of the G-buffer' % (l, kind))
+        if kind == 'specular_directional' and camera_position is None:
+            raise ValueError('light %d (specular_directional) needs camera_position' % l)
+        base = _lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * l
+        slots.append((base, _value(rec[1], 3, 'light %d %s' % (l, 'position' if kind == 'diffuse_point' else 'direction'), dev, batch)))
+        slots.append((base + 3, _value(rec[2], 3, 'light %d color' % l, dev, batch)))
+        if kind == 'specular_directional':
+            slots.append((base + 6, _value(rec[3], 1, 'light %d shininess' % l, dev, batch)))
+        kinds |= _KINDS[kind] << (2 * l)
+        sided |= (1 if rec[-1] else 0) << l
+    width = _lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights)
+    const = [0.] * width
+    tensors = []
+    for start, v in slots:
+        if isinstance(v, list):
+            const[start:start + len(v)] = v
+        else:
+            tensors.append((start, v))
+    return offsets, kinds, sided, lo, hi, flags, const, tensors

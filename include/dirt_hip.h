@@ -274,6 +274,45 @@ int dirt_texture_sample_mip_backward(const float *pyramid, const float *uvs, con
                                      unsigned flags, void *stream);
 
 /*
+ * G-buffer lighting of a deferred shader, fused.  Replaces the torch composition of the reference's shader
+ * (samples/deferred.py:59-98): ambient + the reflectance models of dirt/lighting.py:175-344 per pixel, composited over a
+ * background colour through the mask channel and clamped; specification in dirt_amd/csrc/dirt_shade.hip and DESIGN.md §7b.
+ *   gbuffer [scenes, pixels, Cg], read in place (4-byte alignment suffices); off_colors / off_normals / off_positions: the
+ *   first of three channels of each attribute inside a pixel, off_mask: the mask channel; off_positions / off_mask may be
+ *   -1 (absent: no light may then need positions; every pixel covered).  Attributes may not overlap.
+ *   params [param_scenes, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights], param_scenes = 1 (one block for every
+ *   scene) or scenes: ambient[3], background[3], camera position[3], then per light {direction or position[3], colour[3],
+ *   shininess, 0}.  light_kinds: two bits per light (DIRT_SHADE_DIFFUSE_DIRECTIONAL ...), light 0 lowest; double_sided:
+ *   one bit per light.  flags: DIRT_SHADE_CLAMP (clamp to [clamp_lo, clamp_hi]), DIRT_SHADE_HAS_CAMERA (the block's
+ *   camera position is meaningful: a specular light requires it).
+ *   out [scenes, pixels, 3].
+ * Backward: grad_out [scenes, pixels, 3] -> grad_gbuffer [scenes, pixels, Cg], fully written (zeros in the channels no
+ * attribute uses), and grad_params [param_scenes, ...] shaped like params; either may be NULL and is then not computed.
+ * grad_params needs `scratch`, caller-owned, of dirt_shade_scratch_bytes(scenes, pixels, lights) bytes (0: invalid
+ * sizes): one row of partial sums per workgroup, added by a second launch in a fixed order -- no atomics, the same bits
+ * on every run.  Zero scenes or pixels: success, nothing is launched or written.  Failures: dirt_last_error().
+ */
+#define DIRT_SHADE_MAX_LIGHTS 8
+#define DIRT_SHADE_MAX_CHANNELS 1024
+#define DIRT_SHADE_PARAM_HEAD 9
+#define DIRT_SHADE_PARAM_LIGHT 8
+#define DIRT_SHADE_DIFFUSE_DIRECTIONAL 0  /* dirt/lighting.py:175-218 */
+#define DIRT_SHADE_SPECULAR_DIRECTIONAL 1 /* dirt/lighting.py:221-283 */
+#define DIRT_SHADE_DIFFUSE_POINT 2        /* dirt/lighting.py:286-344 */
+#define DIRT_SHADE_CLAMP 1u
+#define DIRT_SHADE_HAS_CAMERA 2u
+size_t dirt_shade_scratch_bytes(long long scenes, long long pixels, int lights);
+int dirt_shade_forward(const float *gbuffer, const float *params, float *out, long long scenes, long long pixels, int Cg,
+                       int off_colors, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                       unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags,
+                       void *stream);
+int dirt_shade_backward(const float *gbuffer, const float *params, const float *grad_out, float *grad_gbuffer,
+                        float *grad_params, void *scratch, size_t scratch_bytes, long long scenes, long long pixels, int Cg,
+                        int off_colors, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                        unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags,
+                        void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running

@@ -1,0 +1,633 @@
+"""`dirt_amd.shading.shade_gbuffer` (dirt_shade.hip) against the restatement of tests/shade_reference.py: the functions of
+dirt_amd/lighting.py composed on the CPU in float64, gradients by torch's autograd.  Every comparison is per element,
+|gpu - ref64| <= tol * (L1 mass of the element's terms) (+ float32's underflow floor, shade_reference.UNDERFLOW_FLOOR); an element of zero mass must equal the reference exactly;
+non-finite values must sit in the same places.
+
+The tolerances are measured, not chosen: the float32 composition (the same lighting functions, CPU, float32, torch
+autograd -- the implementation users had before the kernel) is run on `tolerance_cases()`, the inputs of the tests below,
+and its worst |f32 - ref64| / mass per kind of result is F32_*; the kernel, which may reorder a pixel's sums and use the
+hardware's reciprocal, gets 4 x that.  Produced by
+
+    python -m tests.shade_reference
+"""
+import ctypes
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import shade_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+F32_PIXELS = 7.04e-6       # worst |f32 - ref64| / mass of the float32 composition on tolerance_cases(): pixels
+F32_D_GBUFFER = {          # ... d gbuffer, by attribute.  The mass counts the two halves of d (t / |t|) / d t and of
+    'colors': 7.11e-6,     # d ((n . l) n) / d n apart (shade_reference._SplitTorch): they cancel at a specular highlight.  What is
+    'normals': 2.89e-4,    # left in the normals' and positions' figures is the conditioning of pow(cos, s): the cosine's rounding,
+    'positions': 2.89e-4,  # relative to a small cosine, times s - 1 (up to 31 here); both are set by the same pixels.
+    'mask': 1.71e-6}
+F32_D_PARAMS = 9.19e-7     # ... parameter gradients
+KERNEL = 4                 # the kernel's allowance over the float32 composition
+
+KINDS = ('diffuse_directional', 'specular_directional', 'diffuse_point')
+LAYOUTS = {   # name -> (Cg, layout): 9 without a mask, the sample's 10, 13 and 16 with the attributes in shuffled order
+    'c9': (9, dict(colors=0, normals=3, positions=6, mask=None)),
+    'c10': (10, dict(R.SAMPLE_LAYOUT)),
+    'c13': (13, dict(colors=9, normals=1, positions=5, mask=4)),
+    'c16': (16, dict(colors=12, normals=2, positions=7, mask=15)),
+}
+
+
+def _load_example(name):
+    spec = importlib.util.spec_from_file_location('example_' + name, os.path.join(ROOT, 'examples', name + '.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+class Case:
+    """Inputs of one comparison: a G-buffer whose pixels stay off the kinks, lights, the other parameters, grad_out."""
+
+    def __init__(self, seed, kinds, double_sided=True, layout='c10', shape=(4099,), batch=None, per_scene=False, mask=True,
+                 clamp=(0., 1.), band=None):
+        rng = np.random.default_rng(seed)
+        self.cg, layout = LAYOUTS[layout]
+        self.layout = dict(layout)
+        if not mask:
+            self.layout['mask'] = None
+        self.shape = ((batch,) if batch else ()) + tuple(shape)
+        n = int(np.prod(self.shape))
+        b = batch if per_scene else None
+        self.lights = R.random_lights(rng, kinds, double_sided, batch=b)
+        # keep a good share of the pixels inside the clamp: the lights' colours share the range
+        self.lights = [(r[0], r[1], (r[2] / max(1, len(kinds))).astype(np.float32)) + tuple(r[3:]) for r in self.lights]
+        vshape = (3,) if b is None else (b, 3)
+        cam = rng.standard_normal(vshape)
+        self.kw = dict(ambient=rng.uniform(0., 0.3, vshape).astype(np.float32), background=rng.uniform(0., 1., vshape).astype(np.float32),
+                       camera_position=(4. * cam / np.linalg.norm(cam, axis=-1, keepdims=True)).astype(np.float32), clamp=clamp)
+        self.idx = np.repeat(np.arange(batch), n // batch) if per_scene else None
+        self.n = n
+        self.band = band   # (first pixel, pixels): the restatement runs on this part only; grad_out is zero elsewhere
+        if band is None:
+            self.g, self.share = R.draw_off_kinks(rng, n, self.cg, self.layout, self.lights, self.kw, scene_index=self.idx)
+            self.go = rng.standard_normal((n, 3)).astype(np.float32)
+        else:
+            self.g = R.random_gbuffer(rng, n, self.cg, self.layout)
+            lo, cnt = band
+            self.g[lo:lo + cnt], self.share = R.draw_off_kinks(rng, cnt, self.cg, self.layout, self.lights, self.kw)
+            self.go = np.zeros((n, 3), np.float32)
+            self.go[lo:lo + cnt] = rng.standard_normal((cnt, 3))
+
+    def reference(self, dtype=torch.float64, masses=True):
+        lo, cnt = self.band if self.band is not None else (0, self.n)
+        return R.compose(self.g[lo:lo + cnt], self.lights, self.layout, grad_out=self.go[lo:lo + cnt], scene_index=self.idx, dtype=dtype,
+                         masses=masses, **self.kw)
+
+    def measure(self):
+        lo, cnt = self.band if self.band is not None else (0, self.n)
+        return (self.g[lo:lo + cnt], self.lights, self.layout, self.kw, self.go[lo:lo + cnt], self.idx)
+
+
+MIXED3 = ('diffuse_directional', 'specular_directional', 'diffuse_point')
+MIXED8 = MIXED3 + ('specular_directional', 'diffuse_point', 'diffuse_directional', 'specular_directional', 'diffuse_directional')
+LIGHT_SETS = {'dd': KINDS[:1], 'sd': KINDS[1:2], 'dp': KINDS[2:], 'mixed3': MIXED3, 'mixed8': MIXED8}
+
+LIGHT_CASES = [(name, ds, mask, clamp) for name in LIGHT_SETS for ds in (False, True) for mask in (False, True) for clamp in (None, (0., 1.))]
+SHAPE_CASES = {
+    'c9': dict(layout='c9'), 'c13': dict(layout='c13'), 'c16': dict(layout='c16'),
+    '1x1': dict(shape=(1, 1)), '1x257': dict(shape=(1, 257)), '33x17': dict(shape=(33, 17)), '640x480': dict(shape=(480, 640)),
+    'batch_shared': dict(shape=(33, 47), batch=3), 'batch_per_scene': dict(shape=(33, 47), batch=3, per_scene=True),
+    'batch_per_scene_large': dict(shape=(70, 61), batch=2, per_scene=True, layout='c16'),
+}
+
+
+def light_case(name, ds, mask, clamp):
+    seed = 1000 + 16 * list(LIGHT_SETS).index(name) + 8 * ds + 4 * mask + 2 * (clamp is not None)
+    sided = ds if name != 'mixed8' else [bool((k + ds) % 2) for k in range(8)]   # mixed sidedness in the 8-light set
+    return Case(seed, LIGHT_SETS[name], double_sided=sided, mask=mask, clamp=clamp)
+
+
+def shape_case(name):
+    return Case(2000 + list(SHAPE_CASES).index(name), MIXED3, double_sided=[False, True, False], **SHAPE_CASES[name])
+
+
+def band_case():
+    return Case(3000, MIXED3, double_sided=[False, False, True], layout='c16', shape=(2048, 2048), band=(1000 * 2048 + 512, 64 * 2048))
+
+
+def non_finite_case(clamp):
+    return Case(4000, MIXED3, double_sided=[False, True, False], shape=(300,), clamp=clamp)
+
+
+def sample_frame(seed, n):
+    """A frame of the sample's layout under the sample's lights, off the kinks -> (gbuffer, lights, kw, grad_out, view, light).
+    No uncovered pixels: the sample's background has two channels exactly at the clamp's lower edge."""
+    ex = _load_example('deferred')
+    rng = np.random.default_rng(seed)
+    view = ex.matrices.compose(ex.matrices.translation(torch.tensor([0., -1.5, -3.5])), ex.matrices.rodrigues(torch.tensor([-0.3, 0., 0.])))
+    light = torch.nn.functional.normalize(torch.tensor([1., -0.3, -0.5]), dim=0)
+    lights, kw = R.sample_lights(light.numpy(), torch.linalg.inv(view)[3, :3].numpy())
+    g, _ = R.draw_off_kinks(rng, n, 10, R.SAMPLE_LAYOUT, lights, kw, covered=0.9)
+    return g, lights, kw, rng.standard_normal((n, 3)).astype(np.float32), view, light
+
+
+def tolerance_cases():
+    """The inputs the float32 figures are measured on: every random input of the comparisons below -- the light and shape
+    cases, the 2048 x 2048 frame by its band, the non-finite test's frame before its pixel is spoilt, and the two frames of the
+    sample's layout.  The hand-made kink pixels are not part: they are a few exactly representable values."""
+    for args in LIGHT_CASES:
+        yield light_case(*args).measure()
+    for name in SHAPE_CASES:
+        yield shape_case(name).measure()
+    yield band_case().measure()
+    for clamp in (None, (0., 1.)):
+        yield non_finite_case(clamp).measure()
+    for seed, n in ((5, 5000), (6, 480 * 640)):
+        g, lights, kw, go, _, _ = sample_frame(seed, n)
+        yield (g, lights, R.SAMPLE_LAYOUT, kw, go, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------- helpers
+
+def close(got, ref, mass, tol, what):
+    got = np.asarray(got.detach().cpu() if isinstance(got, torch.Tensor) else got, dtype=np.float64).reshape(np.shape(ref))
+    ref, mass = np.asarray(ref, dtype=np.float64), np.asarray(mass, dtype=np.float64)
+    fin = np.isfinite(ref)
+    assert np.array_equal(np.isfinite(got), fin), '%s: non-finite values in other places than the restatement' % what
+    err = np.where(fin, np.abs(got - np.where(fin, ref, 0.)), 0.)
+    zero = fin & ~(mass > 0)
+    assert np.all(err[zero] == 0.), '%s: %d elements of zero mass differ from the restatement' % (what, int((err[zero] != 0).sum()))
+    pos = fin & (mass > 0) & np.isfinite(mass)
+    err = np.maximum(err - R.UNDERFLOW_FLOOR, 0.)   # float32's underflow, not the kernel's error (tests/shade_reference.py)
+    ratio = float((err[pos] / mass[pos]).max()) if pos.any() else 0.
+    print('%-60s worst |gpu - ref64| / mass = %.3e (tol %.3e)' % (what, ratio, tol))
+    assert ratio <= tol, '%s: |gpu - ref64| / mass = %.3e > %.3e at element %d' % (what, ratio, tol, int(np.argmax(np.where(pos, err / np.where(pos, mass, 1.), 0.))))
+    return ratio
+
+
+def close_gbuffer(got, ref, mass, layout, factor, what):
+    """d gbuffer attribute by attribute, each with its own measured figure; the channels no attribute uses must be exactly 0"""
+    got = np.asarray(got.detach().cpu() if isinstance(got, torch.Tensor) else got, dtype=np.float64).reshape(np.shape(ref))
+    ref, mass = np.asarray(ref, dtype=np.float64), np.asarray(mass, dtype=np.float64)
+    used = np.zeros(ref.shape[-1], bool)
+    for name, sl in R.attribute_slices(layout).items():
+        close(got[:, sl], ref[:, sl], mass[:, sl], factor * F32_D_GBUFFER[name], '%s d_%s' % (what, name))
+        used[sl] = True
+    assert not got[:, ~used].any(), what + ': a channel no attribute uses received a gradient'
+
+
+def run_fused(case, dev, g=None, grad=True, params_grad=True, g_grad=True):
+    """-> (out, d gbuffer or None, {name: gradient}) of shade_gbuffer with every parameter a GPU tensor"""
+    from dirt_amd import shading
+    if g is None:
+        g = torch.from_numpy(case.g).to(dev).reshape(case.shape + (case.cg,))
+    g = g.detach().requires_grad_(g_grad)
+    named = {}
+
+    def T(name, x):
+        named[name] = torch.from_numpy(np.asarray(x, dtype=np.float32)).to(dev).requires_grad_(params_grad)
+        return named[name]
+
+    lights = []
+    for i, rec in enumerate(case.lights):
+        vec, col = T('light%d.vector' % i, rec[1]), T('light%d.color' % i, rec[2])
+        extra = (T('light%d.shininess' % i, rec[3]),) if rec[0] == 'specular_directional' else ()
+        lights.append((rec[0], vec, col) + extra + (rec[-1],))
+    kw = {k: T(k, case.kw[k]) for k in ('ambient', 'background', 'camera_position')}
+    out = shading.shade_gbuffer(g, lights, clamp=case.kw['clamp'], **case.layout, **kw)
+    if not grad:
+        return out, None, named
+    out.backward(torch.from_numpy(case.go).to(dev).reshape(out.shape))
+    return out, g.grad, {k: t.grad for k, t in named.items()}
+
+
+def compare(case, dev, what, g=None):
+    ref = case.reference()
+    out, dg, dp = run_fused(case, dev, g=g)
+    lo, cnt = case.band if case.band is not None else (0, case.n)
+    out, dg = out.reshape(-1, 3), dg.reshape(-1, case.cg)
+    close(out[lo:lo + cnt], ref['out'], ref['mass_out'], KERNEL * F32_PIXELS, what + ' pixels')
+    close_gbuffer(dg[lo:lo + cnt], ref['d_gbuffer'], ref['mass_gbuffer'], case.layout, KERNEL, what)
+    if case.band is not None:   # grad_out is zero outside the band: so is d gbuffer, exactly
+        assert not dg[:lo].any() and not dg[lo + cnt:].any()
+    for k, want in ref['d_params'].items():
+        close(dp[k], want, ref['mass_params'][k], KERNEL * F32_D_PARAMS, what + ' d_' + k)
+    return out, dg, dp
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU tests
+
+def test_restatement_in_float32_is_the_sample_shader():
+    """The restatement with the sample's lights, run in float32, equals examples/deferred.py::shader_fn on a CPU G-buffer of
+    the sample's layout: pixels and all gradients to the last few ulps."""
+    ex = _load_example('deferred')
+    g, lights, kw, go, view, light = sample_frame(5, 5000)
+    r32 = R.compose(g, lights, R.SAMPLE_LAYOUT, grad_out=go, dtype=torch.float32, masses=False, **kw)
+    gt, lt, vt = torch.from_numpy(g).requires_grad_(True), light.clone().requires_grad_(True), view.clone().requires_grad_(True)
+    px = ex.shader_fn(gt, vt, lt)
+    px.backward(torch.from_numpy(go))
+    r64 = R.compose(g, lights, R.SAMPLE_LAYOUT, grad_out=go, dtype=torch.float64, **kw)
+    # two float32 evaluations of one composition, each within F32_* of the float64 one (they differ in the order of three
+    # additions and in torch's pow for a python-number exponent): within 2 x F32_* of each other
+    assert R.worst_ratio(px.detach(), r32['out'], r64['mass_out']) <= 2 * F32_PIXELS
+    for name, sl in R.attribute_slices(R.SAMPLE_LAYOUT).items():
+        assert R.worst_ratio(gt.grad[:, sl], r32['d_gbuffer'][:, sl], r64['mass_gbuffer'][:, sl]) <= 2 * F32_D_GBUFFER[name], name
+    d_light = r32['d_params']['light0.vector'] + r32['d_params']['light1.vector']
+    m_light = r64['mass_params']['light0.vector'] + r64['mass_params']['light1.vector']
+    assert R.worst_ratio(lt.grad[None], d_light, m_light) <= 2 * F32_D_PARAMS
+    # the view matrix receives the camera position's gradient through inv(): compare that
+    (d_cam_view,) = torch.autograd.grad(torch.linalg.inv(vt)[3, :3], vt, r32['d_params']['camera_position'][0])
+    assert torch.allclose(vt.grad, d_cam_view, rtol=1e-4, atol=1e-7)
+    assert bool((px.detach() != r32['out']).float().mean() < 0.5)   # and most pixels agree exactly
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from dirt_amd import build, _lib
+    build.build_library()
+    return _lib.load()
+
+
+def test_c_entry_points_refuse_bad_arguments_without_a_device(lib):
+    from dirt_amd import _lib
+    one = ctypes.c_void_p(16)   # never dereferenced: validation fails first
+    good = dict(scenes=1, pixels=64, cg=10, oc=4, on=7, op=1, om=0, ps=1, nl=2, kinds=0 | (1 << 2), sided=0, lo=0., hi=1., flags=3)
+
+    def fwd(g=one, p=one, o=one, **over):
+        a = dict(good, **over)
+        return lib.dirt_shade_forward(g, p, o, a['scenes'], a['pixels'], a['cg'], a['oc'], a['on'], a['op'], a['om'], a['ps'], a['nl'], a['kinds'],
+                                      a['sided'], a['lo'], a['hi'], a['flags'], None)
+
+    def bwd(g=one, p=one, go=one, gg=one, gp=one, scratch=one, nbytes=1 << 20, **over):
+        a = dict(good, **over)
+        return lib.dirt_shade_backward(g, p, go, gg, gp, scratch, nbytes, a['scenes'], a['pixels'], a['cg'], a['oc'], a['on'], a['op'], a['om'],
+                                       a['ps'], a['nl'], a['kinds'], a['sided'], a['lo'], a['hi'], a['flags'], None)
+
+    bad = [dict(g=None), dict(p=None), dict(o=None), dict(scenes=-1), dict(pixels=-5), dict(cg=0), dict(oc=8), dict(on=-1), dict(oc=6),
+           dict(op=2), dict(om=5), dict(om=10), dict(op=9), dict(nl=9), dict(nl=-1), dict(op=-1), dict(flags=1), dict(kinds=3), dict(ps=2),
+           dict(lo=2., hi=1.)]
+    for over in bad:
+        assert fwd(**over) == _lib.E_INVALID_ARGUMENT, over
+        assert lib.dirt_last_error().startswith(b'dirt_shade_forward'), over
+    for over in bad:
+        over = {('go' if k == 'o' else k): v for k, v in over.items()}
+        assert bwd(**over) == _lib.E_INVALID_ARGUMENT, over
+        assert lib.dirt_last_error().startswith(b'dirt_shade_backward'), over
+    assert bwd(scratch=None) == _lib.E_INVALID_ARGUMENT and bwd(nbytes=8) == _lib.E_INVALID_ARGUMENT
+    assert bwd(scratch=ctypes.c_void_p(18)) == _lib.E_INVALID_ARGUMENT
+    with pytest.raises(ValueError, match='dirt_shade_backward'):
+        _lib.check(bwd(nbytes=8))
+    # zero pixels (or scenes): a success that launches nothing, whatever the pointers
+    assert fwd(g=None, p=None, o=None, pixels=0) == 0 and fwd(scenes=0, ps=0) == 0
+    assert bwd(g=None, p=None, go=None, gg=None, gp=None, scratch=None, nbytes=0, pixels=0) == 0
+    assert lib.dirt_last_error() == b''
+    # scratch: one row of 9 + 8 lights floats per workgroup of 1024 pixels and scene
+    assert lib.dirt_shade_scratch_bytes(1, 2048 * 2048, 2) == 4096 * 25 * 4
+    assert lib.dirt_shade_scratch_bytes(3, 1025, 8) == 3 * 2 * 73 * 4
+    assert lib.dirt_shade_scratch_bytes(1, 0, 0) == 0 and lib.dirt_shade_scratch_bytes(-1, 5, 0) == 0 and lib.dirt_shade_scratch_bytes(1, 5, 9) == 0
+
+
+def test_shade_gbuffer_refuses_bad_arguments():
+    from dirt_amd import shading
+    with pytest.raises(RuntimeError, match='no CPU fallback'):
+        shading.shade_gbuffer(torch.zeros(4, 4, 10), [], colors=4, normals=7)
+    g = torch.zeros(4, 4, 10)   # the checks behind the device check, called directly: they look at shape and device only
+
+    def check(g, lights, colors, normals, positions=None, mask=None, ambient=(0., 0., 0.), camera_position=None, background=(0., 0., 0.),
+              clamp=(0., 1.)):
+        return shading._check_arguments(g, list(lights), colors, normals, positions, mask, ambient, camera_position, background, clamp)
+
+    d, c = (0., 0., -1.), (1., 1., 1.)
+    ok = dict(colors=4, normals=7, positions=1, mask=0)
+    for kw, lights, match in (
+            (dict(ok, colors=8), [], 'does not fit'), (dict(ok, mask=10), [], 'does not fit'), (dict(ok, normals=-1), [], 'does not fit'),
+            (dict(ok, positions=3), [], 'overlaps'), (dict(ok, mask=5), [], 'overlaps'), (dict(ok, colors=4.), [], 'index of a G-buffer channel'),
+            (ok, [('diffuse_directional', d, c, True)] * 9, 'at most 8'),
+            (ok, [('lambert', d, c, True)], 'expected a record'), (ok, [('diffuse_directional', d, c)], 'has 4 fields'),
+            (ok, [('specular_directional', d, c, 6., True)], 'needs camera_position'),
+            (dict(ok, positions=None), [('diffuse_point', d, c, True)], 'needs the `positions`'),
+            (ok, [('diffuse_directional', (0., 1.), c, True)], '3 numbers'),
+            (ok, [('diffuse_directional', torch.zeros(2, 3), c, True)], 'must have shape'),
+            (dict(ok, clamp=(1., 0.)), [], 'lo <= hi'), (dict(ok, clamp=3.), [], 'clamp must be'),
+            (dict(ok, ambient=(1., 2.)), [], '3 numbers')):
+        with pytest.raises(ValueError, match=match):
+            check(g, lights, **kw)
+    assert check(g, [('diffuse_directional', d, c, True)], **ok)[0] == [4, 7, 1, 0]
+    with pytest.raises(ValueError, match='expects gbuffer'):
+        shading.shade_gbuffer(torch.zeros(5), [], colors=0, normals=3)
+
+
+def test_the_module_is_exported_under_both_package_names():
+    import dirt
+    import dirt_amd
+    import dirt.shading
+    assert dirt.shading is dirt_amd.shading and callable(dirt_amd.shading.shade_gbuffer)
+    from dirt_amd import build
+    assert 'dirt_shade.hip' in build.SOURCES
+
+
+def test_test_data_stays_off_the_kinks():
+    """Drawn pixels are rejected against the float64 restatement; under 5 % of a first draw may be (Case asserts it)."""
+    for case in (light_case('mixed8', True, True, (0., 1.)), shape_case('c16')):
+        assert case.share < 0.05
+        assert bool(R.off_kinks(case.reference(masses=False), case.kw['clamp']).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU tests
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name,ds,mask,clamp', LIGHT_CASES, ids=['%s-%s-%s-%s' % (n, 'double' if d else 'single', 'mask' if m else 'nomask',
+                                                                                      'clamp' if c else 'noclamp') for n, d, m, c in LIGHT_CASES])
+def test_light_kinds_against_the_restatement(gpu, name, ds, mask, clamp):
+    compare(light_case(name, ds, mask, clamp), gpu, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', list(SHAPE_CASES))
+def test_layouts_and_shapes_against_the_restatement(gpu, name):
+    compare(shape_case(name), gpu, name)
+
+
+@pytest.mark.gpu
+def test_a_2048x2048x16_frame_against_the_restatement_on_a_band(gpu):
+    """The restatement runs on a 64-row band of the frame; grad_out is zero outside it, so that the parameter gradients of the
+    whole frame are the band's and d gbuffer is exactly zero elsewhere."""
+    compare(band_case(), gpu, '2048x2048x16')
+
+
+@pytest.mark.gpu
+def test_non_contiguous_and_misaligned_gbuffers(gpu):
+    case = shape_case('33x17')
+    wide = torch.zeros(33, 17, 14, device=gpu)
+    wide[..., 2:12] = torch.from_numpy(case.g).to(gpu).reshape(33, 17, 10)
+    compare(case, gpu, 'non-contiguous', g=wide[..., 2:12])
+    flat = torch.zeros(33 * 17 * 10 + 1, device=gpu)
+    flat[1:] = torch.from_numpy(case.g).to(gpu).reshape(-1)
+    view = flat[1:].view(33, 17, 10)
+    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+    compare(case, gpu, 'misaligned', g=view)
+
+
+def _constructed(dev, rows, lights, kw, go=None, layout=R.SAMPLE_LAYOUT, tensors=()):
+    """fused and restated results on hand-made pixels (rows of the sample's layout); `tensors`: parameter names made GPU leaves"""
+    from dirt_amd import shading
+    g_np = np.asarray(rows, dtype=np.float32)
+    go_np = np.ones((len(g_np), 3), np.float32) if go is None else np.asarray(go, np.float32)
+    ref = R.compose(g_np, lights, layout, grad_out=go_np, **kw)
+    g = torch.from_numpy(g_np).to(dev).requires_grad_(True)
+    named = {}
+
+    def T(name, x):
+        if name not in tensors:
+            return x
+        named[name] = torch.tensor(np.asarray(x, dtype=np.float32), device=dev, requires_grad=True)
+        return named[name]
+
+    gl = [(r[0], T('light%d.vector' % i, r[1]), T('light%d.color' % i, r[2])) + ((T('light%d.shininess' % i, r[3]),) if len(r) == 5 else ()) + (r[-1],)
+          for i, r in enumerate(lights)]
+    gkw = {k: (T(k, v) if k != 'clamp' and v is not None else v) for k, v in kw.items()}
+    out = shading.shade_gbuffer(g, gl, **layout, **gkw)
+    out.backward(torch.from_numpy(go_np).to(dev))
+    return ref, out, g.grad, {k: t.grad for k, t in named.items()}
+
+
+def _check_constructed(ref, out, dg, dp, what):
+    close(out, ref['out'], ref['mass_out'], KERNEL * F32_PIXELS, what + ' pixels')
+    close_gbuffer(dg, ref['d_gbuffer'], ref['mass_gbuffer'], R.SAMPLE_LAYOUT, KERNEL, what)
+    for k, v in dp.items():
+        close(v, ref['d_params'][k], ref['mass_params'][k], KERNEL * F32_D_PARAMS, what + ' d_' + k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('double_sided', [False, True])
+def test_kink_background_pixels(gpu, double_sided):
+    """The commonest pixel of a real frame: all attributes zero, so every cosine is exactly 0.  max(x, 0) passes the gradient
+    there, abs gives 0; the mask still receives lit - background."""
+    d = np.asarray([0.6, -0.64, -0.48], np.float32)
+    lights = [('diffuse_directional', d, (1., 0.5, 0.25), double_sided), ('specular_directional', d, (1., 1., 1.), 6., double_sided),
+              ('diffuse_point', (2., 1., -1.), (0.3, 0.3, 0.9), double_sided)]
+    kw = dict(ambient=(0.2, 0.2, 0.2), background=(0., 0., 0.3), camera_position=(0.5, 1.5, 3.), clamp=(0., 1.))
+    rows = [[0.] * 10, [0.] * 10, [1., 0.1, 0.2, 0.3, 0.5, 0.6, 0.7, 0., 0., 1.], [0., 0.1, 0.2, 0.3, 0.5, 0.6, 0.7, 0., 0., 0.]]
+    tensors = ('light0.vector', 'light1.vector', 'light2.vector', 'light1.shininess', 'background', 'ambient', 'camera_position', 'light0.color')
+    ref, out, dg, dp = _constructed(gpu, rows, lights, kw, tensors=tensors)
+    _check_constructed(ref, out, dg, dp, 'background pixels, double_sided=%s' % double_sided)
+    # the difference the two conventions make is visible in the restatement itself: the normal of a zero pixel gets a gradient
+    # from max(x, 0) only if its mask is non-zero; at least the mask gradient is non-zero here (lit - background = -0.3 in blue)
+    assert float(dg[0, 0]) == pytest.approx(-0.3, abs=1e-6)
+
+
+@pytest.mark.gpu
+def test_kink_single_sided_zero_cosine_passes_the_gradient(gpu):
+    """A covered pixel whose normal is exactly perpendicular to the light: max(cos, 0) passes the gradient at cos == 0 (the
+    normal's gradient is the light's), abs gives 0."""
+    rows = [[1., 0., 0., 0., 0.5, 0.5, 0.5, 1., 0., 0.]]
+    for ds in (False, True):
+        lights = [('diffuse_directional', (0., 0., -1.), (1., 1., 1.), ds)]
+        ref, out, dg, dp = _constructed(gpu, rows, lights, dict(ambient=(0.1, 0.1, 0.1), clamp=(0., 1.)), tensors=('light0.vector',))
+        _check_constructed(ref, out, dg, dp, 'zero cosine, double_sided=%s' % ds)
+        assert (float(dg[0, 9]) != 0.) == (not ds)
+
+
+@pytest.mark.gpu
+def test_kink_where_the_1e_12_sits(gpu):
+    """The reference's two 1e-12s are visible only where the rest vanishes.  Pixel 0: the view vector is exactly perpendicular to
+    the reflected direction (zero normal, so r = d = x; camera straight above), so cos = 1e-12 * sum(r) and, without ambient, the
+    pixel is 1e-12 * colour -- 0 if the 1e-12 were added anywhere else.  Pixel 1 sits exactly at the point light: e = 0 and
+    e / (|e| + 1e-12) = 0 where e / |e| would be NaN; the gradient to its position is n * 1e12, finite."""
+    lights = [('specular_directional', (1., 0., 0.), (1., 1., 1.), 1., False), ('diffuse_point', (0.25, 0.5, -1.), (1., 1., 1.), False)]
+    kw = dict(ambient=(0., 0., 0.), camera_position=(0., 0., 3.), clamp=None)
+    rows = [[1., 0., 0., 0., 0.5, 0.25, 1., 0., 0., 0.], [1., 0.25, 0.5, -1., 0.5, 0.5, 0.5, 0., 0.6, 0.8]]
+    ref, out, dg, dp = _constructed(gpu, rows, lights, kw, tensors=('light0.vector', 'light1.vector', 'camera_position'))
+    _check_constructed(ref, out, dg, dp, 'the 1e-12s')
+    assert float(out[0, 2]) == pytest.approx(1e-12, rel=1e-5) and bool(torch.isfinite(dg).all()) and float(dg[1, 1:4].abs().max()) > 1e10
+
+
+@pytest.mark.gpu
+def test_kink_clamp_edges_pass_the_gradient(gpu):
+    """Pre-clamp values exactly at lo and at hi (exactly representable: colour x ambient with powers of two): torch's clamp
+    passes the gradient at both edges; just outside it does not."""
+    kw = dict(ambient=(0.5, 0.5, 0.5), background=(0., 0., 0.), clamp=(0.25, 1.))
+    rows = [[1., 0., 0., 0., 0.5, 2., 2.5, 0., 0., 1.],     # pre = 0.25 (lo), 1 (hi), 1.25 (above)
+            [1., 0., 0., 0., 0.25, 1., 0.5, 0., 0., 1.]]    # pre = 0.125 (below), 0.5, 0.25 (lo)
+    ref, out, dg, dp = _constructed(gpu, rows, [], kw, tensors=('ambient',))
+    _check_constructed(ref, out, dg, dp, 'clamp edges')
+    assert dg[0, 4:7].tolist() == [0.5, 0.5, 0.] and dg[1, 4:7].tolist() == [0., 0.5, 0.5]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shininess', [1., 2., 6.])
+def test_kink_zero_cosine_under_pow(gpu, shininess):
+    """pow(0, s): gradient 0 to s; to its base 0 for s > 1 and 1 at s = 1.  Both lights have a zero direction, so the reflected
+    direction and with it the cosine are exactly 0, single sided (light 0) and double sided (light 1), on a covered and on an
+    uncovered pixel."""
+    lights = [('specular_directional', (0., 0., 0.), (1., 1., 1.), shininess, False),
+              ('specular_directional', (0., 0., 0.), (1., 1., 1.), shininess, True)]
+    kw = dict(ambient=(0.1, 0.1, 0.1), camera_position=(0., 0., 3.), clamp=None)
+    rows = [[1., 0.1, 0.2, 0., 0.5, 0.5, 0.5, 0., 0., 1.], [1., 0., 0., 0., 1., 1., 1., 0., 0., 0.]]
+    tensors = ('light0.vector', 'light0.shininess', 'light1.shininess', 'camera_position')
+    ref, out, dg, dp = _constructed(gpu, rows, lights, kw, tensors=tensors)
+    _check_constructed(ref, out, dg, dp, 'pow(0, %g)' % shininess)
+    assert float(dp['light0.shininess']) == 0. and float(dp['light1.shininess']) == 0.
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('bad', [float('nan'), float('inf')])
+@pytest.mark.parametrize('attribute', ['normals', 'colors', 'positions', 'mask'])
+@pytest.mark.parametrize('clamp', [None, (0., 1.)])
+def test_non_finite_values_stay_in_their_pixel(gpu, bad, attribute, clamp):
+    """A non-finite attribute makes its own pixel's output and gradient (and the parameter gradients) non-finite exactly where the
+    composition does; every other pixel's output and d gbuffer are what they are without it."""
+    case = non_finite_case(clamp)
+    clean = case.reference()
+    victim = 137
+    case.g[victim, case.layout[attribute]] = bad
+    ref = case.reference()
+    out, dg, dp = run_fused(case, gpu)
+    out, dg = out.detach().cpu().numpy(), dg.cpu().numpy()
+    others = np.arange(case.n) != victim
+    close(out[others], clean['out'][others], clean['mass_out'][others], KERNEL * F32_PIXELS, 'other pixels')
+    close_gbuffer(dg[others], clean['d_gbuffer'][others], clean['mass_gbuffer'][others], case.layout, KERNEL, 'other pixels')
+    assert np.array_equal(np.isfinite(out[victim]), np.isfinite(ref['out'][victim].numpy()))
+    assert np.array_equal(np.isfinite(dg[victim]), np.isfinite(ref['d_gbuffer'][victim].numpy()))
+    for k, want in ref['d_params'].items():
+        assert np.array_equal(np.isfinite(dp[k].cpu().numpy().reshape(want.shape)), np.isfinite(want.numpy())), k
+
+
+@pytest.mark.gpu
+def test_only_the_needed_gradients(gpu):
+    case = shape_case('33x17')
+    ref = case.reference()
+    out, dg, dp = run_fused(case, gpu, params_grad=False)
+    assert all(v is None for v in dp.values())
+    close_gbuffer(dg.reshape(-1, case.cg), ref['d_gbuffer'], ref['mass_gbuffer'], case.layout, KERNEL, 'no parameter gradient:')
+    out, dg, dp = run_fused(case, gpu, g_grad=False)
+    assert dg is None
+    for k, want in ref['d_params'].items():
+        close(dp[k], want, ref['mass_params'][k], KERNEL * F32_D_PARAMS, 'no G-buffer gradient: d_' + k)
+    out, _, _ = run_fused(case, gpu, grad=False, params_grad=False, g_grad=False)
+    assert not out.requires_grad
+
+
+@pytest.mark.gpu
+def test_parameter_gradients_are_reproducible_and_backward_is_reentrant(gpu):
+    case = shape_case('640x480')
+    _, dg1, dp1 = run_fused(case, gpu)
+    _, dg2, dp2 = run_fused(case, gpu)
+    assert torch.equal(dg1, dg2)
+    for k in dp1:
+        assert torch.equal(dp1[k], dp2[k]), k      # bit for bit: fixed-order sums, no atomics
+    # backward twice over one forward (retain_graph=True, as _RasteriseDeferred.backward calls it)
+    from dirt_amd import shading
+    g = torch.from_numpy(case.g).to(gpu).reshape(case.shape + (case.cg,)).requires_grad_(True)
+    d = torch.tensor(case.lights[0][1], device=gpu, requires_grad=True)
+    out = shading.shade_gbuffer(g, [('diffuse_directional', d, (0.5, 0.4, 0.3), False)], ambient=(0.1, 0.1, 0.1), **case.layout)
+    go = torch.from_numpy(case.go).to(gpu).reshape(out.shape)
+    a = torch.autograd.grad(out, [g, d], go, retain_graph=True)
+    b = torch.autograd.grad(out, [g, d], go, retain_graph=True)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and a[0].data_ptr() != b[0].data_ptr()
+
+
+def _sample_fused_shader(gbuffer, view_matrix, light_direction):
+    from dirt_amd import shading
+    lights, kw = R.sample_lights(light_direction, torch.linalg.inv(view_matrix)[3, :3])
+    return shading.shade_gbuffer(gbuffer, lights, **R.SAMPLE_LAYOUT, **kw)
+
+
+@pytest.mark.gpu
+def test_equals_the_sample_shader_on_the_gpu(gpu):
+    """shade_gbuffer with the sample's lights against examples/deferred.py::shader_fn on the GPU.  Both are float32
+    implementations of one composition: torch's is within F32_* of the float64 restatement, the kernel within 4 x that, so
+    they are within 5 x of each other, per element, by the element's mass."""
+    ex = _load_example('deferred')
+    g_np, lights, kw, go_np, view, light = sample_frame(6, 480 * 640)
+    ref = R.compose(g_np, lights, R.SAMPLE_LAYOUT, grad_out=go_np, **kw)
+    res = []
+    for fn in (ex.shader_fn, _sample_fused_shader):
+        g = torch.from_numpy(g_np).to(gpu).reshape(480, 640, 10).requires_grad_(True)
+        v, l = view.to(gpu).requires_grad_(True), light.to(gpu).requires_grad_(True)
+        px = fn(g, v, l)
+        px.backward(torch.from_numpy(go_np).to(gpu).reshape(px.shape))
+        res.append((px.detach().reshape(-1, 3), g.grad.reshape(-1, 10), l.grad, v.grad))
+    (pa, ga, la, va), (pb, gb, lb, vb) = res
+    close(pb, pa.cpu().numpy(), ref['mass_out'], 5 * F32_PIXELS, 'fused vs torch on the GPU: pixels')
+    close_gbuffer(gb, ga.cpu().numpy(), ref['mass_gbuffer'], R.SAMPLE_LAYOUT, 5, 'fused vs torch on the GPU:')
+    m_light = ref['mass_params']['light0.vector'] + ref['mass_params']['light1.vector']
+    close(lb[None], la[None].cpu().numpy(), m_light, 5 * F32_D_PARAMS, 'fused vs torch on the GPU: d_light')
+    # the view matrix gets the camera position's gradient through inv(): linear in it, so the camera's mass carries over
+    m_view = torch.autograd.functional.jacobian(lambda m: torch.linalg.inv(m)[3, :3], view.double()).abs().permute(1, 2, 0) @ \
+        ref['mass_params']['camera_position'][0]
+    close(vb, va.cpu().numpy(), m_view, 5 * F32_D_PARAMS, 'fused vs torch on the GPU: d_view')
+
+
+@pytest.mark.gpu
+def test_rasterise_deferred_with_the_fused_shader(gpu):
+    """End to end on the cube of examples/deferred.py: rasterise_deferred with the fused shader against the same call with the
+    torch shader.  Pixels and the light's gradient by the mass rule (5 x the float32 figure, as above; masses from the
+    restatement on the rasterised G-buffer).  The vertex and view-matrix gradients come from filtering the shaded image,
+    where a one-ulp pixel difference can flip a discrete dilation choice, and no mass is at hand for them: an element counts as
+    agreeing if |a - b| <= 1e-3 * max(|a|, |b|) (or both are below 1e-7); elements that do not are excluded, and their share
+    is capped at 1 % per tensor."""
+    import dirt_amd
+    ex = _load_example('deferred')
+    verts_np, faces_np = ex.build_cube()
+    results = []
+    for fn in (ex.shader_fn, _sample_fused_shader):
+        vertices = torch.from_numpy(verts_np).to(gpu).requires_grad_(True)
+        faces = torch.from_numpy(faces_np).to(gpu)
+        view = ex.matrices.compose(ex.matrices.translation(torch.tensor([0., -1.5, -3.5], device=gpu)),
+                                   ex.matrices.rodrigues(torch.tensor([-0.3, 0., 0.], device=gpu))).requires_grad_(True)
+        light = torch.nn.functional.normalize(torch.tensor([1., -0.3, -0.5], device=gpu), dim=0).requires_grad_(True)
+        clip, f2, attributes = ex.geometry(vertices, faces, view)
+        pixels = dirt_amd.rasterise_deferred(vertices=clip, vertex_attributes=attributes, faces=f2,
+                                             background_attributes=torch.zeros([ex.frame_height, ex.frame_width, 10], device=gpu),
+                                             shader_fn=fn, shader_additional_inputs=[view, light])
+        (pixels ** 2).mean().backward()
+        gbuf = dirt_amd.rasterise(torch.zeros([ex.frame_height, ex.frame_width, 10], device=gpu), clip.detach(), attributes.detach(), f2)
+        results.append((pixels.detach(), vertices.grad, view.grad, light.grad, gbuf, view.detach(), light.detach()))
+    (pa, va, wa, la, gbuf, view, light), (pb, vb, wb, lb, _, _, _) = results
+    lights, kw = R.sample_lights(light.cpu().numpy(), torch.linalg.inv(view)[3, :3].cpu().numpy())
+    go = (2. / pa.numel()) * pa.reshape(-1, 3).cpu().numpy()
+    ref = R.compose(gbuf.reshape(-1, 10).cpu().numpy(), lights, R.SAMPLE_LAYOUT, grad_out=go, **kw)
+    close(pb.reshape(-1, 3), pa.reshape(-1, 3).cpu().numpy(), ref['mass_out'], 5 * F32_PIXELS, 'deferred: pixels')
+    m_light = ref['mass_params']['light0.vector'] + ref['mass_params']['light1.vector']
+    close(lb[None], la[None].cpu().numpy(), m_light, 5 * F32_D_PARAMS, 'deferred: d_light')
+    for name, a, b in (('vertices', va, vb), ('view matrix', wa, wb)):
+        a, b = a.cpu().double(), b.cpu().double()
+        agree = ((a - b).abs() <= 1e-3 * torch.maximum(a.abs(), b.abs())) | ((a.abs() < 1e-7) & (b.abs() < 1e-7))
+        share = 1. - float(agree.double().mean())
+        print('deferred: d_%s: %d of %d elements excluded' % (name, int((~agree).sum()), agree.numel()))
+        assert share <= 0.01, (name, share)
+        assert bool(a.abs().max() > 0)
+
+
+@pytest.mark.gpu
+def test_graphed_step_captures_the_fused_shader(gpu):
+    """A GraphedStep whose loss shades its pixels (a 10-channel rasterise_batch as the G-buffer) with shade_gbuffer captures --
+    the call makes no host synchronisation -- and its replay returns the loss and gradients of the eager step."""
+    import dirt_amd
+    from dirt_amd import shading
+    from tests import scenes
+    s = scenes.rand_scene(200, 96, 128, 10, 41, 0.05, 0.3)
+    bg, v, vc, f = (torch.from_numpy(s[k][None].copy()).to(gpu) for k in ('background', 'vertices', 'vertex_colors', 'faces'))
+    direction = torch.tensor([0.6, -0.64, -0.48], device=gpu, requires_grad=True)
+    camera = torch.tensor([0.5, 1.5, 3.], device=gpu)
+    lights, kw = R.sample_lights(direction, camera)
+
+    def loss_fn(px):
+        return (shading.shade_gbuffer(px, lights, **R.SAMPLE_LAYOUT, **kw) ** 2).mean()
+
+    step = dirt_amd.GraphedStep(bg, v, vc, f, loss_fn=loss_fn)
+    for _ in range(2):
+        loss, (gb, gv, gvc) = step()
+    leaves = [t.detach().clone().requires_grad_(True) for t in (bg, v, vc)]
+    eager = loss_fn(dirt_amd.rasterise_batch(leaves[0], leaves[1], leaves[2], f))
+    eager.backward()
+    torch.cuda.synchronize()
+    assert float((loss - eager).detach().abs()) <= 1e-6 * float(eager.detach().abs())
+    assert torch.equal(gb, leaves[0].grad)      # d gbuffer outside the mesh: the kernel's own output, no atomics on the way
+    assert bool(gb.abs().max() > 0)
+    for a, b in ((gv, leaves[1].grad), (gvc, leaves[2].grad)):   # float atomics in the rasteriser's gradient: summation order
+        agree = (a - b).abs() <= 1e-4 * torch.maximum(a.abs(), b.abs()) + 1e-9
+        assert float(agree.float().mean()) >= 0.99
