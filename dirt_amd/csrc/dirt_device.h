@@ -208,10 +208,11 @@ __device__ inline void edge_eval(const double* coef, double px, double py, doubl
 // Perspective-correct barycentrics and clip-space w of the fragment (csrc/shaders.cpp:52-57,74).
 __device__ inline void bary_eval(const double F[3], uint32_t flags, double inv_det, float b[3], float& clip_w)
 {
-    const double s0 = (flags & 1u) ? -inv_det : inv_det;
-    const double s1 = (flags & 2u) ? -inv_det : inv_det;
-    const double s2 = (flags & 4u) ? -inv_det : inv_det;
-    const float l0 = (float)(F[0] * s0), l1 = (float)(F[1] * s1), l2 = (float)(F[2] * s2);
+    // lambda_k = (float)(F_k * +-inv_det), the sign by the fold flag: taken as a sign flip of the rounded float32 product, which
+    // is the same number bit for bit (rounding to nearest is symmetric: (-F) d rounds to -(F d)) without the three f64 selects
+    const float l0 = __uint_as_float(__float_as_uint((float)(F[0] * inv_det)) ^ (flags << 31));
+    const float l1 = __uint_as_float(__float_as_uint((float)(F[1] * inv_det)) ^ ((flags << 30) & 0x80000000u));
+    const float l2 = __uint_as_float(__float_as_uint((float)(F[2] * inv_det)) ^ ((flags << 29) & 0x80000000u));
     const float s = (l0 + l1) + l2;
     const float r = 1.0f / s;
     b[0] = l0 * r; b[1] = l1 * r; b[2] = l2 * r;

@@ -23,6 +23,7 @@
 //     colours for the shading pass.  Coverage, depth and shading arithmetic are dirt_raster.hip's (dirt_raster_common.h).
 //     Two shapes: four waves per 32 x 32 tile (16 x 16 pixels each), and eight half-size waves for launches of at most 2048
 //     tiles, which end with their heaviest wave.
+#include <type_traits>
 #include "dirt_device.h"
 #include "dirt_launch.h"
 #include "dirt_raster_common.h"
@@ -61,6 +62,25 @@ __device__ __forceinline__ void glds16(const void* base, uint32_t voff, uint32_t
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds_addr) : "memory");
 }
+
+// An object in LDS, said so in its type: what is read through such a pointer is a ds_read whatever the optimiser merges.
+#define DIRT_LDS __attribute__((address_space(3)))
+
+// A load / store at a wave-uniform base plus a 32-bit byte offset per lane (one address register per lane instead of two).
+template <class T>
+__device__ __forceinline__ T ld_at(const void* base, uint32_t off)
+{
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+}
+template <class T>
+__device__ __forceinline__ void st_at(void* base, uint32_t off, T v)
+{
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v;
+}
+
+// s_waitcnt vmcnt(0) as the immediate of __builtin_amdgcn_s_waitcnt (gfx9 encoding: vmcnt in bits 15:14 and 3:0 = 0; expcnt, bits
+// 6:4, and lgkmcnt, bits 11:8, at their maxima 7 and 15 = not waited for)
+constexpr int WAIT_VMCNT_0 = 0x0F70;
 
 struct Float3v { float x, y, z; };   // three channels of a vertex colour: one 12-byte load
 
@@ -351,23 +371,17 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
     for (int k = 0; k < PPL; ++k) { best[k] = (unsigned long long)Z24_CLEAR << 32; cbest[k] = V2_CAP; }  // a tie with the cleared depth never wins
     bool lds_records = true;   // false once a second round has reused the slots (dense meshes): shading data comes from memory then
 
-    // side job: this workgroup's share of the buffers the launch clears (the backward pass's gradient accumulators)
-    if ((p.zero_b_bytes | p.zero_c_bytes) != 0) {
-        const unsigned gwg = blockIdx.y * gridDim.x + blockIdx.x;
-        if (p.zero_b_bytes) zero_share<THREADS>(p.zero_b, p.zero_b_bytes, p.zero_b_per, gwg, tid);
-        if (p.zero_c_bytes) zero_share<THREADS>(p.zero_c, p.zero_c_bytes, p.zero_c_per, gwg, tid);
-    }
     const uint32_t lds_rec = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_address(&s_rec[0]));
     const uint32_t lds_shade = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_address(&s_shade[0]));
 
-    FMARK();  // 1 cells requested, side job issued
+    FMARK();  // 1 cells requested
     for (int round = 0;; ++round) {
         if (tid == 0) s_count = 0;
         __syncthreads();
         FMARK();  // 2 (round 0)
         // ---- the candidates: every set bit claims a slot (a wave-wide prefix of the threads' bit counts, ONE LDS atomic per
         //      wave); bits beyond the round's capacity stay for the next round ----
-        {
+        if (64 * wave < p.nchunk) {   // (wave-uniform: a wave none of whose threads holds a cell -- at K3, waves 3-7 of eight -- has nothing to claim)
             const uint32_t cnt = (uint32_t)__popcll(m_bin) + (uint32_t)__popcll(m_big);
             uint32_t incl = cnt;   // inclusive prefix over the 64 lanes: DPP row shifts, then the rows' totals carried across
             incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111 /* row_shr:1 */, 0xF, 0xF, false);
@@ -488,92 +502,130 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
     // ---- shade ----
     // Per pixel: barycentrics of the winner (csrc/shaders.cpp:52-57,74) from its record in LDS -- or, for candidates of later
     // rounds, in memory --, the backward pass's state, the interpolated colours, the HWC pixel; background where nothing is
-    // visible.  (WAVES = 4 requests the background of all its pixels first and uses it last; the eight-wave shape has 64
-    // registers and twice the waves to hide a load behind: it fetches per pixel.  Bringing it in by LDS-DMA before the
-    // candidates instead was measured: K3 raster 20.7 against 18.3 us -- 16 MB of requests in front of the directory reads.)
-    constexpr bool BG_FIRST = WAVES != 8;
+    // visible.  Ordered so that a wave never waits for memory between its pixels: the background of every pixel that needs it
+    // is requested FIRST and used last, the winners' records are read as LDS (a pointer that may also point to memory makes
+    // them flat loads, each of which waits for LDS *and* memory -- i.e. for the previous pixel's stores to be acknowledged --
+    // and that is what the compiler makes of "LDS value, overwritten from memory where the slot was reused": the from-memory
+    // path is a branch of its own, behind a wave-uniform test), and nothing is loaded after the first store.
+    // (Bringing the background in by LDS-DMA before the candidates instead was measured: K3 raster 20.7 against 18.3 us -- 16 MB
+    // of requests in front of the directory reads.)
     const float* __restrict__ cols = COLOURS ? p.vertex_colors + (size_t)ib * p.V * C : nullptr;
     // (opaque copies of the lane's first pixel: the other pixels' coordinates are re-derived here, one add each, instead of
     // being kept -- at a register bound: spilled -- from the prologue through the coverage loop)
     int xs0 = x0, rs0 = r0;
     asm volatile("" : "+v"(xs0), "+v"(rs0));
-    auto pixel_index = [&](int k, bool& inside) {
+    // a pixel's index as a wave-uniform 64-bit base -- the tile's first row -- plus a 32-bit offset (at most 32 rows of the frame)
+    const size_t row_base = ((size_t)ib * p.H + tr0) * (size_t)p.W;
+    auto pixel_rel = [&](int k, bool& inside) {
         const int x = xs0 + 8 * (k % NB), r = rs0 + 8 * (k / NB);
         inside = x < p.W && r < p.H;
-        return ((size_t)ib * p.H + min(r, p.H - 1)) * p.W + min(x, p.W - 1);
+        return (uint32_t)((min(r, p.H - 1) - tr0) * p.W + min(x, p.W - 1));
     };
-    auto background_at = [&](size_t pix) {
-        const float* __restrict__ bg = p.background + pix * C;
-        if (CSPEC == 4) return *reinterpret_cast<const float4*>(bg);
-        else if (CSPEC == 3) return make_float4(bg[0], bg[1], bg[2], 0.f);
-        else return make_float4(bg[0], 0.f, 0.f, 0.f);
-    };
-    float4 bgv[BG_FIRST ? PPL : 1];
-    if constexpr (BG_FIRST) {
+    const float* __restrict__ bg_base = MODE == 0 ? p.background + row_base * C : nullptr;
+    float* __restrict__ out_base = MODE == 0 ? p.pixels + row_base * C : nullptr;
+    int32_t* __restrict__ vis_base = p.vis ? p.vis + row_base : nullptr;
+    float2* __restrict__ sa_base = p.state_a ? p.state_a + row_base : nullptr;
+    float2* __restrict__ sb_base = p.state_a ? p.state_b + row_base : nullptr;
+    float4 bgv[PPL];
 #pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-            bool inside;
-            const size_t pix = pixel_index(k, inside);
-            bgv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (MODE == 0 && inside && fbest[k] < 0) bgv[k] = background_at(pix);
+    for (int k = 0; k < PPL; ++k) {
+        bool inside;
+        const uint32_t rel = pixel_rel(k, inside);
+        bgv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MODE == 0 && inside && fbest[k] < 0) {
+            const uint32_t off = rel * (uint32_t)(C * sizeof(float));
+            if (CSPEC == 4) bgv[k] = ld_at<float4>(bg_base, off);
+            else if (CSPEC == 3) bgv[k] = make_float4(ld_at<float>(bg_base, off), ld_at<float>(bg_base, off + 4u), ld_at<float>(bg_base, off + 8u), 0.f);
+            else bgv[k] = make_float4(ld_at<float>(bg_base, off), 0.f, 0.f, 0.f);
         }
     }
+    // MEM (compile time): some winner of this wave's pixels is a candidate of a later round, whose slot was reused -- tiles of
+    // more than V2_CAP candidates --: such lanes take their record and colours from memory.  A copy of the pass of its own,
+    // chosen per wave, so that the common one has neither the loads nor the register copies that merge them in.
+    auto shade = [&](auto mem_tag) {
+    constexpr bool MEM = decltype(mem_tag)::value;
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
         const int32_t f = fbest[k];
         const bool has = f >= 0;
         const bool from_lds = has && lds_records && cbest[k] < V2_CAP;
         const int ci = from_lds ? cbest[k] : 0;   // (lanes without a winner read slot 0; what they compute is not used)
+        const DIRT_LDS Slot* sl = (const DIRT_LDS Slot*)&s_shade[ci];
         double cf[9];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) cf[i] = s_shade[ci].coef[i];
-        uint32_t flags = s_shade[ci].flags;
-        double inv_det = s_shade[ci].inv_det;
+        for (int i = 0; i < 9; ++i) cf[i] = sl->coef[i];
+        uint32_t flags = sl->flags;
+        double inv_det = sl->inv_det;
         const bool from_mem = has && !from_lds;
-        const bool any_from_mem = __builtin_amdgcn_ballot_w64(from_mem) != 0ull;   // (wave-uniform; rare: tiles of more than V2_CAP candidates)
-        if (any_from_mem && from_mem) {
-            const FaceRec* __restrict__ rec = recs + f;
+        if constexpr (MEM) {
+            if (from_mem) {
+                const FaceRec* __restrict__ rec = recs + f;
 #pragma unroll
-            for (int i = 0; i < 9; ++i) cf[i] = rec->coef[i];
-            flags = rec->flags; inv_det = rec->inv_det;
+                for (int i = 0; i < 9; ++i) cf[i] = rec->coef[i];
+                flags = rec->flags; inv_det = rec->inv_det;
+            }
         }
         double Fk[3];
         edge_eval(cf, (double)(xs0 + 8 * (k % NB)) + 0.5, (double)(p.H - 1 - (rs0 + 8 * (k / NB))) + 0.5, Fk);
         float b[3], cw;
         bary_eval(Fk, flags, inv_det, b, cw);
         const float b0 = b[0], b1 = b[1], b2 = b[2];
-        bool inside;
-        const size_t pix = pixel_index(k, inside);
-        if (!inside) continue;
-        // the backward pass's state and the visibility export
-        if (p.vis) p.vis[pix] = f;
-        if (p.state_a) store_state(p, pix, has, b0, b1, b2, cw, f);
-        if (MODE != 0) continue;
-        float4 u0 = make_float4(0.f, 0.f, 0.f, 0.f), u1 = u0, u2 = u0;
-        if constexpr (COLOURS) { u0 = s_shade[ci].col[0]; u1 = s_shade[ci].col[1]; u2 = s_shade[ci].col[2]; }
-        if (any_from_mem && from_mem) {
-            if constexpr (COLOURS) {
-                const FaceRec* __restrict__ rec = recs + f;
-                const float* __restrict__ c0 = cols + (size_t)rec->vid[0] * C;
-                const float* __restrict__ c1 = cols + (size_t)rec->vid[1] * C;
-                const float* __restrict__ c2 = cols + (size_t)rec->vid[2] * C;
-                if (CSPEC == 4) { u0 = *reinterpret_cast<const float4*>(c0); u1 = *reinterpret_cast<const float4*>(c1); u2 = *reinterpret_cast<const float4*>(c2); }
-                else if (CSPEC == 3) { u0 = make_float4(c0[0], c0[1], c0[2], 0.f); u1 = make_float4(c1[0], c1[1], c1[2], 0.f); u2 = make_float4(c2[0], c2[1], c2[2], 0.f); }
-                else { u0 = make_float4(c0[0], 0.f, 0.f, 0.f); u1 = make_float4(c1[0], 0.f, 0.f, 0.f); u2 = make_float4(c2[0], 0.f, 0.f, 0.f); }
+        // the winner's colours, once its coefficients are done with (registers)
+        float u[3][4] = {};
+        if constexpr (COLOURS) {
+            const DIRT_LDS float* cl = (const DIRT_LDS float*)&s_shade[ci].col[0];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) u[i / 4][i % 4] = cl[i];
+            if constexpr (MEM) {
+                if (from_mem) {
+                    const FaceRec* __restrict__ rec = recs + f;
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const float* __restrict__ cv = cols + (size_t)rec->vid[v] * C;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) u[v][c] = cv[c];
+                    }
+                }
             }
         }
-        float* __restrict__ out = p.pixels + pix * C;
-        float4 o;   // pixels start as the background: csrc/rasterise_egl.cpp:348-356
-        if constexpr (BG_FIRST) o = bgv[k];
-        else o = has ? make_float4(0.f, 0.f, 0.f, 0.f) : background_at(pix);
-        if (has) {
-            o.x = fmaf(b2, u2.x, fmaf(b1, u1.x, b0 * u0.x));
-            if (CSPEC >= 3) { o.y = fmaf(b2, u2.y, fmaf(b1, u1.y, b0 * u0.y)); o.z = fmaf(b2, u2.z, fmaf(b1, u1.z, b0 * u0.z)); }
-            if (CSPEC == 4) o.w = fmaf(b2, u2.w, fmaf(b1, u1.w, b0 * u0.w));
+        // (the background requests, all of them, are waited for HERE, before the first store and on every path: the stores
+        // below are behind branches, and a wait for a load that was issued before a store that may or may not have been issued
+        // can only be a wait for everything -- the previous pixel's stores included)
+        // Not needed for correctness -- the compiler waits for every load before its use --, and written with the builtin, not as
+        // the asm statements above: the compiler's own placement of waits reads an s_waitcnt instruction, not an asm string, and
+        // it is the compiler that must know nothing is outstanding.
+        if (MODE == 0 && k == 0) __builtin_amdgcn_s_waitcnt(WAIT_VMCNT_0);
+        float4 o = bgv[k];   // pixels start as the background: csrc/rasterise_egl.cpp:348-356
+        if (MODE == 0 && has) {
+            o.x = fmaf(b2, u[2][0], fmaf(b1, u[1][0], b0 * u[0][0]));
+            if (CSPEC >= 3) { o.y = fmaf(b2, u[2][1], fmaf(b1, u[1][1], b0 * u[0][1])); o.z = fmaf(b2, u[2][2], fmaf(b1, u[1][2], b0 * u[0][2])); }
+            if (CSPEC == 4) o.w = fmaf(b2, u[2][3], fmaf(b1, u[1][3], b0 * u[0][3]));
         }
-        if (CSPEC == 4) *reinterpret_cast<float4*>(out) = o;
-        else if (CSPEC == 3) { out[0] = o.x; out[1] = o.y; out[2] = o.z; }
-        else out[0] = o.x;
+        bool inside;
+        const uint32_t rel = pixel_rel(k, inside);
+        if (!inside) continue;
+        // the backward pass's state and the visibility export
+        if (p.vis) st_at<int32_t>(vis_base, rel * 4u, f);
+        if (p.state_a) store_state(sa_base, sb_base, rel * 8u, has, b0, b1, b2, cw, f);
+        if (MODE != 0) continue;
+        const uint32_t off = rel * (uint32_t)(C * sizeof(float));
+        if (CSPEC == 4) st_at<float4>(out_base, off, o);
+        else if (CSPEC == 3) { st_at<float>(out_base, off, o.x); st_at<float>(out_base, off + 4u, o.y); st_at<float>(out_base, off + 8u, o.z); }
+        else st_at<float>(out_base, off, o.x);
+    }
+    };
+    bool some_from_mem = false;
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) some_from_mem |= fbest[k] >= 0 && !(lds_records && cbest[k] < V2_CAP);
+    if (__builtin_amdgcn_ballot_w64(some_from_mem) != 0ull) shade(std::true_type());   // (wave-uniform)
+    else shade(std::false_type());
+    // side job: this workgroup's share of the buffers the launch clears (the backward pass's gradient accumulators) -- LAST:
+    // nothing in this launch reads them, and at the head of the kernel the stores sat in front of the waits the prologue counts by
+    // hand (measured: the step at 20 steps 48.4-49.6 there, 48.4-48.9 here; after the shading requests: scratch, not run)
+    if ((p.zero_b_bytes | p.zero_c_bytes) != 0) {
+        const unsigned gwg = blockIdx.y * gridDim.x + blockIdx.x;
+        if (p.zero_b_bytes) zero_share<THREADS>(p.zero_b, p.zero_b_bytes, p.zero_b_per, gwg, tid);
+        if (p.zero_c_bytes) zero_share<THREADS>(p.zero_c, p.zero_c_bytes, p.zero_c_per, gwg, tid);
     }
     FMARK();  // 9 shaded, stores issued
 #ifdef DIRT_TRACE

@@ -229,10 +229,15 @@ __device__ __forceinline__ void raster_candidate_pair(const TileRec& t0, const T
 // The backward pass's state of one pixel -- csrc/shaders.cpp:64-77: {clip_w, face} and two of the three barycentrics
 // (encode_bary, dirt_device.h; the face index stands for the index triple) -- or the clear values of
 // csrc/rasterise_grad_egl.cpp:442-445.
+// (plane_a, plane_b: wave-uniform bases; off: the pixel's byte offset in either plane, 8 bytes per pixel)
+__device__ __forceinline__ void store_state(float2* plane_a, float2* plane_b, uint32_t off, bool has, float b0, float b1, float b2, float clip_w, int32_t face)
+{
+    *reinterpret_cast<float2*>(reinterpret_cast<char*>(plane_a) + off) = make_float2(has ? clip_w : INFINITY, __int_as_float(face));
+    *reinterpret_cast<float2*>(reinterpret_cast<char*>(plane_b) + off) = has ? encode_bary(b0, b1, b2) : make_float2(-1.f, -1.f);
+}
 __device__ __forceinline__ void store_state(const RasterParams& p, size_t pix, bool has, float b0, float b1, float b2, float clip_w, int32_t face)
 {
-    p.state_a[pix] = make_float2(has ? clip_w : INFINITY, __int_as_float(face));
-    p.state_b[pix] = has ? encode_bary(b0, b1, b2) : make_float2(-1.f, -1.f);
+    store_state(p.state_a + pix, p.state_b + pix, 0u, has, b0, b1, b2, clip_w, face);
 }
 
 // One workgroup's share of a buffer to clear: `per` 16-byte units (the buffers are 16-byte aligned: [B,V,4] floats, the

@@ -46,4 +46,22 @@ report(bs, 6, ['requests issued', 'indices / vertices there (+ second trip)', 'e
                'coverage records + directory stores'], 'setup_kernel_v2 (wave 0 of each chunk)')
 a = report(br, 10, ['cells requested, side job', 'barrier', 'wait cells, claim slots, list', 'barrier', 'coverage records: DMA + wait', 'barrier',
                     'shade DMA issue + coverage loop', 'wait shade data + barrier', 'shade + stores'], 'raster_kernel_v2')
-print('  candidates visited per wave: mean %.1f max %d' % (a[:, 15].mean(), a[:, 15].max()))
+print('  candidates visited per wave: mean %.1f max %d; waves that visited none: %d of %d' % (a[:, 15].mean(), a[:, 15].max(), (a[:, 15] == 0).sum(), len(a)))
+
+
+def critical(a, title, sel):
+    """The split of the waves `sel` picks (the last-finishing one; the mean of the last-finishing 1 %): prologue (to mark 6),
+    coverage loop (to 7), wait for the shading data + barrier (to 8), shading (to 9); wall-clock start and end."""
+    tt = a[:, :10].astype(np.float64)
+    w0 = a[:, 12].astype(np.float64); t0 = w0.min()
+    en = (w0 + a[:, 13] - t0) / 100.0
+    clk = (tt[:, 9] - tt[:, 0]).sum() / (a[:, 13].astype(np.float64) / 100.0).sum()
+    i = sel(en)
+    ph = np.stack([tt[i, 6] - tt[i, 0], tt[i, 7] - tt[i, 6], tt[i, 8] - tt[i, 7], tt[i, 9] - tt[i, 8]], -1).reshape(-1, 4).mean(0)
+    print('  %s: start %.2f us, end %.2f us; prologue %.0f clocks = %.2f us, coverage loop %.0f = %.2f, wait + barrier %.0f = %.2f, shading %.0f = %.2f; candidates %.1f' % (
+        title, ((w0 - t0) / 100.0)[i].mean(), en[i].mean(), ph[0], ph[0] / clk, ph[1], ph[1] / clk, ph[2], ph[2] / clk, ph[3], ph[3] / clk, a[i, 15].mean()))
+
+
+critical(a, 'critical (last-finishing) wave', lambda en: np.argmax(en))
+critical(a, 'mean of the last-finishing 1 % of waves', lambda en: np.argsort(en)[-max(1, len(en) // 100):])
+critical(a, 'mean of all waves', lambda en: np.arange(len(en)))
