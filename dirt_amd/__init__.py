@@ -5,4 +5,6 @@ from . import rasterise_ops  # noqa: F401
 from . import matrices, lighting, projection  # noqa: F401  (dirt.matrices, dirt.lighting, dirt.projection)
 from . import texture  # noqa: F401  (the texture helpers of samples/textured.py)
 from . import shading  # noqa: F401  (the fused G-buffer lighting of samples/deferred.py's shader)
+from . import geometry  # noqa: F401  (the fused vertex stage in front of the rasteriser: transforms and vertex normals)
+from .geometry import MeshTopology, vertex_stage  # noqa: F401
 from .graphed import GraphedStep, backward  # noqa: F401  (a training step captured once as a HIP graph: the remedy for eager autograd's host cost)

@@ -34,6 +34,9 @@ SHADE_PARAM_HEAD, SHADE_PARAM_LIGHT = 9, 8   # floats of the parameter block: am
 SHADE_KINDS = {'diffuse_directional': 0, 'specular_directional': 1, 'diffuse_point': 2}
 SHADE_CLAMP = 1
 SHADE_HAS_CAMERA = 2
+GEOM_PRE_SPLIT = 1
+GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
+GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
 
 E_INVALID_ARGUMENT = -1
 E_TOO_MANY_VERTICES = -2
@@ -49,7 +52,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_profile_read', 'dirt_profile_reset', 'dirt_texture_sample_forward', 'dirt_texture_sample_backward',
            'dirt_texture_sample_backward_image', 'dirt_texture_last_error', 'dirt_texture_mip_levels', 'dirt_texture_mip_build',
            'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
-           'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward')
+           'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward',
+           'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -122,6 +126,13 @@ def load():
         lib.dirt_shade_forward.restype = i
         lib.dirt_shade_backward.argtypes = [fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
         lib.dirt_shade_backward.restype = i
+    if hasattr(lib, 'dirt_geometry_forward') or not override:   # fused vertex stage (ABI 4, additive)
+        lib.dirt_geometry_scratch_bytes.argtypes = [ll, ll, ll]
+        lib.dirt_geometry_scratch_bytes.restype = sz
+        lib.dirt_geometry_forward.argtypes = [fp, i, ip, ip, ip, fp, i, fp, i, fp, fp, fp, ll, ll, ll, u, vp]
+        lib.dirt_geometry_forward.restype = i
+        lib.dirt_geometry_backward.argtypes = [fp, i, ip, ip, ip, fp, i, fp, i, fp, fp, fp, fp, fp, fp, vp, sz, ll, ll, ll, u, vp]
+        lib.dirt_geometry_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

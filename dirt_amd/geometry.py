@@ -1,0 +1,190 @@
+"""The vertex stage in front of the rasteriser, fused: object-space vertices -> clip-space vertices, world positions and
+world normals (what every sample of the reference computes with two matrix products and `lighting.vertex_normals`:
+samples/deferred.py:40-51, samples/simple.py:45-56, samples/textured.py:97-108) as one HIP kernel forward and two or
+three backward (dirt_geometry.hip; specification in DESIGN.md §7c).
+
+    topology = MeshTopology(faces, num_vertices)          # once per mesh: the inverted index the kernels walk
+    for it in range(n):
+        clip, world, normals = vertex_stage(vertices, topology, model, view_projection)
+        pixels = dirt_amd.rasterise_deferred(vertices=clip, faces=topology.faces, ...)
+
+The scatter of `lighting.vertex_normals` (three `index_add`s, float atomics on a GPU) is a gather over the topology's
+inverted index here: no atomics, one launch, and the same bits on every run.
+"""
+import torch
+
+from . import _lib
+from . import rasterise_ops as _ops
+
+_WANT = ('clip', 'world', 'normals')
+# Lists of more than this many entries are summed by a whole wave instead of their vertex's lane; None: the library's
+# default (_lib.GEOM_LONG_LIST_DEFAULT, chosen by measurement: DESIGN.md §7c).  For measurements (tools/bench_geometry.py).
+LONG_LIST = None
+
+
+class MeshTopology:
+    """The faces of a mesh and their inverted index, built once (topology is constant across a fitting loop).
+
+    faces: int32 / int64 [F, 3] on any device; num_vertices: V.  Indices outside [0, V), another shape or dtype raise
+    ValueError (this reads one value back from the device; `vertex_stage` never does).
+    Attributes, all int32 on the device of `faces`:
+        faces [F, 3]; offsets [V + 1]; entries [3 F]: the entries of vertex v are entries[offsets[v]:offsets[v + 1]], each
+        3 * face + corner, ordered by face, then corner.  A vertex no face names has an empty list; a face that names a
+        vertex twice contributes two entries.
+    """
+
+    def __init__(self, faces, num_vertices):
+        if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+            raise ValueError('MeshTopology expects faces [F, 3], got %s' % (tuple(getattr(faces, 'shape', ())),))
+        if faces.dtype not in (torch.int32, torch.int64):
+            raise ValueError('MeshTopology expects int32 or int64 faces, got %s' % faces.dtype)   # dirt/lighting.py:15-17
+        if isinstance(num_vertices, bool) or not isinstance(num_vertices, int) or num_vertices < 0:
+            raise ValueError('MeshTopology expects num_vertices >= 0, got %r' % (num_vertices,))
+        if num_vertices > _lib.GEOM_MAX_VERTICES or faces.shape[0] > _lib.GEOM_MAX_FACES:
+            raise ValueError('MeshTopology: at most %d vertices and %d faces' % (_lib.GEOM_MAX_VERTICES, _lib.GEOM_MAX_FACES))
+        flat = faces.reshape(-1).long()   # position 3 * face + corner
+        if flat.numel():
+            lo, hi = (int(x) for x in torch.stack([flat.min(), flat.max()]).cpu())
+            if lo < 0 or hi >= num_vertices:
+                raise ValueError('MeshTopology: faces name vertices %d..%d, outside [0, %d)' % (lo, hi, num_vertices))
+        # a stable sort of the positions by vertex keeps them in order of face, then corner
+        entries = torch.argsort(flat, stable=True).to(torch.int32)
+        counts = torch.bincount(flat, minlength=num_vertices)
+        offsets = torch.zeros(num_vertices + 1, dtype=torch.int64, device=faces.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        self.num_vertices, self.num_faces = num_vertices, int(faces.shape[0])
+        self.faces, self.offsets, self.entries = faces.to(torch.int32).contiguous(), offsets.to(torch.int32), entries.contiguous()
+
+    @property
+    def device(self):
+        return self.faces.device
+
+    def to(self, device):
+        """The same topology with its three tensors on `device` (nothing is rebuilt or checked again)."""
+        other = object.__new__(MeshTopology)
+        other.num_vertices, other.num_faces = self.num_vertices, self.num_faces
+        other.faces, other.offsets, other.entries = (t.to(device) for t in (self.faces, self.offsets, self.entries))
+        return other
+
+
+class _VertexStage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertices, model, view_projection, topology, meta):
+        lib = _lib.load()
+        B, V, C, batched, want, flags = meta
+        dev = vertices.device
+        lead = (B, V) if batched else (V,)
+        clip, world, normals = (torch.empty(lead + (w,), dtype=torch.float32, device=dev) if name in want else None
+                                for name, w in (('clip', 4), ('world', 4), ('normals', 3)))
+        if B * V:
+            with _ops._on_device(dev):
+                rc = lib.dirt_geometry_forward(vertices.data_ptr(), C, *_index_pointers(topology), *_matrix_arguments(model, view_projection),
+                                               *(t.data_ptr() if t is not None else None for t in (clip, world, normals)),
+                                               B, V, topology.num_faces, flags, _ops._stream_handle(dev))
+            _lib.check(rc)
+        ctx.save_for_backward(vertices, model, view_projection)
+        ctx.topology, ctx.meta = topology, meta
+        return clip, world, normals
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_clip, grad_world, grad_normals):
+        lib = _lib.load()
+        vertices, model, view_projection = ctx.saved_tensors
+        topology = ctx.topology
+        B, V, C, batched, want, flags = ctx.meta
+        dev = vertices.device
+        want_v, want_m, want_p = ctx.needs_input_grad[:3]
+        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
+        grad_v = torch.empty_like(vertices) if want_v else None
+        grad_m = torch.empty_like(model) if want_m else None
+        grad_p = torch.empty_like(view_projection) if want_p else None
+        if not B * V:
+            return grad_v, grad_m.zero_() if want_m else None, grad_p.zero_() if want_p else None, None, None
+        grads = [g.to(torch.float32).contiguous() if g is not None else None for g in (grad_clip, grad_world, grad_normals)]
+        nbytes = lib.dirt_geometry_scratch_bytes(B, V, topology.num_faces)
+        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        with _ops._on_device(dev):
+            rc = lib.dirt_geometry_backward(vertices.data_ptr(), C, *_index_pointers(topology), *_matrix_arguments(model, view_projection),
+                                            *(g.data_ptr() if g is not None else None for g in grads),
+                                            *(g.data_ptr() if g is not None else None for g in (grad_v, grad_m, grad_p)),
+                                            scratch.data_ptr(), nbytes, B, V, topology.num_faces, flags, _ops._stream_handle(dev))
+        _lib.check(rc)
+        return grad_v, grad_m, grad_p, None, None
+
+
+def _index_pointers(topology):
+    # (an empty tensor's data_ptr() is 0: NULL, which the library accepts for a mesh without faces)
+    return tuple(t.data_ptr() or None for t in (topology.faces, topology.offsets, topology.entries))
+
+
+def _matrix_arguments(model, view_projection):
+    """(pointer, scene count) of each matrix as the C ABI takes them: ([4, 4] -> 1, [B, 4, 4] -> B, None -> NULL, 0)"""
+    out = []
+    for m in (model, view_projection):
+        out += [m.data_ptr(), 1 if m.dim() == 2 else int(m.shape[0])] if m is not None else [None, 0]
+    return out
+
+
+def _check_arguments(vertices, topology, model, view_projection, pre_split, want):
+    """Everything `vertex_stage` refuses with a ValueError, from shapes, dtypes and devices alone (no device work): ->
+    (B, V, C, batched, the wanted outputs in canonical order, flags)"""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() not in (2, 3) or vertices.shape[-1] not in (3, 4):
+        raise ValueError('vertex_stage expects vertices [V, 3|4] or [B, V, 3|4], got %s' % (tuple(getattr(vertices, 'shape', ())),))
+    if vertices.dtype != torch.float32:
+        raise ValueError('vertex_stage expects float32 vertices, got %s' % vertices.dtype)
+    if not isinstance(topology, MeshTopology):
+        raise ValueError('vertex_stage expects a MeshTopology (build it once per mesh), got %r' % type(topology).__name__)
+    batched = vertices.dim() == 3
+    B, V, C = (int(vertices.shape[0]) if batched else 1), int(vertices.shape[-2]), int(vertices.shape[-1])
+    if V != topology.num_vertices:
+        raise ValueError('vertex_stage: %d vertices, the topology was built for %d' % (V, topology.num_vertices))
+    if B > 65535:
+        raise ValueError('vertex_stage: %d scenes, at most 65535' % B)
+    if topology.device != vertices.device:
+        raise ValueError('vertex_stage: the topology is on %s, the vertices on %s (use topology.to(device))' % (topology.device, vertices.device))
+    for name, m in (('model', model), ('view_projection', view_projection)):
+        if m is None:
+            continue
+        shapes = [(4, 4), (B, 4, 4)] if batched else [(4, 4)]
+        if not isinstance(m, torch.Tensor) or tuple(m.shape) not in shapes:
+            raise ValueError('%s must have shape %s, got %s' % (name, ' or '.join(str(list(s)) for s in shapes), tuple(getattr(m, 'shape', ()))))
+        if m.dtype != torch.float32:
+            raise ValueError('%s must be float32, got %s' % (name, m.dtype))
+        if m.device != vertices.device:
+            raise ValueError('%s is on %s, the vertices on %s' % (name, m.device, vertices.device))
+    if isinstance(want, str) or any(w not in _WANT for w in want):
+        raise ValueError('want must be a sequence of %s, got %r' % (_WANT, want))
+    want = tuple(w for w in _WANT if w in want)
+    if 'clip' in want and view_projection is None:
+        want = tuple(w for w in want if w != 'clip')   # clip is None without a view_projection
+    long_list = (int(LONG_LIST) << _lib.GEOM_LONG_LIST_SHIFT) & _lib.GEOM_LONG_LIST_MASK if LONG_LIST else 0
+    return B, V, C, batched, want, (_lib.GEOM_PRE_SPLIT if pre_split else 0) | long_list
+
+
+def vertex_stage(vertices, topology, model=None, view_projection=None, *, pre_split=False, want=_WANT):
+    """Transforms and vertex normals in one kernel (samples/deferred.py:40-51), differentiably.  -> (clip, world, normals)
+
+    vertices: float32 [V, 3|4] or [B, V, 3|4] on the GPU; with three components w = 1 is appended.
+    topology: the mesh's `MeshTopology`, on the same device.
+    model, view_projection: [4, 4], or [B, 4, 4] with batched vertices, in the row-vector convention of
+        `dirt_amd.matrices` (v @ M); GPU tensors, differentiable, never read on the host.
+    world4 = v4 @ model (v4 itself without a model); clip = world4 @ view_projection (None without one);
+    normals = lighting.vertex_normals(world4, faces), or lighting.vertex_normals_pre_split(world4, faces) with
+    pre_split=True, the reference's two 1e-12s included (dirt/lighting.py:21-28,31-89,97-129).
+    Returns clip [.., V, 4], world [.., V, 4], normals [.., V, 3]; outputs not named in `want` are None and are neither
+    computed nor written.  Values are this float32 composition; gradients (to all components of the vertices and to both
+    matrices) are those of torch's autograd for it: the norm of a zero vector has gradient 0, so a zero-area face passes
+    d n / 1e-12 to its cross product and nothing through the norm.  Nothing in a call synchronises with the host."""
+    meta = _check_arguments(vertices, topology, model, view_projection, pre_split, want)
+    if not vertices.is_cuda:
+        raise RuntimeError('dirt_amd.geometry.vertex_stage runs on an MI355X only; there is no CPU fallback')
+    v = vertices.contiguous()
+    model, view_projection = (m.contiguous() if m is not None else None for m in (model, view_projection))
+    return _VertexStage.apply(v, model, view_projection, topology, meta)
+
+
+def vertex_normals(vertices, topology, pre_split=False):
+    """`lighting.vertex_normals(vertices, faces)` (or `vertex_normals_pre_split` with pre_split=True) alone, in one kernel:
+    [.., V, 3|4] -> [.., V, 3] (dirt/lighting.py:31-89,97-129)."""
+    return vertex_stage(vertices, topology, pre_split=pre_split, want=('normals',))[2]

@@ -313,6 +313,50 @@ int dirt_shade_backward(const float *gbuffer, const float *params, const float *
                         void *stream);
 
 /*
+ * The vertex stage in front of the rasteriser, fused.  Replaces the torch composition of the reference's samples
+ * (samples/deferred.py:40-51): world4 = v4 @ model, clip = world4 @ view_projection (row vectors), and the vertex normals
+ * of dirt/lighting.py:21-28,31-89 (`vertex_normals`) or, with DIRT_GEOM_PRE_SPLIT, of dirt/lighting.py:97-129
+ * (`vertex_normals_pre_split`), taken from the first three components of world4; specification in
+ * dirt_amd/csrc/dirt_geometry.hip and DESIGN.md §7c.
+ *   vertices [B, V, components], components = 3 (w = 1 is appended) or 4, 4-byte alignment suffices.
+ *   faces [F, 3]: one topology for every scene.  offsets [V + 1], entries [3 F]: its inverted index -- the entries of
+ *   vertex v are entries[offsets[v] .. offsets[v + 1]), each 3 * face + corner, ordered by face, then corner (a face that
+ *   names a vertex twice has two entries; a vertex no face names has none).  The kernels trust the three arrays: every
+ *   index must lie inside [0, V) / [0, 3 F) (dirt_amd.geometry.MeshTopology builds and checks them).
+ *   model, view_projection [scenes, 4, 4] row-major with scenes = 1 (shared) or B; scenes = 0 and NULL: absent (model:
+ *   the identity; view_projection: there is no clip output).
+ *   clip [B, V, 4], world [B, V, 4], normals [B, V, 3]: each may be NULL and is then neither computed nor written.
+ *   flags: DIRT_GEOM_PRE_SPLIT; DIRT_GEOM_LONG_LIST(n): lists of more than n entries are summed by a whole wave
+ *   instead of one lane (0: DIRT_GEOM_LONG_LIST_DEFAULT).
+ * One launch, no atomics.  B or V equal to 0: success, nothing is launched; F = 0 is a mesh without faces (zero normals).
+ * Backward (the gradient of the above, dirt/lighting.py:21-28,31-89,97-129 and samples/deferred.py:40-51 under torch's
+ * autograd: the norm of a zero vector has gradient 0): grad_clip / grad_world / grad_normals, each may be NULL (zero),
+ * -> grad_vertices [B, V, components], grad_model and grad_view_projection (shaped like the matrices); each may be NULL
+ * and is then not computed; those given are fully written.  `scratch` is caller-owned, of
+ * dirt_geometry_scratch_bytes(B, V, F) bytes (0: invalid sizes): d loss / d (un-normalised normal sum) per vertex and
+ * one row of partial matrix sums per workgroup, added by a last launch in a fixed order.  At most 2 launches, + 1 when
+ * a matrix gradient is wanted; no atomics, the same bits on every run.  Failures: dirt_last_error().
+ */
+#define DIRT_GEOM_PRE_SPLIT 1u              /* dirt/lighting.py:97-129 instead of dirt/lighting.py:31-89 */
+#define DIRT_GEOM_LONG_LIST_SHIFT 8
+#define DIRT_GEOM_LONG_LIST_MASK 0xffff00u
+#define DIRT_GEOM_LONG_LIST(n) (((unsigned)(n) << DIRT_GEOM_LONG_LIST_SHIFT) & DIRT_GEOM_LONG_LIST_MASK)
+#define DIRT_GEOM_LONG_LIST_DEFAULT 64
+#define DIRT_GEOM_MAX_VERTICES (1 << 28)
+#define DIRT_GEOM_MAX_FACES (1 << 29)
+size_t dirt_geometry_scratch_bytes(long long B, long long V, long long F);
+int dirt_geometry_forward(const float *vertices, int components, const int32_t *faces, const int32_t *offsets,
+                          const int32_t *entries, const float *model, int model_scenes, const float *view_projection,
+                          int view_projection_scenes, float *clip, float *world, float *normals, long long B, long long V,
+                          long long F, unsigned flags, void *stream);
+int dirt_geometry_backward(const float *vertices, int components, const int32_t *faces, const int32_t *offsets,
+                           const int32_t *entries, const float *model, int model_scenes, const float *view_projection,
+                           int view_projection_scenes, const float *grad_clip, const float *grad_world,
+                           const float *grad_normals, float *grad_vertices, float *grad_model, float *grad_view_projection,
+                           void *scratch, size_t scratch_bytes, long long B, long long V, long long F, unsigned flags,
+                           void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
