@@ -16,6 +16,21 @@
 
 namespace dirt {
 
+// Loads / stores at a 32-bit byte offset from a wave-uniform base: the address stays "scalar base + vector offset"
+// (one VGPR per address instead of two, no 64-bit vector arithmetic).
+template <class T>
+__device__ __forceinline__ T ld_off(const void* base, uint32_t off)
+{
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+}
+template <class T>
+__device__ __forceinline__ void st_off(void* base, uint32_t off, T v)
+{
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v;
+}
+
+struct Float3 { float x, y, z; };   // three channels of a pixel or of a vertex colour: one 12-byte load / store (4-byte aligned)
+
 // One set-up triangle, 128 bytes, 128-byte aligned so a record is one L2 line and can be fetched
 // with two wide scalar loads.  The first 100 bytes are what the coverage / depth loop needs.
 //
@@ -262,6 +277,14 @@ __device__ __forceinline__ int xcd_tile(int b, int ntiles)
 // instructions of a division by a run-time value at the head of every wave.
 // (tiles_x == 1 has no 32-bit magic number -- 2^32 + 1 -- and is marked by 0: the row is the tile index itself.)
 inline uint32_t tile_magic(int tiles_x) { return tiles_x <= 1 ? 0u : (uint32_t)(0x100000000ull / (uint32_t)tiles_x) + 1u; }
+// The tile grid of a launch (RasterParams, GradParams): tile_w x tile_h pixels per workgroup.
+template <class Params>
+inline void set_tile_grid(Params& p, int tile_w, int tile_h)
+{
+    p.tiles_x = (p.W + tile_w - 1) / tile_w;
+    p.tiles_y = (p.H + tile_h - 1) / tile_h;
+    p.tiles_x_magic = tile_magic(p.tiles_x);
+}
 __device__ __forceinline__ void tile_xy(int tile, int tiles_x, uint32_t magic, int& tx, int& ty)
 {
     ty = magic ? (int)__umulhi((uint32_t)tile, magic) : tile;

@@ -66,23 +66,9 @@ __device__ __forceinline__ void glds16(const void* base, uint32_t voff, uint32_t
 // An object in LDS, said so in its type: what is read through such a pointer is a ds_read whatever the optimiser merges.
 #define DIRT_LDS __attribute__((address_space(3)))
 
-// A load / store at a wave-uniform base plus a 32-bit byte offset per lane (one address register per lane instead of two).
-template <class T>
-__device__ __forceinline__ T ld_at(const void* base, uint32_t off)
-{
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
-}
-template <class T>
-__device__ __forceinline__ void st_at(void* base, uint32_t off, T v)
-{
-    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v;
-}
-
 // s_waitcnt vmcnt(0) as the immediate of __builtin_amdgcn_s_waitcnt (gfx9 encoding: vmcnt in bits 15:14 and 3:0 = 0; expcnt, bits
 // 6:4, and lgkmcnt, bits 11:8, at their maxima 7 and 15 = not waited for)
 constexpr int WAIT_VMCNT_0 = 0x0F70;
-
-struct Float3v { float x, y, z; };   // three channels of a vertex colour: one 12-byte load
 
 template <class T>
 __device__ __forceinline__ uint32_t lds_address(T* p)
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(STHREADS) void setup_kernel_v2(const float* __restr
         else {
             const float* __restrict__ cp = cols + (size_t)vid * CK;
             if constexpr (CK == 4) return *reinterpret_cast<const float4*>(cp);
-            else if constexpr (CK == 3) { const Float3v q = *reinterpret_cast<const Float3v*>(cp); return make_float4(q.x, q.y, q.z, 0.f); }
+            else if constexpr (CK == 3) { const Float3 q = *reinterpret_cast<const Float3*>(cp); return make_float4(q.x, q.y, q.z, 0.f); }
             else return make_float4(cp[0], 0.f, 0.f, 0.f);
         }
     };
@@ -534,9 +520,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
         bgv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (MODE == 0 && inside && fbest[k] < 0) {
             const uint32_t off = rel * (uint32_t)(C * sizeof(float));
-            if (CSPEC == 4) bgv[k] = ld_at<float4>(bg_base, off);
-            else if (CSPEC == 3) bgv[k] = make_float4(ld_at<float>(bg_base, off), ld_at<float>(bg_base, off + 4u), ld_at<float>(bg_base, off + 8u), 0.f);
-            else bgv[k] = make_float4(ld_at<float>(bg_base, off), 0.f, 0.f, 0.f);
+            if (CSPEC == 4) bgv[k] = ld_off<float4>(bg_base, off);
+            else if (CSPEC == 3) bgv[k] = make_float4(ld_off<float>(bg_base, off), ld_off<float>(bg_base, off + 4u), ld_off<float>(bg_base, off + 8u), 0.f);
+            else bgv[k] = make_float4(ld_off<float>(bg_base, off), 0.f, 0.f, 0.f);
         }
     }
     // MEM (compile time): some winner of this wave's pixels is a candidate of a later round, whose slot was reused -- tiles of
@@ -605,13 +591,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
         const uint32_t rel = pixel_rel(k, inside);
         if (!inside) continue;
         // the backward pass's state and the visibility export
-        if (p.vis) st_at<int32_t>(vis_base, rel * 4u, f);
+        if (p.vis) st_off<int32_t>(vis_base, rel * 4u, f);
         if (p.state_a) store_state(sa_base, sb_base, rel * 8u, has, b0, b1, b2, cw, f);
         if (MODE != 0) continue;
         const uint32_t off = rel * (uint32_t)(C * sizeof(float));
-        if (CSPEC == 4) st_at<float4>(out_base, off, o);
-        else if (CSPEC == 3) { st_at<float>(out_base, off, o.x); st_at<float>(out_base, off + 4u, o.y); st_at<float>(out_base, off + 8u, o.z); }
-        else st_at<float>(out_base, off, o.x);
+        if (CSPEC == 4) st_off<float4>(out_base, off, o);
+        else if (CSPEC == 3) { st_off<float>(out_base, off, o.x); st_off<float>(out_base, off + 4u, o.y); st_off<float>(out_base, off + 8u, o.z); }
+        else st_off<float>(out_base, off, o.x);
     }
     };
     bool some_from_mem = false;
@@ -664,9 +650,7 @@ bool raster_v2_applies(const RasterParams& p, int B, bool visibility_only)
 hipError_t launch_raster_v2(const RasterParams& p_in, int B, bool visibility_only, hipStream_t stream)
 {
     RasterParams p = p_in;
-    p.tiles_x = (p.W + 31) / 32;
-    p.tiles_y = (p.H + 31) / 32;
-    p.tiles_x_magic = tile_magic(p.tiles_x);
+    set_tile_grid(p, 32, 32);
     const dim3 grid((unsigned)(p.tiles_x * p.tiles_y), (unsigned)B);
     {
         const size_t nwg = (size_t)grid.x * grid.y;

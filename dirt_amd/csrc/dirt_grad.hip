@@ -36,22 +36,7 @@
 
 namespace dirt {
 
-// Preprocessor switch: DIRT_TRACE, per-wave phase timestamps (s_memtime) for tools/trace_grad.py.  Only the tracing build of
-// the library defines it (tools/build_tools.sh); the product library (dirt_amd/build.py) never does.
-#ifdef DIRT_TRACE
-__device__ long long* g_trace_grad = nullptr;
-extern "C" void dirt_debug_set_trace_grad(void* p)
-{
-    long long* q = reinterpret_cast<long long*>(p);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_trace_grad), &q, sizeof(q));
-}
-#define GMARK() do { if (tr_n < 12) { long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); tr_t[tr_n++] = t_; } } while (0)
-#define GCOUNT(i, v) do { tr_c[i] += (v); } while (0)
-#else
-#define GMARK() do {} while (0)
-#define GCOUNT(i, v) do {} while (0)
-#endif
-
+GRAD_TRACE_BUFFER()
 
 constexpr int GT = 32;                  // tile side (pixels)
 constexpr int GTHREADS = 256;           // 4 waves: wave w owns rows 8w .. 8w+7; a DPP row of 16 lanes owns an 8 x 8 block of them
@@ -102,10 +87,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
     static_assert(RING_E1 + 6 * RING_E1_LANES <= 2 * ICELLS, "the ring factors fit in the inbox");
     static_assert(!ALIAS_INBOX || sizeof(float2) * (GTHREADS / 64) * ICELLS <= sizeof(float) * NPLANES * PR * PS, "the inboxes fit in the planes");
 
-#ifdef DIRT_TRACE
-    long long tr_t[12]; int tr_n = 0; long long tr_c[4] = {0, 0, 0, 0};
-    const long long tr_wall0 = wall_clock64();
-#endif
+    GRAD_TRACE_BEGIN();
     GMARK();  // 0 start
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -280,30 +262,16 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
 
     // ---- the face loop.  Every DPP row of the wave (16 lanes = an 8 x 8 pixel block) walks the distinct faces among its
     //      pixels (key[j], -1 = none) and among the ring cells its lanes hold (lkey), all four rows at once: an iteration
-    //      takes one face per row.  Per face every lane forms its masked partial sums -- per vertex k the S values
-    //      b_k * (g_0 .. g_NCHV-1, fx, fy, fw) (S = 3 + NCHV rounded up to even; order below), as S / 2 packed pairs: one
-    //      v_pk_fma_f32 per pair and pixel -- the 3 S sums are reduced over the lanes of the row (row_reduce_scatter,
-    //      dirt_reduce.h: the totals of the row's face land in different lanes of the row) and at most two atomic
-    //      instructions add the four faces' totals to their vertices.  A block sees ~3 faces where the 16 x 8 half
-    //      regions of the two-group version saw ~6. ----
+    //      takes one face per row.  Per face every lane forms its masked partial sums (FaceValues, dirt_grad_common.h), the
+    //      sums are reduced over the lanes of the row (row_reduce_scatter, dirt_reduce.h: the totals of the row's face land in
+    //      different lanes of the row) and at most two atomic instructions add the four faces' totals to their vertices.
+    //      A block sees ~3 faces where the 16 x 8 half regions of the two-group version saw ~6. ----
     auto face_loop = [&](auto nchv_tag, const auto& g, const int (&key)[4], const bool (&covered)[4],
                          const float2v (&fpos_xy)[4], const float (&fpos_w)[4], const int (&lkey)[2], const float (&lb)[2][3], const float (&lf)[2][3]) {
         constexpr int NCHV = decltype(nchv_tag)::value;
-        // FWS (the {3,3} shape with the aliased inbox): an even channel count leaves the w factor alone in its pair -- g.., fx, fy,
-        // fw, 0 -- and the padding costs a register per pixel and per vertex sum.  There fw travels as a SCALAR next to the pairs
-        // (one v_fma_f32 instead of one v_pk_fma_f32 per pixel and vertex: the same instruction count) and its three sums
-        // follow the vertices' blocks in the reduction's input: 9 registers less in a loop that has to fit 128.
-        constexpr bool FWS = ALIAS_INBOX && NCHV == 6;
-        constexpr int S = FWS ? NCHV + 2 : (3 + NCHV + 1) & ~1;      // values per vertex held in pairs (padded to whole pairs)
-        constexpr int HP = S / 2;                   // ... as pairs
-        constexpr int NV = FWS ? 3 * S + 3 : 3 * S; // values per face
-        constexpr int NR = NV <= 16 ? 16 : (NV <= 24 ? 24 : 32);   // ... padded to what the row reduction takes
-        static_assert(NV <= NR, "");
-        // Order of a vertex's values: the colours first (they arrive as whole registers of the grad_pixels loads), then
-        // the position factors with (fx, fy) as one aligned pair: NCHV even: g.., fx, fy, fw, 0;  odd: g.., fw, fx, fy
-        // (FWS: g.., fx, fy per vertex, then fw of the three vertices: IW = S marks "not in the pairs").
-        constexpr int IW = FWS ? S : ((NCHV & 1) ? NCHV : NCHV + 2), IX = (NCHV & 1) ? NCHV + 1 : NCHV, IY = IX + 1;
-        static_assert((IX & 1) == 0 && IY < S && (FWS || IW < S), "");
+        using L = FaceValues<NCHV, ALIAS_INBOX && NCHV == 6>;   // (FWS: the {3,3} shape with the aliased inbox)
+        constexpr bool FWS = L::FWS;
+        constexpr int S = L::S, HP = L::HP, NV = L::NV, NR = L::NR, IW = L::IW, IX = L::IX, IY = L::IY;
         // this lane's roles: it adds the row totals of values rv[0], rv[1] of the row's face (row_value_of_lane): vertex
         // rv / S, component c = rv % S: c < NCHV: colour c; IX, IY, IW: (x, y, w) of grad_vertices
         // Pairs of rows: the two rows end up with the same totals -- see the end of an iteration -- so the even row sends
@@ -345,20 +313,11 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
         // pending faces: the keys of this lane's pixels / ring cells not yet added (NONE: none or done; "no face" is -1 = NONE)
         constexpr uint32_t NONE = 0xFFFFFFFFu;
         uint32_t pend[6];
-        // ---- non-finite factors (a NaN / Inf in grad_pixels, in `pixels` through the Scharr filter, a degenerate clip_w).
-        //      The loop below multiplies every pixel's factors by a barycentric that is ZEROED where the pixel is not of the
-        //      row's face: 0 * NaN would carry one pixel's NaN into every face of its 16 x 8 half region, where the reference
-        //      adds a pixel's terms to the vertices of its own face only (:140,228-230).  Such a pixel (rare; a sum of
-        //      finite factors that overflows is treated alike) adds its 3 (NCHV + 3) products itself -- the reference's own
-        //      atomics, term for term -- and leaves the loop: factors zeroed, face struck off. ----
+        // non-finite factors (pixel_nonfinite, dirt_grad_common.h): here 0 * NaN would reach every face of the pixel's 16 x 8
+        // half region
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float2v t = fp[j][0];
-#pragma unroll
-            for (int h = 1; h < HP; ++h) t += fp[j][h];
-            if (FWS) t.x += fpw[j];
-            const float u = (t.x + t.y) + ((bk[j][0] + bk[j][1]) + bk[j][2]);   // non-finite iff a factor is, or the sum overflows
-            const bool bad = !__builtin_isfinite(u);
+            const bool bad = pixel_nonfinite<L>(fp[j], fpw[j], bk[j]);
             pend[j] = bad ? NONE : (uint32_t)key[j];
             if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {   // wave-uniform: not taken on finite data
                 if (bad) {
@@ -384,18 +343,11 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
             }
         }
         pend[4] = (uint32_t)lkey[0]; pend[5] = (uint32_t)lkey[1];
-        // the row's next face: the smallest pending key of its 16 lanes (an all-lanes minimum by four DPP rotations)
+        // the row's next face: the smallest pending key of its 16 lanes ... and (pairs) of the other row of its pair: the left
+        // (rows 0, 1) and the right (2, 3) 16 x 8 pixels of the region
         auto next_face = [&]() {
-            uint32_t K = min(min(min(pend[0], pend[1]), min(pend[2], pend[3])), min(pend[4], pend[5]));
-            K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x128 /* row_ror:8 */, 0xF, 0xF, true));
-            K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x124 /* row_ror:4 */, 0xF, 0xF, true));
-            K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x122 /* row_ror:2 */, 0xF, 0xF, true));
-            K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x121 /* row_ror:1 */, 0xF, 0xF, true));
-            if (!ROWS) {   // ... and of the other row of its pair: the left (rows 0, 1) and the right (2, 3) 16 x 8 pixels of the region
-                const auto sw = __builtin_amdgcn_permlane16_swap(K, K, false, false);
-                K = min(sw[0], sw[1]);
-            }
-            return K;
+            const uint32_t K = row_min(min(min(min(pend[0], pend[1]), min(pend[2], pend[3])), min(pend[4], pend[5])));
+            return ROWS ? K : row_pair_min(K);
         };
         // (the loop is rotated: the next face is chosen as soon as this one's pixels are struck off the pending list, so
         // that its chain of cross-lane minima runs alongside the reduction's chain of cross-lane adds)
@@ -403,7 +355,6 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
         for (;;) {
             const lanemask live = __builtin_amdgcn_ballot_w64(K != NONE);   // rows that still have a face
             if (live == 0ull) break;
-            // the vertices this lane adds to (requested now, needed after the reduction)
             // the vertices this lane adds to (requested now, needed after the reduction)
             const uint32_t fbase = (K != NONE ? K : 0u) * 12u;
             int vsel[NROLES];
@@ -462,35 +413,20 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
             float d0, d1;
             row_reduce_scatter<NR>(acc, lane, d0, d1);
             if (!ROWS) {   // the two rows of a pair worked on the same face: their totals, added (both rows get the sum)
-                const auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d0), __float_as_uint(d0), false, false);
-                d0 = __uint_as_float(s0[0]) + __uint_as_float(s0[1]);
-                if (NR >= 24) {
-                    const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d1), __float_as_uint(d1), false, false);
-                    d1 = __uint_as_float(s1[0]) + __uint_as_float(s1[1]);
-                }
+                d0 = row_pair_sum(d0);
+                if (NR >= 24) d1 = row_pair_sum(d1);
             }
             // (a row / pair without a face this iteration has all-zero totals)
             float total[NROLES];
             total[0] = ROWS ? d0 : (odd_row ? d1 : d0);
             if (NROLES == 2) total[NROLES - 1] = d1;
-            // The addresses are formed BEFORE the branches on purpose: the wait for the vertex indices then sits on every
-            // path.  Inside a branch it would leave the load pending on the path around it, and the compiler answers that
-            // with s_waitcnt vmcnt(0) in the loop header -- where it also waits, every iteration, for the previous
-            // iteration's atomic to be acknowledged by the memory system (+3 us at K3, +11 us at K3-256).
+            // (addresses before the branches: pinned_vertex_address)
             float* dst[NROLES];
 #pragma unroll
-            for (int e = 0; e < NROLES; ++e) {
-                dst[e] = reinterpret_cast<float*>(reinterpret_cast<char*>(role_base[e]) + (size_t)((uint32_t)vsel[e] * role_stride[e]));
-                asm volatile("" : "+v"(dst[e]));
-            }
+            for (int e = 0; e < NROLES; ++e) dst[e] = pinned_vertex_address(role_base[e], vsel[e], role_stride[e]);
 #pragma unroll
-            for (int e = 0; e < NROLES; ++e) {
-                if (role_valid[e] && total[e] != 0.f)
-                    // (written as a GLOBAL atomic: behind the asm barrier above the compiler no longer knows the pointer's
-                    // address space and emits flat_atomic_add_f32, which is issued to the LDS and the memory pipeline alike
-                    // and counts on both wait counters)
-                    asm volatile("global_atomic_add_f32 %0, %1, off" : : "v"(dst[e]), "v"(total[e]) : "memory");
-            }
+            for (int e = 0; e < NROLES; ++e)
+                if (role_valid[e] && total[e] != 0.f) global_add(dst[e], total[e]);
             K = K_next;
         }
     };
@@ -663,19 +599,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
 #pragma unroll
                 for (int P = 0; P < NP_MAX; ++P) {
                     if (P >= 2 && !single) { Sx[P] = float2v{0.f, 0.f}; Sy[P] = float2v{0.f, 0.f}; continue; }
-                    // at(ox, oy) of pixel q: row 1 - oy, column q + 1 + ox of the taps; pixels q = 2P, 2P + 1
-                    const float2v mm = T[2][P], m0 = T[1][P], mp = T[0][P];
-                    const float2v pm = T[2][P + 1], p0 = T[1][P + 1], pp = T[0][P + 1];
-                    float2v d1 = ((mm + mp) - pm) - pp;
-                    float2v d2 = m0 - p0;
-                    float2v m1 = d1 * (3.f / 32.f), m2 = d2 * (10.f / 32.f);
-                    Sx[P] = m1 + m2;
-                    d1 = ((mm + pm) - mp) - pp;
-                    // the middle column of each pixel: the high half of one tap pair and the low half of the next
-                    d2.x = T[2][P].y - T[0][P].y;
-                    d2.y = T[2][P + 1].x - T[0][P + 1].x;
-                    m1 = d1 * (3.f / 32.f); m2 = d2 * (10.f / 32.f);
-                    Sy[P] = m1 + m2;
+                    scharr_pk(T, P, Sx[P], Sy[P]);
                 }
                 auto comp = [](const float2v (&v)[NP_MAX], int q) { return (q & 1) ? v[q >> 1].y : v[q >> 1].x; };
                 if (!single) {
@@ -721,7 +645,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
                             uint32_t bits = 0;
 #pragma unroll
                             for (int j = 0; j < 4; ++j) bits |= __builtin_amdgcn_inverse_ballot_w64(horiz_m[gi][j]) ? (1u << j) : 0u;
-                            bits = alias_wrap_fixup(p.pixels, p.B, H, W, C, iib, y, xs, cbase + ch, ib, bits, 0);
+                            bits = alias_wrap_fixup(p.pixels, p.B, H, W, C, iib, y, xs, cbase + ch, ib, bits);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) horiz_m[gi][j] = __builtin_amdgcn_ballot_w64(((bits >> j) & 1u) != 0u);
                         }
@@ -936,14 +860,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
 
     run_pass(integral_constant<int, CSPEC>{}, integral_constant<int, CSPEC == 1 ? 1 : 3>{});
     GMARK();  // 7 done
-#ifdef DIRT_TRACE
-    if (lane == 0 && g_trace_grad) {
-        long long* o = g_trace_grad + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 16;
-        for (int i = 0; i < 12; ++i) o[i] = i < tr_n ? tr_t[i] : 0;
-        o[12] = tr_c[0]; o[13] = tr_c[1];
-        o[14] = tr_wall0; o[15] = (((long long)wall_clock64() - tr_wall0) << 20) | (long long)(__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4 /* HW_REG_HW_ID */) & 0xFFFFF);
-    }
-#endif
+    GRAD_TRACE_END();
 }
 
 // The gradient pass's shape (pick_grad_shape); launch_grad launches it.
@@ -1058,9 +975,7 @@ hipError_t launch_grad(const GradParams& p_in, hipStream_t stream)
 {
     if (p_in.B == 0) return hipSuccess;
     GradParams p = p_in;
-    p.tiles_x = (p.W + GT - 1) / GT;
-    p.tiles_y = (p.H + GT - 1) / GT;
-    p.tiles_x_magic = tile_magic(p.tiles_x);
+    set_tile_grid(p, GT, GT);
     p.inv_w = 1.f / (float)p.W; p.inv_h = 1.f / (float)p.H;   // (IEEE divisions, as the kernel's own would be)
     p.pixels_aligned16 = ((reinterpret_cast<uintptr_t>(p.pixels) | reinterpret_cast<uintptr_t>(p.grad_pixels) |
                            reinterpret_cast<uintptr_t>(p.grad_background)) & 15u) == 0 ? 1 : 0;

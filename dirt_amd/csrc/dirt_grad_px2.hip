@@ -30,20 +30,7 @@
 
 namespace dirt {
 
-#ifdef DIRT_TRACE
-// Per-wave phase timestamps for tools/trace_grad.py (the layout of dirt_grad.hip's trace); tracing build only.
-__device__ long long* g_trace_grad_px2 = nullptr;
-extern "C" void dirt_debug_set_trace_grad_px2(void* p)
-{
-    long long* q = reinterpret_cast<long long*>(p);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_trace_grad_px2), &q, sizeof(q));
-}
-#define XMARK() do { if (tr_n < 12) { long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); tr_t[tr_n++] = t_; } } while (0)
-#define XCOUNT(i, v) do { tr_c[i] += (v); } while (0)
-#else
-#define XMARK() do {} while (0)
-#define XCOUNT(i, v) do {} while (0)
-#endif
+GRAD_TRACE_BUFFER(_px2)
 
 #ifndef DIRT_PX2_WAVES
 #define DIRT_PX2_WAVES(C_, DEBUG_) ((C_) == 4 ? 5 : ((DEBUG_) ? 7 : 8))   // waves per SIMD the register allocation aims at: 88 VGPRs for 4 channels (two channel
@@ -65,11 +52,9 @@ constexpr int XICELLS = 10 * XIS;       // ... of a wave's 16 x 8 region and the
 constexpr int XRING = 2 * 18 + 2 * 8;   // ring cells: one per lane (52 of 64)
 constexpr int PX = 2;                   // pixels per lane
 
-// alias_wrap_fixup (dirt_grad_common.h) with ROLLED loops: quirk Q1 at the right image border -- for the pixels of a pair
-// (first column xs, row y) flagged in `which`, the aliased "channels" 1, 2 of 1-channel group c lie in the NEXT image row (past
-// the end of the tensor: clamped to its last element), and their dilation axis (:185) is decided again from memory.  Same
-// arithmetic; one Scharr stencil at a time, nine loads each, so that this rare path (the last two interior columns of a
-// frame) is not the kernel's register high-water mark (inlined and unrolled it was: 106 VGPRs against ~90).
+// alias_wrap_fixup (dirt_grad_common.h) with ROLLED loops over the same scharr(): for the pixels of a pair (first column xs,
+// row y) flagged in `which`.  One stencil at a time, nine loads each, so that this rare path is not the kernel's register
+// high-water mark (inlined and unrolled it was: 106 VGPRs against ~90).
 __device__ __forceinline__ uint32_t alias_wrap_fixup_rolled(const float* __restrict__ pixels, int B, int H, int W, int C, int iib, int y, int xs,
                                                          int c, uint32_t which, uint32_t bits)
 {
@@ -78,7 +63,7 @@ __device__ __forceinline__ uint32_t alias_wrap_fixup_rolled(const float* __restr
     for (int j = 0; j < PX; ++j) {
         if (!((which >> j) & 1u)) continue;
         const size_t centre = ((size_t)iib * H + y) * W + xs + j;   // flat pixel index of the pixel
-        float l1x = 0.f, l1y = 0.f;
+        float l1y = 0.f, l1x = 0.f;
 #pragma unroll 1
         for (int ch = 0; ch < 3; ++ch) {
             // w[r][i] = element (centre + ch + i - 1) of row y - 1 + r in flat order, clamped to the end of the tensor
@@ -91,17 +76,8 @@ __device__ __forceinline__ uint32_t alias_wrap_fixup_rolled(const float* __restr
                     if (m > last) m = last;
                     w[r][i] = pixels[m * C + c];
                 }
-            const float mm = w[2][0], m0 = w[1][0], mp = w[0][0];
-            const float zm = w[2][1], zp = w[0][1];
-            const float pm = w[2][2], p0 = w[1][2], pp = w[0][2];
-            float d1 = ((mm + mp) - pm) - pp;
-            float d2 = m0 - p0;
-            float m1 = d1 * (3.f / 32.f), m2 = d2 * (10.f / 32.f);
-            const float sx = m1 + m2;
-            d1 = ((mm + pm) - mp) - pp;
-            d2 = zm - zp;
-            m1 = d1 * (3.f / 32.f); m2 = d2 * (10.f / 32.f);
-            const float sy = m1 + m2;
+            float sx, sy;
+            scharr(w, sx, sy);
             l1x = ch == 0 ? fabsf(sx) : l1x + fabsf(sx);
             l1y = ch == 0 ? fabsf(sy) : l1y + fabsf(sy);
         }
@@ -125,11 +101,8 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
     __shared__ __align__(16) float2 s_vw[XR][XVS];               // {clip_w, face} of every pixel of the halo'd tile
     __shared__ __align__(16) float2 s_inbox[XTHREADS / 64][XICELLS];  // per wave: (fx, fy) sent to each pixel of its region + ring
 
-#ifdef DIRT_TRACE
-    long long tr_t[12]; int tr_n = 0; long long tr_c[4] = {0, 0, 0, 0};
-    const long long tr_wall0 = wall_clock64();
-#endif
-    XMARK();  // 0 start
+    GRAD_TRACE_BEGIN();
+    GMARK();  // 0 start
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -253,7 +226,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
         z[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (lane + 64 < XICELLS / 2) z[lane + 64] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    XMARK();  // 1 loads issued, state tile stored
+    GMARK();  // 1 loads issued, state tile stored
 #pragma unroll
     for (int k = 0; k < PITEMS; ++k) {
         const int row = st_row + PROWS * k;
@@ -261,9 +234,9 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) s_pix[ch][row][st_ci] = stage_v[k][ch];
     }
-    XMARK();  // 2 planes stored
+    GMARK();  // 2 planes stored
     __syncthreads();
-    XMARK();  // 3 barrier passed
+    GMARK();  // 3 barrier passed
 
     // ---- Scharr (:126-127, operation for operation: negative-offset minus positive-offset, offset_y is up = the previous
     //      tensor row) on the lane's pair with the packed fp32 instructions, streamed per channel into what is needed of it:
@@ -303,19 +276,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
 #pragma unroll
             for (int P = 0; P < 2; ++P) {
                 if (P >= 1 && !single) { Sx[P] = float2v{0.f, 0.f}; Sy[P] = float2v{0.f, 0.f}; continue; }
-                // at(ox, oy) of pixel q: row 1 - oy, column q + 1 + ox of the taps; pixels q = 2P, 2P + 1
-                const float2v mm = T[2][P], m0 = T[1][P], mp = T[0][P];
-                const float2v pm = T[2][P + 1], p0 = T[1][P + 1], pp = T[0][P + 1];
-                float2v d1 = ((mm + mp) - pm) - pp;
-                float2v d2 = m0 - p0;
-                float2v m1 = d1 * (3.f / 32.f), m2 = d2 * (10.f / 32.f);
-                Sx[P] = m1 + m2;
-                d1 = ((mm + pm) - mp) - pp;
-                // the middle column of each pixel: the high half of one tap pair and the low half of the next
-                d2.x = T[2][P].y - T[0][P].y;
-                d2.y = T[2][P + 1].x - T[0][P + 1].x;
-                m1 = d1 * (3.f / 32.f); m2 = d2 * (10.f / 32.f);
-                Sy[P] = m1 + m2;
+                scharr_pk(T, P, Sx[P], Sy[P]);
             }
             auto comp = [](const float2v (&v)[2], int q) { return (q & 1) ? v[q >> 1].y : v[q >> 1].x; };
             const float2v gp = float2v{g[0][ch], g[1][ch]};
@@ -363,7 +324,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
             __builtin_amdgcn_sched_barrier(0);  // one channel's taps at a time
         }
     }
-    XMARK();  // 4 Scharr done
+    GMARK();  // 4 Scharr done
 
     // ---- the pair and its six neighbours: clip_w and face ----
     float w_own[PX], w_up[PX], w_dn[PX], w_l, w_r;
@@ -439,11 +400,10 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
             }
         }
     }
-    XMARK();  // 5 dilation done
+    GMARK();  // 5 dilation done
 
     // ---- position totals of the pair's pixels (own sums + what the neighbours sent through the inbox, and fw of the totals)
-    //      and the ring: what this wave's pixels sent to pixels of other waves.  Those pixels' faces take it through the face
-    //      loop, one ring cell per lane: cells 0-17 the row above, 18-35 the row below, 36-43 / 44-51 the columns left / right. ----
+    //      and the ring: one ring cell per lane (52 of 64) ----
     float2v fpos_xy[PX];
     float fpos_w[PX];
     int lkey = -1;
@@ -484,25 +444,16 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
                 }
             }
         }
-        XCOUNT(0, __popcll(__builtin_amdgcn_ballot_w64(lkey >= 0)));
+        GCOUNT(0, __popcll(__builtin_amdgcn_ballot_w64(lkey >= 0)));
     }
-    XMARK();  // 6 face loop starts
+    GMARK();  // 6 face loop starts
 
     // ---- the face loop (dirt_grad.hip): the two rows of an 8 x 8 block walk the distinct faces among their pixels (key[j],
     //      -1 = none) and among the ring cells their lanes hold (lkey), both blocks of the wave at once.  Per face every lane
-    //      forms its masked partial sums -- per vertex k the S values b_k * (g_0 .. g_NCH-1, fx, fy, fw) (S = 3 + NCH rounded
-    //      up to even; order below), as S / 2 packed pairs: one v_pk_fma_f32 per pair and pixel -- the 3 S sums are reduced
-    //      over the lanes of each row (row_reduce_scatter), the two rows' totals joined (v_permlane16_swap) and ONE atomic
-    //      instruction adds them to the face's three vertices. ----
-    constexpr int S = (3 + NCH + 1) & ~1;       // values per vertex (padded to whole pairs)
-    constexpr int HP = S / 2;                   // ... as pairs
-    constexpr int NV = 3 * S;                   // values per face
-    constexpr int NR = NV <= 16 ? 16 : 24;      // ... padded to what the row reduction takes
-    static_assert(NV <= NR, "");
-    // Order of a vertex's values: the colours first, then the position factors with (fx, fy) as one aligned pair:
-    // NCH even: g.., fx, fy, fw, 0;  odd: g.., fw, fx, fy.
-    constexpr int IW = (NCH & 1) ? NCH : NCH + 2, IX = (NCH & 1) ? NCH + 1 : NCH, IY = IX + 1;
-    static_assert((IX & 1) == 0 && IY < S && IW < S, "");
+    //      forms its masked partial sums (FaceValues), they are reduced over the lanes of each row (row_reduce_scatter), the two
+    //      rows' totals joined and ONE atomic instruction adds them to the face's three vertices. ----
+    using L = FaceValues<NCH>;
+    constexpr int S = L::S, HP = L::HP, NV = L::NV, NR = L::NR, IW = L::IW, IX = L::IX, IY = L::IY;
     // this lane's role: it adds the pair-of-rows total of value rv of the block's face (row_value_of_lane): vertex rv / S,
     // component c = rv % S: c < NCH: colour c; IX, IY, IW: (x, y, w) of grad_vertices.  The two rows end up with the same
     // totals, so the even row sends d0's value and the odd row d1's: one atomic instruction per iteration.
@@ -531,11 +482,6 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
     // pending faces: the keys of this lane's pixels / ring cell not yet added (NONE: none or done; "no face" is -1 = NONE)
     constexpr uint32_t NONE = 0xFFFFFFFFu;
     uint32_t pend[PX + 1];
-    // ---- non-finite factors (a NaN / Inf in grad_pixels, in `pixels` through the Scharr filter, a degenerate clip_w).  The
-    //      loop multiplies every pixel's factors by a barycentric that is ZEROED where the pixel is not of the block's face:
-    //      0 * NaN would carry one pixel's NaN into every face of its 8 x 8 block, where the reference adds a pixel's terms to
-    //      the vertices of its own face only (:140,228-230).  Such a pixel adds its 3 (NCH + 3) products itself -- the
-    //      reference's own atomics, term for term -- and leaves the loop: factors zeroed, face struck off. ----
     bool gbk_done[PX];   // grad_background of the pixel was written here (a non-finite uncovered pixel: its factors are zeroed for the loop)
     auto store_gbk = [&](int j) {
         const uint32_t off = own_off + (uint32_t)j * pixel_bytes;
@@ -550,11 +496,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
     };
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-        float2v t = fp[j][0];
-#pragma unroll
-        for (int h = 1; h < HP; ++h) t += fp[j][h];
-        const float u = (t.x + t.y) + ((bk[j][0] + bk[j][1]) + bk[j][2]);   // non-finite iff a factor is, or the sum overflows
-        const bool bad = !__builtin_isfinite(u);
+        const bool bad = pixel_nonfinite<L>(fp[j], 0.f, bk[j]);
         gbk_done[j] = false;
         pend[j] = bad ? NONE : (uint32_t)key[j];
         if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {   // wave-uniform: not taken on finite data
@@ -583,17 +525,8 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
         }
     }
     pend[PX] = (uint32_t)lkey;
-    // the block's next face: the smallest pending key of its 32 lanes (an all-lanes minimum by four DPP rotations and one
-    // swap with the other row of the block)
-    auto next_face = [&]() {
-        uint32_t K = min(min(pend[0], pend[1]), pend[2]);
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x128 /* row_ror:8 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x124 /* row_ror:4 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x122 /* row_ror:2 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x121 /* row_ror:1 */, 0xF, 0xF, true));
-        const auto sw = __builtin_amdgcn_permlane16_swap(K, K, false, false);
-        return min(sw[0], sw[1]);
-    };
+    // the block's next face: the smallest pending key of its 32 lanes
+    auto next_face = [&]() { return row_pair_min(row_min(min(min(pend[0], pend[1]), pend[2]))); };
     // (the loop is rotated: the next face is chosen as soon as this one's pixels are struck off the pending list, so that its
     // chain of cross-lane minima runs alongside the reduction's chain of cross-lane adds)
     uint32_t K = next_face();
@@ -632,7 +565,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
                 }
             }
         }
-        XCOUNT(1, 1);
+        GCOUNT(1, 1);
         const uint32_t K_next = next_face();
         float acc[NR];
 #pragma unroll
@@ -640,24 +573,15 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
         float d0, d1;
         row_reduce_scatter<NR>(acc, lane, d0, d1);
         // the two rows of a block worked on the same face: their totals, added (both rows get the sum)
-        const auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d0), __float_as_uint(d0), false, false);
-        d0 = __uint_as_float(s0[0]) + __uint_as_float(s0[1]);
-        if (NR >= 24) {
-            const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(d1), __float_as_uint(d1), false, false);
-            d1 = __uint_as_float(s1[0]) + __uint_as_float(s1[1]);
-        }
+        d0 = row_pair_sum(d0);
+        if (NR >= 24) d1 = row_pair_sum(d1);
         // (a block without a face this iteration has all-zero totals)
         const float total = odd_row ? d1 : d0;
-        // The address is formed BEFORE the branch on purpose: the wait for the vertex index then sits on every path (inside
-        // the branch the load stays pending on the path around it and the compiler answers with s_waitcnt vmcnt(0) in the
-        // loop header, where it also waits for the previous iteration's atomic: dirt_grad.hip).
-        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(role_base) + (size_t)((uint32_t)vsel * role_stride));
-        asm volatile("" : "+v"(dst));
-        if (role_valid && total != 0.f)
-            asm volatile("global_atomic_add_f32 %0, %1, off" : : "v"(dst), "v"(total) : "memory");
+        float* dst = pinned_vertex_address(role_base, vsel, role_stride);
+        if (role_valid && total != 0.f) global_add(dst, total);
         K = K_next;
     }
-    XMARK();  // 7 loop done
+    GMARK();  // 7 loop done
 
     // ---- background gradient (:143-147): grad_pixels where nothing is covered, zero elsewhere.  After the face loop (the
     //      stores of a wave then spread over the time in which the waves finish) and from the registers the loop's colour
@@ -665,23 +589,14 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
 #pragma unroll
     for (int j = 0; j < PX; ++j)
         if (in_px[j] && !gbk_done[j]) store_gbk(j);
-    XMARK();  // 8 done
-#ifdef DIRT_TRACE
-    if (lane == 0 && g_trace_grad_px2) {
-        long long* o = g_trace_grad_px2 + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 16;
-        for (int i = 0; i < 12; ++i) o[i] = i < tr_n ? tr_t[i] : 0;
-        o[12] = tr_c[0]; o[13] = tr_c[1];
-        o[14] = tr_wall0; o[15] = (((long long)wall_clock64() - tr_wall0) << 20) | (long long)(__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4 /* HW_REG_HW_ID */) & 0xFFFFF);
-    }
-#endif
+    GMARK();  // 8 done
+    GRAD_TRACE_END(_px2);
 }
 
 hipError_t launch_grad_px2(const GradParams& p, hipStream_t stream)
 {
     GradParams q = p;
-    q.tiles_x = (p.W + XT - 1) / XT;
-    q.tiles_y = (p.H + YT - 1) / YT;
-    q.tiles_x_magic = tile_magic(q.tiles_x);
+    set_tile_grid(q, XT, YT);
     const dim3 grid((unsigned)(q.tiles_x * q.tiles_y), (unsigned)p.B), block(XTHREADS);
 #define DIRT_LAUNCH_PX2(C_)                                                                          \
     do {                                                                                             \

@@ -22,20 +22,7 @@
 
 namespace dirt {
 
-#ifdef DIRT_TRACE
-// Per-wave phase timestamps for tools/trace_grad.py (the layout of dirt_grad.hip's trace); tracing build only.
-__device__ long long* g_trace_grad_small = nullptr;
-extern "C" void dirt_debug_set_trace_grad_small(void* p)
-{
-    long long* q = reinterpret_cast<long long*>(p);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_trace_grad_small), &q, sizeof(q));
-}
-#define SMARK() do { if (tr_n < 12) { long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); tr_t[tr_n++] = t_; } } while (0)
-#define SCOUNT(i, v) do { tr_c[i] += (v); } while (0)
-#else
-#define SMARK() do {} while (0)
-#define SCOUNT(i, v) do {} while (0)
-#endif
+GRAD_TRACE_BUFFER(_small)
 
 namespace {
 
@@ -44,23 +31,6 @@ constexpr int SROWS = ST + 2;     // staged rows y0-1 .. y0+16
 constexpr int SCOLS = ST + 4;     // staged columns x0-1 .. x0+18: a single channel's aliased "channels" (quirk Q1) are the next two pixels
 constexpr int SIB = 10;           // inbox row stride: cell (ty + 1) * 10 + tx + 1 for ty, tx in -1..8 (the wave's 8 x 8 region + ring)
 constexpr int SRING = 36;         // ring cells of a region
-
-// Scharr response of one "channel" from its 3 x 3 taps w[r][i] = (row y - 1 + r, column x - 1 + i), operation for operation
-// as csrc/rasterise_grad_egl.cu:126-127 (negative-offset minus positive-offset; offset_y is up = the previous tensor row).
-__device__ __forceinline__ void scharr(const float (&w)[3][3], float& sx, float& sy)
-{
-    const float mm = w[2][0], m0 = w[1][0], mp = w[0][0];
-    const float zm = w[2][1], zp = w[0][1];
-    const float pm = w[2][2], p0 = w[1][2], pp = w[0][2];
-    float d1 = ((mm + mp) - pm) - pp;
-    float d2 = m0 - p0;
-    float m1 = d1 * (3.f / 32.f), m2 = d2 * (10.f / 32.f);
-    sx = m1 + m2;
-    d1 = ((mm + pm) - mp) - pp;
-    d2 = zm - zp;
-    m1 = d1 * (3.f / 32.f); m2 = d2 * (10.f / 32.f);
-    sy = m1 + m2;
-}
 
 }  // namespace
 
@@ -77,11 +47,8 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
     __shared__ __align__(16) float2 s_inbox[4][SIB * SIB + 2];                   // per wave: (fx, fy) sent to each pixel of its region + ring
     constexpr int LC = CSPEC == 3 ? 4 : CSPEC;       // floats per staged pixel
 
-#ifdef DIRT_TRACE
-    long long tr_t[12]; int tr_n = 0; long long tr_c[4] = {0, 0, 0, 0};
-    const long long tr_wall0 = wall_clock64();
-#endif
-    SMARK();  // 0 start
+    GRAD_TRACE_BEGIN();
+    GMARK();  // 0 start
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int iib = blockIdx.y;
     const int H = p.H, W = p.W;
@@ -168,10 +135,10 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
     }
     float bk[3];
     decode_bary(state_b[own], bk);
-    SMARK();  // 1 loads issued, tile stored
-    SMARK();  // 2
+    GMARK();  // 1 loads issued, tile stored
+    GMARK();  // 2
     __syncthreads();
-    SMARK();  // 3 barrier passed
+    GMARK();  // 3 barrier passed
 
     // ---- Scharr, the L1 norms that choose the dilation axis (:185, all three "channels" of the reference's Vec3 in its
     //      summation order) and dL/dx, dL/dy of :203-208, per channel group ----
@@ -221,14 +188,14 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
                 if (!q1_intended && x0 + ST + 3 > W) {   // workgroup-uniform: only tiles on the right image border
                     const uint32_t ib = (interior && x + 3 > W - 1) ? 1u : 0u;
                     if (__builtin_amdgcn_ballot_w64(ib != 0u) != 0ull)
-                        hz = (alias_wrap_fixup(p.pixels, p.B, H, W, C, iib, y, x, ch, ib, hz ? 1u : 0u, 0) & 1u) != 0u;
+                        hz = (alias_wrap_fixup(p.pixels, p.B, H, W, C, iib, y, x, ch, ib, hz ? 1u : 0u) & 1u) != 0u;
                 }
                 horiz[gi] = hz;
             }
         }
     }
 
-    SMARK();  // 4 Scharr done
+    GMARK();  // 4 Scharr done
     // ---- the pixel and its four neighbours: clip_w and face ----
     const float2 s_own = s_vw[ly + 1][lx + 1], s_l = s_vw[ly + 1][lx], s_r = s_vw[ly + 1][lx + 2];
     const float2 s_u = s_vw[ly][lx + 1], s_d = s_vw[ly + 2][lx + 1];
@@ -291,7 +258,7 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
         }
     }
 
-    SMARK();  // 5 dilation done
+    GMARK();  // 5 dilation done
     // ---- totals per target pixel: own + what the neighbours sent; the ring cells (targets outside this wave's region) ----
     const float2 in_own = inbox[my_cell];
     const float px_x = fx + in_own.x, px_y = fy + in_own.y;
@@ -352,20 +319,13 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
     }
     constexpr uint32_t NONE = 0xFFFFFFFFu;
     uint32_t pend0 = covered ? (uint32_t)f_own : NONE, pend1 = (uint32_t)lkey;
-    auto next_face = [&]() {
-        uint32_t K = min(pend0, pend1);
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x128 /* row_ror:8 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x124 /* row_ror:4 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x122 /* row_ror:2 */, 0xF, 0xF, true));
-        K = min(K, (uint32_t)__builtin_amdgcn_mov_dpp((int)K, 0x121 /* row_ror:1 */, 0xF, 0xF, true));
-        return K;
-    };
-    SCOUNT(0, __popcll(__builtin_amdgcn_ballot_w64(lkey >= 0)));
-    SMARK();  // 6 face loop starts
+    auto next_face = [&]() { return row_min(min(pend0, pend1)); };
+    GCOUNT(0, __popcll(__builtin_amdgcn_ballot_w64(lkey >= 0)));
+    GMARK();  // 6 face loop starts
     uint32_t K = next_face();
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(K != NONE) == 0ull) break;
-        SCOUNT(1, 1);
+        GCOUNT(1, 1);
         const bool live = K != NONE;
         const bool m0 = live & (pend0 == K), m1 = live & (pend1 == K);
         // the face's three vertex indices, from whichever lanes of the row hold it (+1: 0 = "not mine"); all holders agree
@@ -376,11 +336,7 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
                                    m0 ? (uint32_t)vid_own.z + 1u : (m1 ? (uint32_t)lvid.z + 1u : 0u)};
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                uint32_t r = h[k];
-                r = max(r, (uint32_t)__builtin_amdgcn_mov_dpp((int)r, 0x128 /* row_ror:8 */, 0xF, 0xF, true));
-                r = max(r, (uint32_t)__builtin_amdgcn_mov_dpp((int)r, 0x124 /* row_ror:4 */, 0xF, 0xF, true));
-                r = max(r, (uint32_t)__builtin_amdgcn_mov_dpp((int)r, 0x122 /* row_ror:2 */, 0xF, 0xF, true));
-                r = max(r, (uint32_t)__builtin_amdgcn_mov_dpp((int)r, 0x121 /* row_ror:1 */, 0xF, 0xF, true));
+                const uint32_t r = row_max(h[k]);
                 rvid[k] = r != 0u ? r - 1u : 0u;   // (a row without a face this iteration: vertex 0, and `live` keeps it from adding anything)
             }
         }
@@ -408,7 +364,8 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
         float total[NROLES];
         total[0] = d0;
         if (NROLES == 2) total[NROLES - 1] = d1;
-        // (addresses before the branches: see the face loop of dirt_grad.hip)
+        // (addresses before the branches, for the reason given at pinned_vertex_address in dirt_grad_common.h; formed and pinned
+        // in place here, not by a call of it: through the call the compiler swaps the multiply's operands)
         float* dst[NROLES];
 #pragma unroll
         for (int e = 0; e < NROLES; ++e) {
@@ -417,27 +374,17 @@ __global__ __launch_bounds__(256) void grad_kernel_px1(GradParams p)
         }
 #pragma unroll
         for (int e = 0; e < NROLES; ++e)
-            if (role_valid[e] && live && total[e] != 0.f)
-                asm volatile("global_atomic_add_f32 %0, %1, off" : : "v"(dst[e]), "v"(total[e]) : "memory");
+            if (role_valid[e] && live && total[e] != 0.f) global_add(dst[e], total[e]);
         K = K_next;
     }
-    SMARK();  // 7 done
-#ifdef DIRT_TRACE
-    if (lane == 0 && g_trace_grad_small) {
-        long long* o = g_trace_grad_small + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 16;
-        for (int i = 0; i < 12; ++i) o[i] = i < tr_n ? tr_t[i] : 0;
-        o[12] = tr_c[0]; o[13] = tr_c[1];
-        o[14] = tr_wall0; o[15] = (((long long)wall_clock64() - tr_wall0) << 20) | (long long)(__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4 /* HW_REG_HW_ID */) & 0xFFFFF);
-    }
-#endif
+    GMARK();  // 7 done
+    GRAD_TRACE_END(_small);
 }
 
 hipError_t launch_grad_small(const GradParams& p, hipStream_t stream)
 {
     GradParams q = p;
-    q.tiles_x = (p.W + ST - 1) / ST;
-    q.tiles_y = (p.H + ST - 1) / ST;
-    q.tiles_x_magic = tile_magic(q.tiles_x);
+    set_tile_grid(q, ST, ST);
     const dim3 grid((unsigned)(q.tiles_x * q.tiles_y), (unsigned)p.B), block(256);
 #define DIRT_LAUNCH_SMALL(C_)                                                                        \
     do {                                                                                             \

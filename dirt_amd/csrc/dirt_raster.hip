@@ -713,9 +713,7 @@ hipError_t launch_raster(const RasterParams& p_in, int B, bool visibility_only, 
     if (raster_v2_applies(p_in, B, visibility_only)) return launch_raster_v2(p_in, B, visibility_only, stream);
     RasterParams p = p_in;
     const int tile = raster_tile_choice(p.H, p.W, B, p.flags);   // (the bin grid was sized for this very choice: dirt_capi.hip::geom_params)
-    p.tiles_x = (p.W + tile - 1) / tile;
-    p.tiles_y = (p.H + tile - 1) / tile;
-    p.tiles_x_magic = tile_magic(p.tiles_x);
+    set_tile_grid(p, tile, tile);
     const dim3 grid((unsigned)(p.tiles_x * p.tiles_y), (unsigned)B);
     {
         const size_t nwg = (size_t)grid.x * grid.y;

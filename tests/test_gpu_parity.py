@@ -374,6 +374,34 @@ def test_channel_group_passes(gpu, oracle, C):
                 assert np.array_equal(dbg.cpu().numpy(), ow['debug_thingy']), 'C=%d debug_thingy' % C
             parity.grads_close(gv, gvc, ow, 'C=%d flags=%d' % (C, flags), tol=5e-6)
 
+def test_aliased_inbox_shape_as_the_library_picks_it(gpu, oracle):
+    """grad_kernel<4, false, false, false, true> -- the per-wave inbox aliased onto the pixel planes -- is the library's own
+    choice for 4-channel grids of at least 2 048 workgroups of 32 x 32 tiles, which no small frame reaches: 128 scenes of
+    128 x 128 pixels (16 tiles each) do, with no shape pinned and no debug output.  Eight distinct scenes, repeated 16 times, so
+    that the oracle runs on eight: forward bit for bit, grad_background exactly, every repeat's gradients within the suite's
+    5e-6 of the oracle's, and the 16 repeats of a scene within the same tolerance of each other.  Every element is compared."""
+    H = W = 128
+    C, NS, REP = 4, 8, 16
+    s = scenes.batch_scene(40, H, W, C, seeds=list(range(61, 61 + NS)), r_lo=0.05, r_hi=0.3)
+    want = oracle.forward(s['background'], s['vertices'], s['vertex_colors'], s['faces'])
+    ow = oracle.backward(s['vertices'], s['faces'], want, s['grad_pixels'])
+    d = {k: _t(np.tile(s[k], (REP,) + (1,) * (s[k].ndim - 1)), gpu) for k in ('background', 'vertices', 'vertex_colors', 'faces', 'grad_pixels')}
+    assert d['background'].shape[0] * ((H + 31) // 32) * ((W + 31) // 32) >= 2048
+    px = ops._op_rasterise(d['background'], d['vertices'], d['vertex_colors'], d['faces'], H, W, C)
+    got = px.cpu().numpy().reshape(REP, NS, H, W, C)
+    assert np.array_equal(got.view(np.uint32), np.broadcast_to(want.view(np.uint32), got.shape))
+    gb, gv, gvc, _ = ops._op_rasterise_grad(d['vertices'], d['faces'], px, d['grad_pixels'], H, W, C)
+    gb = gb.cpu().numpy().reshape(REP, NS, H, W, C)
+    assert np.array_equal(gb.view(np.uint32), np.broadcast_to(ow['grad_background'].view(np.uint32), gb.shape))
+    gv = gv.cpu().numpy().reshape((REP, NS) + tuple(gv.shape[1:]))
+    gvc = gvc.cpu().numpy().reshape((REP, NS) + tuple(gvc.shape[1:]))
+    assert np.isfinite(gv).all() and np.isfinite(gvc).all()   # grads_close leaves non-finite elements out: there are none
+    first = dict(ow, grad_vertices=gv[0], grad_vertex_colors=gvc[0])
+    for r in range(REP):
+        parity.grads_close(gv[r], gvc[r], ow, 'aliased inbox, repeat %d' % r, tol=5e-6)
+        parity.grads_close(gv[r], gvc[r], first, 'aliased inbox, repeat %d against repeat 0' % r, tol=5e-6)
+
+
 @pytest.mark.parametrize('C', [1, 3, 4, 5, 16])
 def test_dense_outputs_from_the_state(gpu, oracle, C):
     """DIRT_FLAG_DENSE_FROM_STATE (what the autograd path uses): the gradients are summed in the state's interleaved
