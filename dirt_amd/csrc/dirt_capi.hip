@@ -13,19 +13,12 @@
 #include "../../include/dirt_hip.h"
 #include "dirt_launch.h"
 #include "dirt_raster_common.h"
+#include "dirt_stage.h"
 
 namespace {
 
 thread_local char g_last_error[512] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
+constexpr dirt::ErrorSetter fail = dirt::set_last_error;
 
 // ---- optional per-kernel HIP-event timing (DIRT_FLAG_PROFILE) ----------------------------------
 enum Slot { SLOT_GEOMETRY = 0, SLOT_RASTER_FWD, SLOT_RASTER_VIS, SLOT_GRAD, SLOT_COUNT };
@@ -283,12 +276,12 @@ dirt::RasterParams raster_params(const Carved& c, const dirt::GeomParams& g, int
 }  // namespace
 
 namespace dirt {
-// dirt_last_error()'s text for the entry points that live in other translation units (dirt_shade.hip): returns `code`
+// dirt_last_error()'s text, for this file (`fail`) and the entry points of dirt_shade.hip and dirt_geometry.hip
 int set_last_error(int code, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
+    format_error(g_last_error, sizeof(g_last_error), fmt, ap);
     va_end(ap);
     return code;
 }

@@ -32,9 +32,7 @@
 // gradient is wanted): 2 launches, + 1 for the matrices.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include "../../include/dirt_hip.h"
-#include "dirt_launch.h"
+#include "dirt_stage.h"
 
 namespace dirt {
 
@@ -63,23 +61,11 @@ struct VertexStageParams {
     int pre_split, long_list;
 };
 
-struct G3 { float x, y, z; };      // consecutive floats, 4-byte aligned: one access
-struct G4 { float x, y, z, w; };
-
-__device__ __forceinline__ float g_dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void g_cross(const float (&a)[3], const float (&b)[3], float (&c)[3])
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // a vertex as the composition sees it: (x, y, z, w or 1)
 __device__ __forceinline__ void load_vertex(const VertexStageParams& P, const float* __restrict__ vb, int u, float (&x)[4])
 {
     const float* __restrict__ p = vb + (size_t)u * P.C;
-    const G3 t = *reinterpret_cast<const G3*>(p);
+    const Float3 t = *reinterpret_cast<const Float3*>(p);
     x[0] = t.x; x[1] = t.y; x[2] = t.z;
     x[3] = P.C == 4 ? p[3] : 1.f;
 }
@@ -116,26 +102,8 @@ __device__ __forceinline__ void face_geometry(const VertexStageParams& P, const 
     world3(P, vb, m, has_model, q.i[2], w2);
 #pragma unroll
     for (int j = 0; j < 3; ++j) { q.e1[j] = w1[j] - w0[j]; q.e2[j] = w2[j] - w0[j]; }
-    g_cross(q.e1, q.e2, q.n);
-    q.len = sqrtf(g_dot3(q.n, q.n));
-}
-
-// ---- the sum of a value over the 64 lanes of a wave, in every lane, in a fixed tree: DPP adds inside the rows of 16, then the four rows
-template <int CTRL>
-__device__ __forceinline__ float geom_dpp(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ float geom_wave_sum(float v)
-{
-    v += geom_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += geom_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += geom_dpp<0x141>(v);   // row_half_mirror
-    v += geom_dpp<0x140>(v);   // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
+    cross3(q.e1, q.e2, q.n);
+    q.len = sqrtf(dot3(q.n, q.n));
 }
 
 // ---- s = the sum of term(entry) over entries [beg, end) of this lane's vertex.  Lists of up to `long_list` entries are walked
@@ -166,7 +134,7 @@ __device__ __forceinline__ void sum_over_list(const int32_t* __restrict__ entrie
             term(entries[e], c);
             p[0] += c[0]; p[1] += c[1]; p[2] += c[2];
         }
-        p[0] = geom_wave_sum(p[0]); p[1] = geom_wave_sum(p[1]); p[2] = geom_wave_sum(p[2]);
+        p[0] = wave_sum(p[0]); p[1] = wave_sum(p[1]); p[2] = wave_sum(p[2]);
         if (lane == src) { s[0] = p[0]; s[1] = p[1]; s[2] = p[2]; }
     }
 }
@@ -204,12 +172,12 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_forward_kernel(VertexStageP
         load_vertex(P, vb, i, x);
         if (has_model) transform<4>(x, m, w);
         else { w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3]; }
-        if (P.world) *reinterpret_cast<G4*>(P.world + row * 4) = G4{w[0], w[1], w[2], w[3]};
+        if (P.world) *reinterpret_cast<Float4*>(P.world + row * 4) = Float4{w[0], w[1], w[2], w[3]};
         if (P.clip) {
             float q[16], c[4];
             load_matrix(P.vp + (size_t)blockIdx.y * P.vp_stride, q);
             transform<4>(w, q, c);
-            *reinterpret_cast<G4*>(P.clip + row * 4) = G4{c[0], c[1], c[2], c[3]};
+            *reinterpret_cast<Float4*>(P.clip + row * 4) = Float4{c[0], c[1], c[2], c[3]};
         }
     }
     if (!P.normals) return;   // (uniform)
@@ -218,10 +186,10 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_forward_kernel(VertexStageP
     normal_sum(P, vb, m, has_model, beg, end, s);
     if (!live) return;
     if (!P.pre_split) {
-        const float inv = 1.f / (sqrtf(g_dot3(s, s)) + 1.e-12f);
+        const float inv = 1.f / (sqrtf(dot3(s, s)) + 1.e-12f);
         s[0] *= inv; s[1] *= inv; s[2] *= inv;
     }
-    *reinterpret_cast<G3*>(P.normals + row * 3) = G3{s[0], s[1], s[2]};
+    store3(P.normals + row * 3, s);
 }
 
 // ---- backward, first launch: d loss / d s from d loss / d normals, per vertex (s recomputed as the forward computes it)
@@ -238,12 +206,13 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_sum_grad_kernel(VertexStage
     float s[3];
     normal_sum(P, vb, m, has_model, beg, end, s);
     if (!live) return;
-    const G3 t = *reinterpret_cast<const G3*>(P.g_normals + row * 3);
-    const float gn[3] = {t.x, t.y, t.z};
+    float gn[3];
+    load3(P.g_normals + row * 3, gn);
     // normals = s / (L + 1e-12):  d s = gn / (L + 1e-12) + (d L) s / L,  d L = -(gn . s) / (L + 1e-12)^2;  nothing through L at s = 0
-    const float L = sqrtf(g_dot3(s, s)), inv = 1.f / (L + 1.e-12f);
-    const float k = L == 0.f ? 0.f : -((g_dot3(gn, s) * inv) * inv) / L;
-    *reinterpret_cast<G3*>(P.g_sum_out + row * 3) = G3{gn[0] * inv + s[0] * k, gn[1] * inv + s[1] * k, gn[2] * inv + s[2] * k};
+    const float L = sqrtf(dot3(s, s)), inv = 1.f / (L + 1.e-12f);
+    const float k = L == 0.f ? 0.f : -((dot3(gn, s) * inv) * inv) / L;
+    const float gs[3] = {gn[0] * inv + s[0] * k, gn[1] * inv + s[1] * k, gn[2] * inv + s[2] * k};
+    store3(P.g_sum_out + row * 3, gs);
 }
 
 // ---- backward, second launch: per vertex, the gradient its incident faces send to its world position (each face's gradient
@@ -272,18 +241,18 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_gather_kernel(VertexStagePa
             face_geometry(P, vb, m, has_model, f, q);
             float gf[3];   // d loss / d fn: the face's unit normal went to its three vertices
             {
-                const G3 a = *reinterpret_cast<const G3*>(gs + (size_t)q.i[0] * 3), b = *reinterpret_cast<const G3*>(gs + (size_t)q.i[1] * 3),
-                         d = *reinterpret_cast<const G3*>(gs + (size_t)q.i[2] * 3);
+                const Float3 a = *reinterpret_cast<const Float3*>(gs + (size_t)q.i[0] * 3), b = *reinterpret_cast<const Float3*>(gs + (size_t)q.i[1] * 3),
+                         d = *reinterpret_cast<const Float3*>(gs + (size_t)q.i[2] * 3);
                 gf[0] = (a.x + b.x) + d.x; gf[1] = (a.y + b.y) + d.y; gf[2] = (a.z + b.z) + d.z;
             }
             // fn = n / (len + 1e-12): as for s above; a zero-area face passes gf / 1e-12 on
             const float inv = 1.f / (q.len + 1.e-12f);
-            const float k = q.len == 0.f ? 0.f : -((g_dot3(gf, q.n) * inv) * inv) / q.len;
+            const float k = q.len == 0.f ? 0.f : -((dot3(gf, q.n) * inv) * inv) / q.len;
             const float gn[3] = {gf[0] * inv + q.n[0] * k, gf[1] * inv + q.n[1] * k, gf[2] * inv + q.n[2] * k};
             // n = e1 x e2:  d e1 = e2 x gn,  d e2 = gn x e1;  corner 1 receives d e1, corner 2 d e2, corner 0 minus both
             float ge1[3], ge2[3];
-            g_cross(q.e2, gn, ge1);
-            g_cross(gn, q.e1, ge2);
+            cross3(q.e2, gn, ge1);
+            cross3(gn, q.e1, ge2);
 #pragma unroll
             for (int j = 0; j < 3; ++j) c[j] = corner == 1 ? ge1[j] : (corner == 2 ? ge2[j] : -(ge1[j] + ge2[j]));
         }, s);
@@ -295,11 +264,11 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_gather_kernel(VertexStagePa
         if (has_model) transform<4>(x, m, w);
         else { w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3]; }
         if (P.g_world) {
-            const G4 t = *reinterpret_cast<const G4*>(P.g_world + row * 4);
+            const Float4 t = *reinterpret_cast<const Float4*>(P.g_world + row * 4);
             G[0] += t.x; G[1] += t.y; G[2] += t.z; G[3] += t.w;
         }
         if (P.g_clip) {   // clip = world4 @ vp
-            const G4 t = *reinterpret_cast<const G4*>(P.g_clip + row * 4);
+            const Float4 t = *reinterpret_cast<const Float4*>(P.g_clip + row * 4);
             gc[0] = t.x; gc[1] = t.y; gc[2] = t.z; gc[3] = t.w;
             float q[16];
             load_matrix(P.vp + (size_t)blockIdx.y * P.vp_stride, q);
@@ -312,7 +281,7 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_gather_kernel(VertexStagePa
             for (int r = 0; r < 4; ++r)
                 g[r] = has_model ? ((G[0] * m[4 * r] + G[1] * m[4 * r + 1]) + G[2] * m[4 * r + 2]) + G[3] * m[4 * r + 3] : G[r];
             float* __restrict__ o = P.gv + row * P.C;
-            *reinterpret_cast<G3*>(o) = G3{g[0], g[1], g[2]};
+            *reinterpret_cast<Float3*>(o) = Float3{g[0], g[1], g[2]};
             if (P.C == 4) o[3] = g[3];
         }
     }
@@ -323,53 +292,35 @@ __global__ __launch_bounds__(VS_BLOCK) void geometry_gather_kernel(VertexStagePa
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float a = geom_wave_sum(live ? x[r] * G[j] : 0.f), b = geom_wave_sum(live ? w[r] * gc[j] : 0.f);
+                const float a = wave_sum(live ? x[r] * G[j] : 0.f), b = wave_sum(live ? w[r] * gc[j] : 0.f);
                 if (lane == 0) { s_part[wave * VS_PARTIAL + 4 * r + j] = a; s_part[wave * VS_PARTIAL + 16 + 4 * r + j] = b; }
             }
         }
         __syncthreads();
-        if (tid < VS_PARTIAL) {
-            const float t = (s_part[tid] + s_part[VS_PARTIAL + tid]) + (s_part[2 * VS_PARTIAL + tid] + s_part[3 * VS_PARTIAL + tid]);
-            P.partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * VS_PARTIAL + tid] = t;
-        }
+        if (tid < VS_PARTIAL) fold_waves_to_row<VS_PARTIAL>(s_part, P.partial, tid);
     }
 }
 
-// ---- backward, last launch: the rows of partial sums added in a fixed order.  Workgroup (k, b) sums value k (0-15: d model,
+// ---- backward, last launch: the rows of partial sums added in a fixed order (block_column_sum).  Workgroup (k, b) sums value k (0-15: d model,
 // 16-31: d view_projection) of scene b -- or, for a matrix shared by the scenes, workgroup (k, 0) that of all of them
 __global__ __launch_bounds__(VS_BLOCK) void geometry_reduce_kernel(const float* __restrict__ partial, float* __restrict__ g_model, float* __restrict__ g_vp,
                                                                    int model_shared, int vp_shared, long long blocks, int B)
 {
     __shared__ float s_sum[VS_BLOCK];
-    const int tid = threadIdx.x, k = blockIdx.x, b = blockIdx.y;
+    const int k = blockIdx.x, b = blockIdx.y;
     float* __restrict__ out = k < 16 ? g_model : g_vp;
     const bool shared = k < 16 ? model_shared : vp_shared;
     if (!out || (shared && b != 0)) return;   // (uniform)
     const long long rows = shared ? blocks * B : blocks;
-    const float* __restrict__ base = partial + (size_t)b * blocks * VS_PARTIAL + k;
-    float s = 0.f;
-    for (long long r = tid; r < rows; r += VS_BLOCK) s += base[r * VS_PARTIAL];
-    s_sum[tid] = s;
-    __syncthreads();
-    for (int h = VS_BLOCK / 2; h > 0; h >>= 1) {
-        if (tid < h) s_sum[tid] += s_sum[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) out[(size_t)b * 16 + (k & 15)] = s_sum[0];
+    const float total = block_column_sum<VS_BLOCK>(partial + (size_t)b * blocks * VS_PARTIAL + k, rows, VS_PARTIAL, s_sum);
+    if (threadIdx.x == 0) out[(size_t)b * 16 + (k & 15)] = total;
 }
 
 }  // namespace dirt
 
 extern "C" {
 
-#define GEOM_FAIL(...) return dirt::set_last_error(DIRT_E_INVALID_ARGUMENT, __VA_ARGS__)
-#define GEOM_OK() dirt::set_last_error(DIRT_OK, "%s", "")
-
-static int geom_hip(const char* who, hipError_t e)
-{
-    if (e != hipSuccess) return dirt::set_last_error(DIRT_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return GEOM_OK();
-}
+static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
 static long long geom_blocks(long long V) { return (V + dirt::VS_BLOCK - 1) / dirt::VS_BLOCK; }
 
@@ -382,18 +333,18 @@ static int geom_check(const char* who, const float* vertices, int components, co
                       const float* model, int model_scenes, const float* view_projection, int vp_scenes, long long B, long long V, long long F,
                       unsigned flags, dirt::VertexStageParams& P)
 {
-    if (B < 0 || V < 0 || F < 0) GEOM_FAIL("%s: negative sizes (B=%lld V=%lld F=%lld)", who, B, V, F);
-    if (!geom_sizes_ok(B, V, F)) GEOM_FAIL("%s: B=%lld V=%lld F=%lld, at most 65535 scenes, %d vertices, %d faces", who, B, V, F,
-                                           DIRT_GEOM_MAX_VERTICES, DIRT_GEOM_MAX_FACES);
-    if (components != 3 && components != 4) GEOM_FAIL("%s: vertices have %d components, 3 or 4", who, components);
-    if (model_scenes != 0 && model_scenes != 1 && model_scenes != B) GEOM_FAIL("%s: model_scenes=%d is none of 0, 1, B=%lld", who, model_scenes, B);
-    if (vp_scenes != 0 && vp_scenes != 1 && vp_scenes != B) GEOM_FAIL("%s: view_projection_scenes=%d is none of 0, 1, B=%lld", who, vp_scenes, B);
-    if (flags & ~(DIRT_GEOM_PRE_SPLIT | DIRT_GEOM_LONG_LIST_MASK)) GEOM_FAIL("%s: unknown flags 0x%x", who, flags);
+    if (B < 0 || V < 0 || F < 0) STAGE_FAIL("%s: negative sizes (B=%lld V=%lld F=%lld)", who, B, V, F);
+    if (!geom_sizes_ok(B, V, F)) STAGE_FAIL("%s: B=%lld V=%lld F=%lld, at most 65535 scenes, %d vertices, %d faces", who, B, V, F,
+                                            DIRT_GEOM_MAX_VERTICES, DIRT_GEOM_MAX_FACES);
+    if (components != 3 && components != 4) STAGE_FAIL("%s: vertices have %d components, 3 or 4", who, components);
+    if (model_scenes != 0 && model_scenes != 1 && model_scenes != B) STAGE_FAIL("%s: model_scenes=%d is none of 0, 1, B=%lld", who, model_scenes, B);
+    if (vp_scenes != 0 && vp_scenes != 1 && vp_scenes != B) STAGE_FAIL("%s: view_projection_scenes=%d is none of 0, 1, B=%lld", who, vp_scenes, B);
+    if (flags & ~(DIRT_GEOM_PRE_SPLIT | DIRT_GEOM_LONG_LIST_MASK)) STAGE_FAIL("%s: unknown flags 0x%x", who, flags);
     if (B == 0 || V == 0) return DIRT_OK;
-    if (!vertices || !offsets) GEOM_FAIL("%s: vertices / offsets is NULL", who);
-    if (F > 0 && (!faces || !entries)) GEOM_FAIL("%s: faces / entries is NULL", who);
-    if ((model_scenes != 0) != (model != nullptr)) GEOM_FAIL("%s: model and model_scenes=%d disagree", who, model_scenes);
-    if ((vp_scenes != 0) != (view_projection != nullptr)) GEOM_FAIL("%s: view_projection and view_projection_scenes=%d disagree", who, vp_scenes);
+    if (!vertices || !offsets) STAGE_FAIL("%s: vertices / offsets is NULL", who);
+    if (F > 0 && (!faces || !entries)) STAGE_FAIL("%s: faces / entries is NULL", who);
+    if ((model_scenes != 0) != (model != nullptr)) STAGE_FAIL("%s: model and model_scenes=%d disagree", who, model_scenes);
+    if ((vp_scenes != 0) != (view_projection != nullptr)) STAGE_FAIL("%s: view_projection and view_projection_scenes=%d disagree", who, vp_scenes);
     P.v = vertices; P.faces = faces; P.offsets = offsets; P.entries = entries; P.model = model; P.vp = view_projection;
     P.V = (int)V; P.C = components;
     P.model_stride = model_scenes == 1 ? 0 : 16; P.vp_stride = vp_scenes == 1 ? 0 : 16;
@@ -418,12 +369,12 @@ int dirt_geometry_forward(const float* vertices, int components, const int32_t* 
     int rc = geom_check(who, vertices, components, faces, offsets, entries, model, model_scenes, view_projection, view_projection_scenes, B, V, F,
                         flags, P);
     if (rc) return rc;
-    if (B == 0 || V == 0 || (!clip && !world && !normals)) return GEOM_OK();
-    if (clip && !view_projection) GEOM_FAIL("%s: clip is wanted and there is no view_projection", who);
+    if (B == 0 || V == 0 || (!clip && !world && !normals)) return dirt::stage_ok(report);
+    if (clip && !view_projection) STAGE_FAIL("%s: clip is wanted and there is no view_projection", who);
     P.clip = clip; P.world = world; P.normals = normals;
     const dim3 grid((unsigned)geom_blocks(V), (unsigned)B);
     hipLaunchKernelGGL(dirt::geometry_forward_kernel, grid, dim3(dirt::VS_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
-    return geom_hip(who, hipGetLastError());
+    return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 int dirt_geometry_backward(const float* vertices, int components, const int32_t* faces, const int32_t* offsets, const int32_t* entries,
@@ -437,15 +388,14 @@ int dirt_geometry_backward(const float* vertices, int components, const int32_t*
     int rc = geom_check(who, vertices, components, faces, offsets, entries, model, model_scenes, view_projection, view_projection_scenes, B, V, F,
                         flags, P);
     if (rc) return rc;
-    if (B == 0 || V == 0 || (!grad_vertices && !grad_model && !grad_view_projection)) return GEOM_OK();
-    if (grad_clip && !view_projection) GEOM_FAIL("%s: grad_clip is given and there is no view_projection", who);
-    if (grad_model && !model) GEOM_FAIL("%s: grad_model is wanted and there is no model", who);
-    if (grad_view_projection && !view_projection) GEOM_FAIL("%s: grad_view_projection is wanted and there is no view_projection", who);
+    if (B == 0 || V == 0 || (!grad_vertices && !grad_model && !grad_view_projection)) return dirt::stage_ok(report);
+    if (grad_clip && !view_projection) STAGE_FAIL("%s: grad_clip is given and there is no view_projection", who);
+    if (grad_model && !model) STAGE_FAIL("%s: grad_model is wanted and there is no model", who);
+    if (grad_view_projection && !view_projection) STAGE_FAIL("%s: grad_view_projection is wanted and there is no view_projection", who);
     const bool mats = grad_model || grad_view_projection, sum_pass = grad_normals && !P.pre_split;
     if (mats || sum_pass) {
-        const size_t need = dirt_geometry_scratch_bytes(B, V, F);
-        if (!scratch || scratch_bytes < need) GEOM_FAIL("%s: scratch is NULL or smaller than dirt_geometry_scratch_bytes (%zu < %zu)", who, scratch_bytes, need);
-        if (reinterpret_cast<uintptr_t>(scratch) & 3u) GEOM_FAIL("%s: scratch is not 4-byte aligned", who);
+        rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_geometry_scratch_bytes(B, V, F), "dirt_geometry_scratch_bytes");
+        if (rc) return rc;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long blocks = geom_blocks(V);
@@ -459,18 +409,18 @@ int dirt_geometry_backward(const float* vertices, int components, const int32_t*
         P.g_sum = sums;
         hipLaunchKernelGGL(dirt::geometry_sum_grad_kernel, grid, dim3(dirt::VS_BLOCK), 0, s, P);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return geom_hip(who, e);
+        if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     }
     if (mats) hipLaunchKernelGGL(dirt::geometry_gather_kernel<true>, grid, dim3(dirt::VS_BLOCK), 0, s, P);
     else hipLaunchKernelGGL(dirt::geometry_gather_kernel<false>, grid, dim3(dirt::VS_BLOCK), 0, s, P);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return geom_hip(who, e);
+    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (mats) {
         hipLaunchKernelGGL(dirt::geometry_reduce_kernel, dim3(dirt::VS_PARTIAL, (unsigned)B), dim3(dirt::VS_BLOCK), 0, s, P.partial, grad_model,
                            grad_view_projection, model_scenes == 1 ? 1 : 0, view_projection_scenes == 1 ? 1 : 0, blocks, (int)B);
         e = hipGetLastError();
     }
-    return geom_hip(who, e);
+    return dirt::stage_hip(report, who, e);
 }
 
 }  // extern "C"

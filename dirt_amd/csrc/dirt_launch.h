@@ -123,7 +123,4 @@ hipError_t launch_grad(const GradParams& p, hipStream_t stream);
 hipError_t launch_grad_small(const GradParams& p, hipStream_t stream);  // dirt_grad_small.hip; p as filled by launch_grad
 hipError_t launch_grad_px2(const GradParams& p, hipStream_t stream);    // dirt_grad_px2.hip (two pixels per lane, 32 x 16 tiles); p as filled by launch_grad
 
-// sets the calling thread's dirt_last_error() text (printf-style; "" clears it) and returns `code` (dirt_capi.hip)
-int set_last_error(int code, const char* fmt, ...);
-
 }  // namespace dirt

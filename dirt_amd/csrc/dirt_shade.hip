@@ -27,9 +27,7 @@
 // atomics, and the same bits on every run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include "../../include/dirt_hip.h"
-#include "dirt_launch.h"
+#include "dirt_stage.h"
 
 namespace dirt {
 
@@ -51,16 +49,6 @@ struct ShadeParams {
     int clamp;
     float lo, hi;
 };
-
-struct V3 { float x, y, z; };   // three consecutive floats, 4-byte aligned: one 12-byte access
-
-__device__ __forceinline__ void load3(const float* __restrict__ p, float (&v)[3])
-{
-    const V3 t = *reinterpret_cast<const V3*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-
-__device__ __forceinline__ float dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 __device__ __forceinline__ float fold_cos(float c, bool ds) { return ds ? fabsf(c) : (c < 0.f ? 0.f : c); }
 
@@ -144,30 +132,9 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeParams 
 #pragma unroll
         for (int j = 0; j < 3; ++j) lit[j] += (L[3 + j] * px.c[j]) * f;
     }
-    V3 o;
     const float om = 1.f - px.m;
-    o.x = clamp_out(P, lit[0] * px.m + prm[3] * om);
-    o.y = clamp_out(P, lit[1] * px.m + prm[4] * om);
-    o.z = clamp_out(P, lit[2] * px.m + prm[5] * om);
-    *reinterpret_cast<V3*>(P.out + pix * 3) = o;
-}
-
-// ---- the sum of a value over the 64 lanes of a wave, in every lane: DPP adds inside the rows of 16, then the four rows
-template <int CTRL>
-__device__ __forceinline__ float shade_dpp(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += shade_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += shade_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += shade_dpp<0x141>(v);   // row_half_mirror: the other quad of the eight
-    v += shade_dpp<0x140>(v);   // row_mirror: the other eight of the row
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
+    const float o[3] = {clamp_out(P, lit[0] * px.m + prm[3] * om), clamp_out(P, lit[1] * px.m + prm[4] * om), clamp_out(P, lit[2] * px.m + prm[5] * om)};
+    store3(P.out + pix * 3, o);
 }
 
 // which value of a pixel's LDS row goes to channel `ch` of d gbuffer (10: the row's zero)
@@ -333,30 +300,19 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams
             if (lane == 0) s_part[wave * NP + k] = s;
         }
         __syncthreads();
-        if (tid < NP) {
-            const float s = (s_part[tid] + s_part[NP + tid]) + (s_part[2 * NP + tid] + s_part[3 * NP + tid]);
-            P.partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NP + tid] = s;
-        }
+        if (tid < NP) fold_waves_to_row<NP>(s_part, P.partial, tid);
     }
 }
 
 // ---- the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a fixed order:
-// workgroup (k, b) sums value k; lane t takes rows t, t + 256, ..., then the 256 lanes fold in LDS
+// workgroup (k, b) sums value k (block_column_sum)
 __global__ __launch_bounds__(SHADE_BLOCK) void shade_reduce_kernel(const float* __restrict__ partial, float* __restrict__ grad_params,
                                                                    long long rows, int NP)
 {
     __shared__ float s_sum[SHADE_BLOCK];
-    const int tid = threadIdx.x, k = blockIdx.x;
-    const float* __restrict__ base = partial + (size_t)blockIdx.y * rows * NP + k;
-    float s = 0.f;
-    for (long long r = tid; r < rows; r += SHADE_BLOCK) s += base[r * NP];
-    s_sum[tid] = s;
-    __syncthreads();
-    for (int h = SHADE_BLOCK / 2; h > 0; h >>= 1) {
-        if (tid < h) s_sum[tid] += s_sum[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) grad_params[(size_t)blockIdx.y * NP + k] = s_sum[0];
+    const int k = blockIdx.x;
+    const float total = block_column_sum<SHADE_BLOCK>(partial + (size_t)blockIdx.y * rows * NP + k, rows, NP, s_sum);
+    if (threadIdx.x == 0) grad_params[(size_t)blockIdx.y * NP + k] = total;
 }
 
 template <int NL>
@@ -371,14 +327,7 @@ void shade_launch_backward(const ShadeParams& P, bool params, bool gbuf, dim3 gr
 
 extern "C" {
 
-#define SHADE_FAIL(...) return dirt::set_last_error(DIRT_E_INVALID_ARGUMENT, __VA_ARGS__)
-#define SHADE_OK() dirt::set_last_error(DIRT_OK, "%s", "")
-
-static int shade_hip(const char* who, hipError_t e)
-{
-    if (e != hipSuccess) return dirt::set_last_error(DIRT_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SHADE_OK();
-}
+static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
 static long long shade_blocks(long long pixels) { return (pixels + dirt::SHADE_BLOCK * dirt::SHADE_ITER - 1) / (dirt::SHADE_BLOCK * dirt::SHADE_ITER); }
 
@@ -386,29 +335,29 @@ static int shade_check(const char* who, long long scenes, long long pixels, int 
                        int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned flags, float lo, float hi,
                        dirt::ShadeParams& P)
 {
-    if (scenes < 0 || pixels < 0) SHADE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
-    if (scenes > 65535) SHADE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
-    if (pixels > (1ll << 40)) SHADE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
-    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) SHADE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
-    if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) SHADE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_MAX_LIGHTS);
-    if (param_scenes != 1 && param_scenes != scenes) SHADE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
+    if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
+    if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
+    if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
+    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) STAGE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_MAX_LIGHTS);
+    if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
     const int off[4] = {off_colors, off_normals, off_positions, off_mask}, width[4] = {3, 3, 3, 1};
     const char* const names[4] = {"colors", "normals", "positions", "mask"};
     for (int a = 0; a < 4; ++a) {
         if (off[a] == -1 && a >= 2) continue;
-        if (off[a] < 0 || off[a] + width[a] > Cg) SHADE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
+        if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
         for (int b = 0; b < a; ++b)
             if (off[b] >= 0 && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
-                SHADE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
+                STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
     }
     for (int l = 0; l < lights; ++l) {
         const int kind = (light_kinds >> (2 * l)) & 3;
-        if (kind > DIRT_SHADE_DIFFUSE_POINT) SHADE_FAIL("%s: light %d has unknown kind %d", who, l, kind);
-        if (kind != DIRT_SHADE_DIFFUSE_DIRECTIONAL && off_positions < 0) SHADE_FAIL("%s: light %d needs positions, the G-buffer has none", who, l);
+        if (kind > DIRT_SHADE_DIFFUSE_POINT) STAGE_FAIL("%s: light %d has unknown kind %d", who, l, kind);
+        if (kind != DIRT_SHADE_DIFFUSE_DIRECTIONAL && off_positions < 0) STAGE_FAIL("%s: light %d needs positions, the G-buffer has none", who, l);
         if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL && !(flags & DIRT_SHADE_HAS_CAMERA))
-            SHADE_FAIL("%s: light %d is specular and needs a camera position (DIRT_SHADE_HAS_CAMERA)", who, l);
+            STAGE_FAIL("%s: light %d is specular and needs a camera position (DIRT_SHADE_HAS_CAMERA)", who, l);
     }
-    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) SHADE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
     P.pixels = pixels; P.Cg = Cg; P.oc = off_colors; P.on = off_normals; P.op = off_positions; P.om = off_mask; P.nl = lights;
     P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
     P.kinds = light_kinds; P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0; P.lo = lo; P.hi = hi;
@@ -430,13 +379,13 @@ int dirt_shade_forward(const float* gbuffer, const float* params, float* out, lo
     int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
                          clamp_lo, clamp_hi, P);
     if (rc) return rc;
-    if (scenes * pixels == 0) return SHADE_OK();
-    if (!gbuffer || !params || !out) SHADE_FAIL("%s: gbuffer / params / out is NULL", who);
-    if (pixels > 0x7fffffffll * dirt::SHADE_BLOCK) SHADE_FAIL("%s: too many pixels per scene", who);
+    if (scenes * pixels == 0) return dirt::stage_ok(report);
+    if (!gbuffer || !params || !out) STAGE_FAIL("%s: gbuffer / params / out is NULL", who);
+    if (pixels > 0x7fffffffll * dirt::SHADE_BLOCK) STAGE_FAIL("%s: too many pixels per scene", who);
     P.g = gbuffer; P.prm = params; P.out = out; P.dsided = double_sided;
     const dim3 grid((unsigned)((pixels + dirt::SHADE_BLOCK - 1) / dirt::SHADE_BLOCK), (unsigned)scenes);
     hipLaunchKernelGGL(dirt::shade_forward_kernel, grid, dim3(dirt::SHADE_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
-    return shade_hip(who, hipGetLastError());
+    return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 int dirt_shade_backward(const float* gbuffer, const float* params, const float* grad_out, float* grad_gbuffer, float* grad_params,
@@ -449,15 +398,14 @@ int dirt_shade_backward(const float* gbuffer, const float* params, const float* 
     int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
                          clamp_lo, clamp_hi, P);
     if (rc) return rc;
-    if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params)) return SHADE_OK();
-    if (!gbuffer || !params || !grad_out) SHADE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
+    if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params)) return dirt::stage_ok(report);
+    if (!gbuffer || !params || !grad_out) STAGE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
     if (grad_params) {
-        const size_t need = dirt_shade_scratch_bytes(scenes, pixels, lights);
-        if (!scratch || scratch_bytes < need) SHADE_FAIL("%s: scratch is NULL or smaller than dirt_shade_scratch_bytes (%zu < %zu)", who, scratch_bytes, need);
-        if (reinterpret_cast<uintptr_t>(scratch) & 3u) SHADE_FAIL("%s: scratch is not 4-byte aligned", who);
+        rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_shade_scratch_bytes(scenes, pixels, lights), "dirt_shade_scratch_bytes");
+        if (rc) return rc;
     }
     const long long blocks = shade_blocks(pixels);
-    if (blocks > 0x7fffffffll) SHADE_FAIL("%s: too many pixels per scene", who);
+    if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
     P.g = gbuffer; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.partial = static_cast<float*>(scratch); P.dsided = double_sided;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)blocks, (unsigned)scenes);
@@ -474,7 +422,7 @@ int dirt_shade_backward(const float* gbuffer, const float* params, const float* 
     default: dirt::shade_launch_backward<8>(P, params_wanted, gbuf, grid, s); break;
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return shade_hip(who, e);
+    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (params_wanted) {
         const int NP = DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
         const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
@@ -482,7 +430,7 @@ int dirt_shade_backward(const float* gbuffer, const float* params, const float* 
                            static_cast<const float*>(scratch), grad_params, rows, NP);
         e = hipGetLastError();
     }
-    return shade_hip(who, e);
+    return dirt::stage_hip(report, who, e);
 }
 
 }  // extern "C"

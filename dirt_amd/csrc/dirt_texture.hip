@@ -10,7 +10,6 @@
 // last texel -- the last texel is used.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/dirt_hip.h"
 #include "dirt_texture_common.h"
 
 namespace dirt {
@@ -166,13 +165,10 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
 hipError_t launch_texture_forward(const TexParams& p, hipStream_t stream)
 {
     if (p.n == 0) return hipSuccess;
-    long long blocks = (p.n + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.texture) & 15u) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15u) == 0;
-    if (p.Ct == 4 && a16) hipLaunchKernelGGL(texture_forward_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    else if (p.Ct == 3) hipLaunchKernelGGL(texture_forward_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    else if (p.Ct == 1) hipLaunchKernelGGL(texture_forward_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(texture_forward_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    dispatch_channels(p.Ct, a16, [&](auto ct) {
+        hipLaunchKernelGGL(texture_forward_kernel<decltype(ct)::value>, dim3(capped_blocks(p.n)), dim3(256), 0, stream, p);
+    });
     return hipGetLastError();
 }
 
@@ -185,69 +181,65 @@ hipError_t launch_texture_backward(const TexParams& p, long long rows, long long
     if (tiles_x * tiles_y > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
     const bool a16 = (reinterpret_cast<uintptr_t>(p.grad_out) & 15u) == 0;
-    if (p.Ct == 4 && a16) hipLaunchKernelGGL(texture_backward_kernel<4>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
-    else if (p.Ct == 3) hipLaunchKernelGGL(texture_backward_kernel<3>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
-    else if (p.Ct == 1) hipLaunchKernelGGL(texture_backward_kernel<1>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
-    else hipLaunchKernelGGL(texture_backward_kernel<0>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
+    dispatch_channels(p.Ct, a16, [&](auto ct) {
+        hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
+    });
     return hipGetLastError();
+}
+
+namespace {
+thread_local char g_tex_error[256] = "";
+}
+
+// dirt_texture_last_error()'s text, for this file and dirt_texture_mip.hip
+int set_texture_error(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    format_error(g_tex_error, sizeof(g_tex_error), fmt, ap);
+    va_end(ap);
+    return code;
 }
 
 }  // namespace dirt
 
 extern "C" {
 
-namespace {
-thread_local char g_tex_error[256] = "";
-}
-const char* dirt_texture_last_error(void) { return g_tex_error; }
+static constexpr dirt::ErrorSetter report = dirt::set_texture_error;   // the error channel of this file's entry points
+
+const char* dirt_texture_last_error(void) { return dirt::g_tex_error; }
 
 static int tex_check(const char* who, const void* texture, const void* uvs, long long n, int Ht, int Wt, int Ct, int uv_stride)
 {
-    if (n < 0 || Ht <= 0 || Wt <= 0 || Ct <= 0 || uv_stride < 2) {
-        snprintf(g_tex_error, sizeof(g_tex_error), "%s: bad sizes (n=%lld Ht=%d Wt=%d Ct=%d uv_stride=%d)", who, n, Ht, Wt, Ct, uv_stride);
-        return DIRT_E_INVALID_ARGUMENT;
-    }
-    if (n > 0 && (!texture || !uvs)) {
-        snprintf(g_tex_error, sizeof(g_tex_error), "%s: texture / uvs is NULL", who);
-        return DIRT_E_INVALID_ARGUMENT;
-    }
+    if (n < 0 || Ht <= 0 || Wt <= 0 || Ct <= 0 || uv_stride < 2)
+        TEX_FAIL("%s: bad sizes (n=%lld Ht=%d Wt=%d Ct=%d uv_stride=%d)", who, n, Ht, Wt, Ct, uv_stride);
+    if (n > 0 && (!texture || !uvs)) TEX_FAIL("%s: texture / uvs is NULL", who);
     return DIRT_OK;
 }
 
 int dirt_texture_sample_forward(const float* texture, const float* uvs, float* out, long long n, int Ht, int Wt, int Ct, int uv_stride,
                                 unsigned flags, void* stream)
 {
-    int rc = tex_check("dirt_texture_sample_forward", texture, uvs, n, Ht, Wt, Ct, uv_stride);
+    const char* who = "dirt_texture_sample_forward";
+    int rc = tex_check(who, texture, uvs, n, Ht, Wt, Ct, uv_stride);
     if (rc) return rc;
-    if (n > 0 && !out) { snprintf(g_tex_error, sizeof(g_tex_error), "dirt_texture_sample_forward: out is NULL"); return DIRT_E_INVALID_ARGUMENT; }
+    if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
     dirt::TexParams p{};
     p.texture = texture; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.flags = flags; p.out = out;
-    const hipError_t e = dirt::launch_texture_forward(p, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { snprintf(g_tex_error, sizeof(g_tex_error), "dirt_texture_sample_forward: %s", hipGetErrorString(e)); return DIRT_E_HIP; }
-    g_tex_error[0] = 0;
-    return DIRT_OK;
+    return dirt::stage_hip(report, who, dirt::launch_texture_forward(p, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int dirt_texture_sample_backward_image(const float* texture, const float* uvs, const float* grad_out, float* grad_texture, float* grad_uvs,
                                        long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride, int grad_uv_stride, unsigned flags,
                                        void* stream)
 {
-    const char* who = "dirt_texture_sample_backward";
-    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) {
-        snprintf(g_tex_error, sizeof(g_tex_error), "%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
-        return DIRT_E_INVALID_ARGUMENT;
-    }
+    const char* who = "dirt_texture_sample_backward";   // (the flat-list entry point's name: it forwards here)
+    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) TEX_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
     const long long n = rows * cols;
     int rc = tex_check(who, texture, uvs, n, Ht, Wt, Ct, uv_stride);
     if (rc) return rc;
-    if (n > 0 && (!grad_out || !grad_texture)) {
-        snprintf(g_tex_error, sizeof(g_tex_error), "%s: grad_out / grad_texture is NULL", who);
-        return DIRT_E_INVALID_ARGUMENT;
-    }
-    if (grad_uvs && grad_uv_stride < 2) {
-        snprintf(g_tex_error, sizeof(g_tex_error), "%s: grad_uv_stride < 2", who);
-        return DIRT_E_INVALID_ARGUMENT;
-    }
+    if (n > 0 && (!grad_out || !grad_texture)) TEX_FAIL("%s: grad_out / grad_texture is NULL", who);
+    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(grad_texture, 0, sizeof(float) * (size_t)Ht * Wt * Ct, s);
     if (e == hipSuccess) {
@@ -256,9 +248,7 @@ int dirt_texture_sample_backward_image(const float* texture, const float* uvs, c
         p.flags = flags; p.grad_out = grad_out; p.grad_texture = grad_texture; p.grad_uvs = grad_uvs;
         e = dirt::launch_texture_backward(p, rows, cols, s);
     }
-    if (e != hipSuccess) { snprintf(g_tex_error, sizeof(g_tex_error), "%s: %s", who, hipGetErrorString(e)); return DIRT_E_HIP; }
-    g_tex_error[0] = 0;
-    return DIRT_OK;
+    return dirt::stage_hip(report, who, e);
 }
 
 int dirt_texture_sample_backward(const float* texture, const float* uvs, const float* grad_out, float* grad_texture, float* grad_uvs,

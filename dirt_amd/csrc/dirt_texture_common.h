@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dirt_stage.h"
 
 namespace dirt {
 
@@ -26,22 +27,20 @@ __device__ __forceinline__ void uv_to_index(float u, float v, int Ht, int Wt, bo
     }
 }
 
-struct Tex3 { float x, y, z; };   // a 3-channel texel / pixel: one 12-byte access
-
 // One texel / output pixel of CT channels as a register array, with the widest access its size and alignment allow
 // (CT = 4: 16 bytes; 3: 12; 1: 4; 0: any count `ct`, channel by channel).
 template <int CT>
 __device__ __forceinline__ void load_ch(const float* __restrict__ p, int ct, float (&v)[CT ? CT : 1], int ch0 = 0)
 {
     if constexpr (CT == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-    else if constexpr (CT == 3) { const Tex3 q = *reinterpret_cast<const Tex3*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; }
+    else if constexpr (CT == 3) load3(p, v);
     else v[0] = p[ch0];
 }
 template <int CT>
 __device__ __forceinline__ void store_ch(float* __restrict__ p, const float (&v)[CT ? CT : 1], int ch0 = 0)
 {
     if constexpr (CT == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else if constexpr (CT == 3) *reinterpret_cast<Tex3*>(p) = Tex3{v[0], v[1], v[2]};
+    else if constexpr (CT == 3) store3(p, v);
     else p[ch0] = v[0];
 }
 

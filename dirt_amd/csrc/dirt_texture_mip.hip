@@ -33,8 +33,6 @@
 // atomics into the scratch pyramid where the footprint does not fit; then the collapse.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include "../../include/dirt_hip.h"
 #include "dirt_texture_common.h"
 
 namespace dirt {
@@ -443,34 +441,26 @@ void mip_offsets(MipParams& p)
 
 extern "C" {
 
-static char* mip_err() { return const_cast<char*>(dirt_texture_last_error()); }   // dirt_texture.hip's thread-local message
-#define MIP_FAIL(...) do { snprintf(mip_err(), 256, __VA_ARGS__); return DIRT_E_INVALID_ARGUMENT; } while (0)
+static constexpr dirt::ErrorSetter report = dirt::set_texture_error;   // the error channel of this file's entry points
 
 int dirt_texture_mip_levels(int Ht, int Wt, int Ct, int max_level, long long* pyramid_floats)
 {
-    if (Ht <= 0 || Wt <= 0 || Ct <= 0) MIP_FAIL("dirt_texture_mip_levels: bad sizes (Ht=%d Wt=%d Ct=%d)", Ht, Wt, Ct);
+    if (Ht <= 0 || Wt <= 0 || Ct <= 0) TEX_FAIL("dirt_texture_mip_levels: bad sizes (Ht=%d Wt=%d Ct=%d)", Ht, Wt, Ct);
     dirt::MipParams p{};
     p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.L = dirt::mip_level_count(Ht, Wt, max_level);
     dirt::mip_offsets(p);
     if (pyramid_floats) *pyramid_floats = p.L < dirt::MIP_MAX ? p.off[p.L] : p.off[p.L - 1] + (long long)dirt::mip_dim(Ht, p.L - 1) * dirt::mip_dim(Wt, p.L - 1) * Ct;
-    mip_err()[0] = 0;
+    dirt::stage_ok(report);
     return p.L;
 }
 
 static int mip_check(const char* who, int Ht, int Wt, int Ct, int levels, dirt::MipParams& p)
 {
-    if (Ht <= 0 || Wt <= 0 || Ct <= 0) MIP_FAIL("%s: bad sizes (Ht=%d Wt=%d Ct=%d)", who, Ht, Wt, Ct);
+    if (Ht <= 0 || Wt <= 0 || Ct <= 0) TEX_FAIL("%s: bad sizes (Ht=%d Wt=%d Ct=%d)", who, Ht, Wt, Ct);
     if (levels < 1 || levels > dirt::mip_level_count(Ht, Wt, -1))
-        MIP_FAIL("%s: %d levels, a %d x %d texture has 1..%d", who, levels, Ht, Wt, dirt::mip_level_count(Ht, Wt, -1));
+        TEX_FAIL("%s: %d levels, a %d x %d texture has 1..%d", who, levels, Ht, Wt, dirt::mip_level_count(Ht, Wt, -1));
     p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.L = levels;
     dirt::mip_offsets(p);
-    return DIRT_OK;
-}
-
-static int mip_hip(const char* who, hipError_t e)
-{
-    if (e != hipSuccess) { snprintf(mip_err(), 256, "%s: %s", who, hipGetErrorString(e)); return DIRT_E_HIP; }
-    mip_err()[0] = 0;
     return DIRT_OK;
 }
 
@@ -480,15 +470,16 @@ int dirt_texture_mip_build(const float* texture, float* pyramid, int Ht, int Wt,
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
-    if (!texture || !pyramid) MIP_FAIL("%s: texture / pyramid is NULL", who);
+    if (!texture || !pyramid) TEX_FAIL("%s: texture / pyramid is NULL", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (levels == 1) return mip_hip(who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct, hipMemcpyDeviceToDevice, s));
+    if (levels == 1)
+        return dirt::stage_hip(report, who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct, hipMemcpyDeviceToDevice, s));
     const int kt = min(levels - 1, dirt::MIP_TILE_LEVELS);
     const int tiles_y = dirt::mip_dim(Ht, kt), tiles_x = dirt::mip_dim(Wt, kt);
-    if ((long long)tiles_x * tiles_y > 0x7fffffffll) MIP_FAIL("%s: texture too large", who);
+    if ((long long)tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: texture too large", who);
     hipLaunchKernelGGL(dirt::mip_build_blocks_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
     if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel, dim3(1), dim3(1024), 0, s, pyramid, p, kt);
-    return mip_hip(who, hipGetLastError());
+    return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
@@ -497,12 +488,10 @@ int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, in
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
-    if (!grad_pyramid || !grad_texture) MIP_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
+    if (!grad_pyramid || !grad_texture) TEX_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
     const long long n = (long long)Ht * Wt * Ct;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(dirt::mip_collapse_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), grad_pyramid, grad_texture, p);
-    return mip_hip(who, hipGetLastError());
+    hipLaunchKernelGGL(dirt::mip_collapse_kernel, dim3(dirt::capped_blocks(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), grad_pyramid, grad_texture, p);
+    return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 static int mip_sample_check(const char* who, const float* pyramid, const float* uvs, const float* lod, long long rows, long long cols,
@@ -511,11 +500,11 @@ static int mip_sample_check(const char* who, const float* pyramid, const float* 
 {
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
-    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) MIP_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
-    if (image_rows < 1 || (rows > 0 && rows % image_rows)) MIP_FAIL("%s: image_rows=%d does not divide rows=%lld", who, image_rows, rows);
-    if (uv_stride < 2) MIP_FAIL("%s: uv_stride < 2", who);
-    if (mask && mask_stride < 1) MIP_FAIL("%s: mask_stride < 1", who);
-    if (rows * cols > 0 && (!pyramid || !uvs)) MIP_FAIL("%s: pyramid / uvs is NULL", who);
+    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) TEX_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
+    if (image_rows < 1 || (rows > 0 && rows % image_rows)) TEX_FAIL("%s: image_rows=%d does not divide rows=%lld", who, image_rows, rows);
+    if (uv_stride < 2) TEX_FAIL("%s: uv_stride < 2", who);
+    if (mask && mask_stride < 1) TEX_FAIL("%s: mask_stride < 1", who);
+    if (rows * cols > 0 && (!pyramid || !uvs)) TEX_FAIL("%s: pyramid / uvs is NULL", who);
     p.pyr = pyramid; p.uvs = uvs; p.lod = lod; p.mask = lod ? nullptr : mask; p.rows = rows; p.cols = cols; p.image_rows = image_rows;
     p.uv_stride = uv_stride; p.mask_stride = mask_stride;
     return DIRT_OK;
@@ -529,20 +518,17 @@ int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, cons
     dirt::MipParams p{};
     int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
     if (rc) return rc;
-    if (flags & DIRT_TEX_NEAREST) MIP_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
+    if (flags & DIRT_TEX_NEAREST) TEX_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
     const long long n = rows * cols;
-    if (n > 0 && !out) MIP_FAIL("%s: out is NULL", who);
-    if (n == 0) { mip_err()[0] = 0; return DIRT_OK; }
+    if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
+    if (n == 0) return dirt::stage_ok(report);
     p.lod_bias = lod_bias; p.flags = flags; p.out = out;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 256 * 64) blocks = 256 * 64;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-    if (Ct == 4 && a16) hipLaunchKernelGGL(dirt::mip_forward_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (Ct == 3) hipLaunchKernelGGL(dirt::mip_forward_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (Ct == 1) hipLaunchKernelGGL(dirt::mip_forward_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(dirt::mip_forward_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return mip_hip(who, hipGetLastError());
+    dirt::dispatch_channels(Ct, a16, [&](auto ct) {
+        hipLaunchKernelGGL(dirt::mip_forward_kernel<decltype(ct)::value>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, p);
+    });
+    return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
@@ -554,30 +540,29 @@ int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, con
     dirt::MipParams p{};
     int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
     if (rc) return rc;
-    if (flags & DIRT_TEX_NEAREST) MIP_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
-    if (!grad_pyramid || !grad_texture) MIP_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
+    if (flags & DIRT_TEX_NEAREST) TEX_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
+    if (!grad_pyramid || !grad_texture) TEX_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
     const long long n = rows * cols;
-    if (n > 0 && !grad_out) MIP_FAIL("%s: grad_out is NULL", who);
-    if (grad_uvs && grad_uv_stride < 2) MIP_FAIL("%s: grad_uv_stride < 2", who);
-    if (grad_lod && !lod) MIP_FAIL("%s: grad_lod needs lod", who);
+    if (n > 0 && !grad_out) TEX_FAIL("%s: grad_out is NULL", who);
+    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
+    if (grad_lod && !lod) TEX_FAIL("%s: grad_lod needs lod", who);
     p.lod_bias = lod_bias; p.flags = flags; p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod;
     p.guv_stride = grad_uv_stride;
     const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
     const long long tiles_x = (cols + tw - 1) / tw, tiles_y = (rows + th - 1) / th;
-    if (tiles_x * tiles_y > 0x7fffffffll) MIP_FAIL("%s: pixel grid too large", who);
+    if (tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long pyr_floats = p.off[levels - 1] + (long long)dirt::mip_dim(Ht, levels - 1) * dirt::mip_dim(Wt, levels - 1) * Ct;
     hipError_t e = hipMemsetAsync(grad_pyramid, 0, sizeof(float) * (size_t)pyr_floats, s);
-    if (e != hipSuccess) return mip_hip(who, e);
+    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (n > 0) {
         const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
         const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
-        if (Ct == 4 && a16) hipLaunchKernelGGL(dirt::mip_backward_kernel<4>, grid, block, 0, s, p, tw, th, (int)tiles_x);
-        else if (Ct == 3) hipLaunchKernelGGL(dirt::mip_backward_kernel<3>, grid, block, 0, s, p, tw, th, (int)tiles_x);
-        else if (Ct == 1) hipLaunchKernelGGL(dirt::mip_backward_kernel<1>, grid, block, 0, s, p, tw, th, (int)tiles_x);
-        else hipLaunchKernelGGL(dirt::mip_backward_kernel<0>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        dirt::dispatch_channels(Ct, a16, [&](auto ct) {
+            hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+        });
         e = hipGetLastError();
-        if (e != hipSuccess) return mip_hip(who, e);
+        if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     }
     return dirt_texture_mip_collapse(grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
 }

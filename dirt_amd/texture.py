@@ -51,6 +51,13 @@ def sample_texture(texture, indices, mode='bilinear'):
     raise NotImplementedError(mode)
 
 
+def _check(rc):
+    """A return code of a texture entry point -> ValueError with dirt_texture_last_error()'s text.  Every non-zero code, DIRT_E_HIP
+    included: _lib.check raises RuntimeError for that one, and following it here would change what callers catch."""
+    if rc:
+        raise ValueError(_lib.load().dirt_texture_last_error().decode())
+
+
 def _pairs_in_place(uvs):
     """(tensor to pass, element stride between pairs) such that pair i starts at data_ptr + 4 * i * stride: a slice
     `gbuffer[..., a:a+2]` of a contiguous G-buffer is read in place, anything else is made contiguous."""
@@ -82,8 +89,7 @@ class _SampleTextureUV(torch.autograd.Function):
         with _ops._on_device(texture.device):
             rc = lib.dirt_texture_sample_forward(texture.data_ptr(), src.data_ptr(), out.data_ptr(), n, ht, wt, ct, stride, flags,
                                                  _ops._stream_handle(texture.device))
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         ctx.save_for_backward(texture, src)
         ctx.meta = (stride, flags, tuple(uvs.shape))
         return out
@@ -109,8 +115,7 @@ class _SampleTextureUV(torch.autograd.Function):
             rc = lib.dirt_texture_sample_backward_image(texture.data_ptr(), src.data_ptr(), grad_out.data_ptr(), grad_texture.data_ptr(),
                                                         grad_uvs.data_ptr() if grad_uvs is not None else None, rows, cols, ht, wt, ct, stride, 2,
                                                         flags, _ops._stream_handle(texture.device))
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         return grad_texture, grad_uvs, None
 
 
@@ -147,8 +152,7 @@ def _mip_geometry(ht, wt, ct, max_level):
     lib = _lib.load()
     floats = ctypes.c_longlong(0)
     levels = lib.dirt_texture_mip_levels(ht, wt, ct, -1 if max_level is None else max_level, ctypes.byref(floats))
-    if levels < 1:
-        raise ValueError(lib.dirt_texture_last_error().decode())
+    _check(min(levels, 0))   # a level count (>= 1), or an error code
     geo, off = [], 0
     for k in range(levels):
         h, w = max(ht >> k, 1), max(wt >> k, 1)
@@ -174,8 +178,7 @@ class _MipPyramid(torch.autograd.Function):
         pyr = torch.empty(floats, dtype=torch.float32, device=texture.device)
         with _ops._on_device(texture.device):
             rc = lib.dirt_texture_mip_build(texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(texture.device))
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         ctx.meta = (ht, wt, ct, levels)
         return pyr
 
@@ -188,8 +191,7 @@ class _MipPyramid(torch.autograd.Function):
         grad_texture = torch.empty((ht, wt, ct), dtype=torch.float32, device=grad_pyr.device)
         with _ops._on_device(grad_pyr.device):
             rc = lib.dirt_texture_mip_collapse(grad_pyr.data_ptr(), grad_texture.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(grad_pyr.device))
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         return grad_texture, None, None
 
 
@@ -244,8 +246,7 @@ class _SampleTextureMip(torch.autograd.Function):
                 rc = lib.dirt_texture_sample_mip_forward(pyr.data_ptr(), src.data_ptr(), lod_t.data_ptr() if lod_t is not None else None,
                                                          mask_t.data_ptr() if mask_t is not None else None, out.data_ptr(), rows, cols,
                                                          image_rows, ht, wt, ct, levels, stride, mask_stride, float(lod_bias), flags, stream)
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         ctx.save_for_backward(pyr, src, lod_t, mask_t)
         ctx.meta = (stride, mask_stride, flags, float(lod_bias), tuple(uvs.shape), rows, cols, image_rows, ht, wt, ct, levels, floats)
         return out
@@ -268,8 +269,7 @@ class _SampleTextureMip(torch.autograd.Function):
                                                       grad_texture.data_ptr(), grad_uvs.data_ptr() if grad_uvs is not None else None,
                                                       grad_lod.data_ptr() if grad_lod is not None else None, rows, cols, image_rows,
                                                       ht, wt, ct, levels, stride, 2, mask_stride, lod_bias, flags, _ops._stream_handle(dev))
-        if rc:
-            raise ValueError(lib.dirt_texture_last_error().decode())
+        _check(rc)
         return grad_texture, grad_uvs, grad_lod, None, None, None, None
 
 

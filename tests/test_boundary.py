@@ -91,6 +91,45 @@ def test_error_codes_before_any_device_work(lib):
     assert lib.dirt_rasterise_forward(None, None, None, None, None, 0, 3, 1, 8, 8, 3, None, 0, 0, None) == 0
 
 
+def test_the_two_error_channels_stay_separate_and_bounded(lib):
+    """dirt_last_error() (rasteriser, shade, geometry) and dirt_texture_last_error() (texture, mip) are two thread-local
+    buffers: a refused call writes its own and leaves the other as it was, and the texture buffer (256 bytes) is never
+    overrun.  Its longest messages -- a pixel grid and a size check of extreme values -- stay whole and below the buffer's
+    size: no format of that channel can reach it, so what is pinned is the text and the bound."""
+    from dirt_amd import _lib
+    one = ctypes.c_void_p(16)   # never dereferenced: validation fails first
+    err, tex_err = lib.dirt_last_error, lib.dirt_texture_last_error
+
+    def shade_refused():   # -1 scenes
+        return lib.dirt_shade_forward(one, one, one, -1, 64, 10, 4, 7, 1, 0, 1, 0, 0, 0, 0., 1., 0, None)
+
+    def mip_refused():     # an 8 x 8 texture has 1..4 levels
+        return lib.dirt_texture_mip_build(one, one, 8, 8, 3, 9, None)
+
+    assert mip_refused() == _lib.E_INVALID_ARGUMENT
+    tex_before = tex_err()
+    assert tex_before.startswith(b'dirt_texture_mip_build') and b'levels' in tex_before
+    assert shade_refused() == _lib.E_INVALID_ARGUMENT
+    shade_text = err()
+    assert shade_text.startswith(b'dirt_shade_forward') and b'negative sizes' in shade_text
+    assert tex_err() == tex_before
+
+    assert lib.dirt_texture_mip_collapse(one, one, 0, 8, 3, 1, None) == _lib.E_INVALID_ARGUMENT
+    assert tex_err().startswith(b'dirt_texture_mip_collapse') and b'bad sizes' in tex_err()
+    assert err() == shade_text
+
+    lo = -(1 << 63)
+    rc = lib.dirt_texture_sample_mip_backward(one, one, None, None, one, one, one, one, None, lo, lo, 1, 8, 8, 3, 4, 2, 2, 1, 0.0, 0, None)
+    assert rc == _lib.E_INVALID_ARGUMENT
+    assert tex_err() == b'dirt_texture_sample_mip_backward: bad pixel grid (rows=%d cols=%d)' % (lo, lo)
+    assert len(tex_err()) < 256
+    big = -(1 << 31)
+    assert lib.dirt_texture_sample_forward(one, one, one, lo, big, big, big, big, 0, None) == _lib.E_INVALID_ARGUMENT
+    assert tex_err() == b'dirt_texture_sample_forward: bad sizes (n=%d Ht=%d Wt=%d Ct=%d uv_stride=%d)' % (lo, big, big, big, big)
+    assert len(tex_err()) < 256
+    assert err() == shade_text
+
+
 def test_python_api_mirrors_the_reference_signatures():
     """dirt/rasterise_ops.py:13,51,260,313 and dirt/__init__.py:2."""
     import dirt_amd
