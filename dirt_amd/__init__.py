@@ -7,4 +7,6 @@ from . import texture  # noqa: F401  (the texture helpers of samples/textured.py
 from . import shading  # noqa: F401  (the fused G-buffer lighting of samples/deferred.py's shader)
 from . import geometry  # noqa: F401  (the fused vertex stage in front of the rasteriser: transforms and vertex normals)
 from .geometry import MeshTopology, vertex_stage  # noqa: F401
+from . import skinning  # noqa: F401  (fused linear-blend skinning in front of the vertex stage: a blend of bone matrices per vertex)
+from .skinning import SkinWeights, skin_vertices  # noqa: F401
 from .graphed import GraphedStep, backward  # noqa: F401  (a training step captured once as a HIP graph: the remedy for eager autograd's host cost)

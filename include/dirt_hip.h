@@ -357,6 +357,50 @@ int dirt_geometry_backward(const float *vertices, int components, const int32_t 
                            void *stream);
 
 /*
+ * Linear-blend skinning in front of the vertex stage, fused.  Extends what the reference's samples do with one matrix
+ * for the whole mesh (samples/deferred.py:40-41: one `model` transform per scene) to a per-vertex blend of bone
+ * matrices; specification in dirt_amd/csrc/dirt_skin.hip and DESIGN.md §7d.  Per scene, row vectors:
+ *     M[v] = sum over k in slot order of bone_weights[v, k] * transforms[bone_indices[v, k]],   posed[v] = (v4 @ M[v])[:3]
+ *   vertices [vertex_scenes, V, components], components = 3 (w = 1 is appended) or 4, 4-byte alignment suffices;
+ *   vertex_scenes = 1 (one rest mesh for every scene) or B.
+ *   bone_indices int32 [V, K], bone_weights [V, K], 1 <= K <= DIRT_SKIN_MAX_INFLUENCES: one table for every scene.  Weights
+ *   are taken as given (nothing is renormalised; a zero weight is padding; a vertex may name a bone in two slots).
+ *   transforms [transform_scenes, J, 4, 4] row-major (translation in row 3), transform_scenes = 1 or B, J <=
+ *   DIRT_SKIN_MAX_BONES.  Column 3 is never read.  Up to DIRT_SKIN_LDS_BONES bones a workgroup stages the scene's 4x3
+ *   blocks in LDS (12 KB); with more they are read through the caches.
+ *   posed [B, V, 3]; NULL: nothing is computed.
+ * One launch, no atomics.  B or V equal to 0: success, nothing is launched.  flags: none defined, must be 0.
+ * Backward: grad_posed [B, V, 3] -> grad_vertices (shaped like vertices), grad_transforms (shaped like transforms, column
+ * 3 written as zero, a bone no vertex names all zero) and grad_weights [V, K]; each may be NULL and is then not computed;
+ * those given are fully written, an operand shared by the scenes receiving the sum over the scenes.  grad_transforms
+ * needs the inverted index of bone_indices (dirt_amd.skinning.SkinWeights builds it):
+ *   entries [V K]: the positions v * K + k, ordered by bone, then position;
+ *   chunk_table [chunks, 3]: (bone, begin, end) -- every bone's run of `entries` cut into pieces of a fixed number of
+ *   entries, none spanning two bones, ordered by bone, then begin; chunks <= DIRT_SKIN_MAX_CHUNKS;
+ *   chunk_offsets [J + 1]: the chunks of bone j are chunk_offsets[j] .. chunk_offsets[j + 1]);
+ * and `scratch`, caller-owned, of dirt_skin_scratch_bytes(B, chunks) = 4 * 12 * B * chunks bytes (0: invalid sizes): one
+ * row of partial sums per (scene, chunk), added by a second launch in a fixed order.  The kernels trust the index arrays:
+ * every bone index must lie inside [0, J), every entry inside [0, V K).  At most 4 launches; no atomics, the same bits on
+ * every run.  Failures: dirt_last_error().
+ */
+#define DIRT_SKIN_MAX_INFLUENCES 8
+#define DIRT_SKIN_MAX_BONES 65536
+#define DIRT_SKIN_LDS_BONES 256
+#define DIRT_SKIN_MAX_VERTICES (1 << 28)
+#define DIRT_SKIN_MAX_ENTRIES (1 << 30) /* V K: the positions v * K + k and the kernels' entry counters are int32 */
+#define DIRT_SKIN_MAX_CHUNKS 0x7fffffff
+size_t dirt_skin_scratch_bytes(long long B, long long chunks);
+int dirt_skin_forward(const float *vertices, int components, int vertex_scenes, const int32_t *bone_indices,
+                      const float *bone_weights, const float *transforms, int transform_scenes, float *posed, long long B,
+                      long long V, int K, int J, unsigned flags, void *stream);
+int dirt_skin_backward(const float *vertices, int components, int vertex_scenes, const int32_t *bone_indices,
+                       const float *bone_weights, const float *transforms, int transform_scenes, const int32_t *entries,
+                       const int32_t *chunk_table, const int32_t *chunk_offsets, const float *grad_posed,
+                       float *grad_vertices, float *grad_transforms, float *grad_weights, void *scratch,
+                       size_t scratch_bytes, long long B, long long V, int K, int J, long long chunks, unsigned flags,
+                       void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
