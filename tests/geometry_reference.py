@@ -57,6 +57,14 @@ def fan_mesh(rng, blades=2000):
     """One vertex in `blades` faces: a pinwheel of well-shaped triangles that share vertex 0 and nothing else (they overlap
     in space, which the vertex stage does not mind), all wound the same way so that the hub's normal is a long sum.
     -> (vertices [1 + 2 blades, 3], faces [blades, 3])"""
+    v = np.concatenate([np.zeros((1, 3)), _pinwheel_rim(rng, blades).reshape(-1, 3)]).astype(np.float32)
+    b = np.arange(blades)
+    return v, np.stack([np.zeros_like(b), 1 + 2 * b, 2 + 2 * b], 1).astype(np.int32)
+
+
+def _pinwheel_rim(rng, blades):
+    """The two rim vertices of every blade of a pinwheel around the origin: an opening of 40 to 80 degrees between two
+    edges of length 0.6 to 1, a little out of the plane.  -> [blades, 2, 3] float64"""
     theta = rng.uniform(0., 2. * np.pi, blades)
     open_ = np.deg2rad(rng.uniform(40., 80., blades))
     r = rng.uniform(0.6, 1., (blades, 2))
@@ -64,9 +72,27 @@ def fan_mesh(rng, blades=2000):
     for k, ang in enumerate((theta, theta + open_)):
         rim[:, k, 0], rim[:, k, 1] = r[:, k] * np.cos(ang), r[:, k] * np.sin(ang)
         rim[:, k, 2] = rng.uniform(-0.1, 0.1, blades)
-    v = np.concatenate([np.zeros((1, 3)), rim.reshape(-1, 3)]).astype(np.float32)
-    b = np.arange(blades)
-    return v, np.stack([np.zeros_like(b), 1 + 2 * b, 2 + 2 * b], 1).astype(np.int32)
+    return rim
+
+
+def hubs_mesh(rng, hubs):
+    """Several fans in one mesh.  hubs: [(vertex index, blades)]; every hub is the centre, somewhere in [-0.5, 0.5]^3, of a
+    pinwheel like `fan_mesh`'s with two private rim vertices per blade; the rim vertices take the indices the hubs leave,
+    in order (hub after hub, blade after blade).  The faces are ordered by hub, then blade: (hub, rim, rim), so a hub's
+    list has `blades` entries and a rim vertex's one.
+    -> (vertices [len(hubs) + 2 sum(blades), 3], faces [sum(blades), 3])"""
+    total = len(hubs) + 2 * sum(blades for _, blades in hubs)
+    at = [h for h, _ in hubs]
+    assert len(set(at)) == len(at) and all(0 <= h < total for h in at), (at, total)
+    free = np.setdiff1d(np.arange(total), at)
+    v, faces, used = np.zeros((total, 3)), [], 0
+    for h, blades in hubs:
+        centre = rng.uniform(-0.5, 0.5, 3)
+        slots = free[used:used + 2 * blades]
+        used += 2 * blades
+        v[h], v[slots] = centre, (_pinwheel_rim(rng, blades) + centre).reshape(-1, 3)
+        faces.append(np.stack([np.full(blades, h), slots[0::2], slots[1::2]], 1))
+    return v.astype(np.float32), np.concatenate(faces).astype(np.int32)
 
 
 def split_mesh(vertices, faces):

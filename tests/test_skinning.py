@@ -52,6 +52,26 @@ SHAPES = {
     'b3_root_shared_rest': (2200, 4, 24, 3, None, 3, True),
 }
 CASES = list(SHAPES)
+# Random inputs added after the F32 figures were measured: not part of tolerance_cases(); the float32 composition stays within
+# the committed figures on them (test_extra_cases_stay_within_the_committed_figures), so the kernel's bound rests on the same
+# ground.  name: the columns of SHAPES (a scene count of 1 is a batch of one: [1, V, C], [1, J, 4, 4]), then the `chunk` the
+# SkinWeights is built with (None: the library's own) and the seed.  The bone gradient's second launch gives every column 21
+# slots, each summing a bone's rows slot, slot + 21, ...: a bone has one row per chunk, per scene too for shared transforms.
+EXTRA_SHAPES = {
+    'rows_per_scene': (352, 4, 3, 3, 2, 2, True, 16, 8200),             # bone 0: at least 22 chunks in every scene, per-scene output
+    'rows_shared_pose': (65, 4, 2, 3, 8, None, True, 32, 8201),         # at least 3 chunks x 8 scenes: rows decoded as (scene, chunk)
+    'rows_shared_rest_k5': (65, 5, 2, 4, None, 8, True, 32, 8202),      # the same chunks through the generic-K sum kernel, per-scene output
+    'b40_shared_pose': (64, 4, 3, 3, 40, None, False, None, 8203),      # 40 rows per bone with the library's own chunking
+    'j256': (600, 4, 256, 3, None, None, False, None, 8264),            # the staging array exactly full (seed 8204: float32's own d_transforms at 1.25 x F32)
+    'j257': (600, 4, 257, 3, None, None, False, None, 8205),            # the first J that is not staged
+    'j256_k5_b2': (300, 5, 256, 4, 2, 2, False, None, 8206),            # the same, generic K, restaged per scene in the shared backward
+    'j257_k5_b2': (300, 5, 257, 4, 2, 2, False, None, 8207),
+    'b1_vertices': (257, 4, 24, 3, 1, None, False, None, 8208),         # a batch of one: batched shapes in and out
+    'b1_transforms': (257, 5, 24, 4, None, 1, False, None, 8209),
+    'b1_both': (257, 4, 24, 4, 1, 1, False, None, 8210),
+}
+EXTRA_CASES = list(EXTRA_SHAPES)
+EXACT_ROWS = (21, 22, 42, 43, 64)                                       # around one and two turns of the 21 slots, and into the fourth
 GRAD_PATTERNS = list(itertools.product((False, True), repeat=3))   # requires_grad of (vertices, transforms, weights)
 
 
@@ -64,12 +84,17 @@ def _load_example(name):
 
 def case(name):
     """The keyword arguments of skin_reference.compose for one comparison (the GPU runs get the same arrays)."""
-    V, K, J, C, vb, tb, root = SHAPES[name]
-    rng = np.random.default_rng(8000 + CASES.index(name))
+    if name in EXTRA_SHAPES:
+        V, K, J, C, vb, tb, root, _chunk, seed = EXTRA_SHAPES[name]
+    else:
+        (V, K, J, C, vb, tb, root), seed = SHAPES[name], 8000 + CASES.index(name)
+    rng = np.random.default_rng(seed)
     v = rng.uniform(-1., 1., ((vb,) if vb else ()) + (V, 3))
     if C == 4:
         v = np.concatenate([v, rng.uniform(0.9, 1.1, v.shape[:-1] + (1,))], -1)
     idx, w = R.random_weights(rng, V, K, J, root=root)
+    if name.startswith('j25'):
+        idx[0, 0], idx[-1, -1] = 0, J - 1      # the first and the last staged block (or the first unstaged bone) are read
     grad = rng.standard_normal(((vb or tb,) if (vb or tb) else ()) + (V, 3)).astype(np.float32)
     return dict(vertices=v.astype(np.float32), bone_indices=idx, bone_weights=w, transforms=R.random_transforms(rng, J, tb), grad=grad)
 
@@ -115,22 +140,23 @@ def close(got, ref, mass, tol, what):
     return ratio
 
 
-def run_fused(kw, dev, requires=(True, True, True)):
-    """-> (posed, {gradient name: tensor or None}) of skin_vertices on the arrays of `kw`"""
+def run_fused(kw, dev, requires=(True, True, True), chunk=None):
+    """-> (posed, {gradient name: tensor or None}) of skin_vertices on the arrays of `kw`; chunk: that of the SkinWeights"""
     from dirt_amd import skinning
     v = torch.from_numpy(kw['vertices']).to(dev).requires_grad_(requires[0])
     T = torch.from_numpy(kw['transforms']).to(dev).requires_grad_(requires[1])
     w = torch.from_numpy(kw['bone_weights']).to(dev).requires_grad_(requires[2])
-    skin = skinning.SkinWeights(torch.from_numpy(kw['bone_indices']).to(dev), torch.from_numpy(kw['bone_weights']).to(dev), int(kw['transforms'].shape[-3]))
+    skin = skinning.SkinWeights(torch.from_numpy(kw['bone_indices']).to(dev), torch.from_numpy(kw['bone_weights']).to(dev), int(kw['transforms'].shape[-3]),
+                               chunk=chunk)
     posed = skinning.skin_vertices(v, skin, T, weights=w)
     if posed.requires_grad:
         posed.backward(torch.from_numpy(kw['grad']).to(dev))
     return posed, {'d_vertices': v.grad, 'd_transforms': T.grad, 'd_weights': w.grad}
 
 
-def compare(kw, dev, what, requires=(True, True, True), factor=KERNEL):
+def compare(kw, dev, what, requires=(True, True, True), factor=KERNEL, chunk=None):
     ref = R.compose(**kw)
-    posed, grads = run_fused(kw, dev, requires=requires)
+    posed, grads = run_fused(kw, dev, requires=requires, chunk=chunk)
     assert posed.shape == ref['posed'].shape and posed.requires_grad == any(requires)
     close(posed, ref['posed'], ref['mass_posed'], factor * F32['posed'], '%s posed' % what)
     for k, on in zip(R.GRAD_KINDS, requires):
@@ -203,6 +229,82 @@ def test_the_restatement_is_the_dense_composition_and_within_its_masses():
     assert SHAPES['j300'][2] > _lib.SKIN_LDS_BONES
     smpl = smpl_case()
     assert ((smpl['dense'] != 0).sum(1) == 4).all()
+
+
+def test_extra_cases_stay_within_the_committed_figures():
+    """EXTRA_CASES are not part of what F32 was measured on; the float32 composition's own error on them is within the
+    committed figures all the same, so 4 x F32 allows the kernel there what it allows it on tolerance_cases()."""
+    measured = R.measure_f32(case(name) for name in EXTRA_CASES)
+    print(measured)
+    for k, v in measured.items():
+        assert v <= F32[k], '%s: committed %.3e, measured on the extra cases %.3e' % (k, F32[k], v)
+
+
+def bone_rows(kw, chunk):
+    """rows the bone gradient's second launch adds per bone and output scene: the bone's chunks, times the scenes for shared transforms"""
+    from dirt_amd import skinning
+    skin = skinning.SkinWeights(torch.from_numpy(kw['bone_indices']), torch.from_numpy(kw['bone_weights']), kw['transforms'].shape[-3], chunk=chunk)
+    scenes = kw['vertices'].shape[0] if kw['vertices'].ndim == 3 and kw['transforms'].ndim == 3 else 1
+    return np.diff(skin.chunk_offsets.numpy()) * scenes
+
+
+def exact_rows_case(n, scenes=None):
+    """K = 1, two bones, 70 vertices, the first n on bone 0; weights of 0.5, 1 and 2, small integers everywhere else (vertices
+    with their own w, transforms that are not affine): every product and sum of the composition is exact in float32 in any
+    order.  Built with chunk=1, bone 0 has n rows of one entry each -- 3 n with `scenes`=3 of per-scene vertices under shared
+    transforms."""
+    rng = np.random.default_rng(9200 + n)
+    V = 70
+    idx = (np.arange(V) >= n).astype(np.int32)[:, None]
+    w = rng.choice(np.asarray([0.5, 1., 2.], np.float32), (V, 1))
+    lead = (scenes,) if scenes else ()
+    v = np.concatenate([rng.integers(-3, 4, lead + (V, 3)), rng.integers(1, 3, lead + (V, 1))], -1).astype(np.float32)
+    return dict(vertices=v, bone_indices=idx, bone_weights=w, transforms=rng.integers(-2, 3, (2, 4, 4)).astype(np.float32),
+                grad=rng.integers(-2, 3, lead + (V, 3)).astype(np.float32))
+
+
+def test_the_extra_cases_hold_what_their_names_say():
+    """The row counts that take the reduce kernel's slots into a second turn, the slot count itself, and the staging limit the
+    J cases straddle: a change of SK_SLOTS, CHUNK or DIRT_SKIN_LDS_BONES fails here instead of leaving the cases short of
+    the paths they are for."""
+    from dirt_amd import _lib, skinning
+    source = open(os.path.join(ROOT, 'dirt_amd', 'csrc', 'dirt_skin.hip')).read()
+    assert 'constexpr int SK_SLOTS = 21;' in source
+    slots = 21
+    rows = {name: bone_rows(case(name), EXTRA_SHAPES[name][7]) for name in EXTRA_CASES}
+    for name in ('rows_per_scene', 'rows_shared_pose', 'b40_shared_pose'):
+        assert rows[name].max() > slots, (name, rows[name])
+    assert rows['rows_per_scene'][0] >= 22 and case('rows_per_scene')['transforms'].shape == (2, 3, 4, 4)
+    assert rows['rows_shared_pose'][0] >= 3 * 8 and rows['rows_shared_pose'][0] % 8 == 0 and case('rows_shared_pose')['transforms'].ndim == 3
+    assert rows['b40_shared_pose'].tolist() == [40, 40, 40] and EXTRA_SHAPES['b40_shared_pose'][7] is None and skinning.CHUNK >= 4 * 64
+    # (per-scene transforms: the rows of an output are one scene's chunks; this case is for the scene index of the generic-K FIRST launch)
+    kw = case('rows_shared_rest_k5')
+    assert rows['rows_shared_rest_k5'][0] >= 3 and kw['transforms'].shape == (8, 2, 4, 4) and kw['bone_indices'].shape[1] == 5
+    for n in EXACT_ROWS:
+        assert bone_rows(exact_rows_case(n), 1).tolist() == [n, 70 - n] and bone_rows(exact_rows_case(n, 3), 1).tolist() == [3 * n, 3 * (70 - n)]
+        # every value is a multiple of 0.5 below 2^23: float32 holds each partial sum exactly, in whatever order they are added
+        for scenes in (None, 3):
+            kw = exact_rows_case(n, scenes)
+            ref = R.compose(**kw)
+            assert 2 ** 24 > 2 * max(float(ref['mass_' + k].max()) for k in R.VALUE_KINDS + R.GRAD_KINDS)
+            assert all(bool((2 * ref[k] == (2 * ref[k]).round()).all()) for k in R.VALUE_KINDS + R.GRAD_KINDS)
+            # the test bites: a reduce that took only the first turn of its slots (rows 0 .. 20 of bone 0, scene by scene then
+            # chunk by chunk) would write another d T[0] -- the rows it left out do not cancel
+            v4, g = torch.from_numpy(kw['vertices']).double().reshape(-1, 70, 4), torch.from_numpy(kw['grad']).double().reshape(-1, 70, 3)
+            per_row = (torch.from_numpy(kw['bone_weights']).double()[None, :n, :, None] * v4[:, :n, :, None] * g[:, :n, None, :]).reshape(-1, 4, 3)
+            assert torch.equal(per_row.sum(0), ref['d_transforms'][0, :, :3])
+            if len(per_row) > slots:
+                assert not torch.equal(per_row[:slots].sum(0), per_row.sum(0)), (n, scenes)
+    assert _lib.SKIN_LDS_BONES == 256
+    for name in EXTRA_CASES:
+        if name.startswith('j25'):
+            kw = case(name)
+            J = kw['transforms'].shape[-3]
+            assert J == (256 if name.startswith('j256') else 257) and kw['bone_indices'][0, 0] == 0 and kw['bone_indices'][-1, -1] == J - 1
+    assert case('j256')['transforms'].shape[-3] == _lib.SKIN_LDS_BONES == case('j257')['transforms'].shape[-3] - 1
+    for name, vs, ts in (('b1_vertices', (1, 257, 3), (24, 4, 4)), ('b1_transforms', (257, 4), (1, 24, 4, 4)), ('b1_both', (1, 257, 4), (1, 24, 4, 4))):
+        kw = case(name)
+        assert kw['vertices'].shape == vs and kw['transforms'].shape == ts and kw['grad'].shape == (1, 257, 3)
 
 
 def test_skin_weights_is_the_brute_force_inversion():
@@ -402,6 +504,88 @@ def test_hand_made_index_cases_follow_the_composition(gpu):
         assert float(dw[vertex, slot]) == want
     assert bool(dw[1, 1] != 0) and bool(dw[2, 0] != 0)
     assert torch.equal(dw[0, 0], dw[0, 1]) and torch.equal(dw[3, 0], dw[3, 1])    # one bone in both slots
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', EXTRA_CASES)
+def test_extra_cases_against_the_restatement(gpu, name):
+    """More rows per bone than the reduce kernel has slots (per scene, over the scenes of a shared pose, with the library's own
+    chunking), J at and one past the LDS staging limit, and a batch of one on either operand or both."""
+    kw = case(name)
+    posed, grads, _ = compare(kw, gpu, name, chunk=EXTRA_SHAPES[name][7])
+    if name.startswith('b1'):
+        assert posed.shape == (1, 257, 3)
+        for k, operand in zip(R.GRAD_KINDS, ('vertices', 'transforms', 'bone_weights')):
+            assert grads[k].shape == kw[operand].shape, k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('n', EXACT_ROWS)
+def test_more_rows_than_slots_exactly(gpu, n):
+    """exact_rows_case: bone 0 has n rows (3 n over three scenes of a shared pose) of one entry each, and every sum is exact in
+    float32 in any order, so the kernels equal the float64 composition to the bit: a row left out or added twice cannot hide
+    under a tolerance."""
+    compare(exact_rows_case(n), gpu, '%d rows' % n, factor=0., chunk=1)
+    compare(exact_rows_case(n, 3), gpu, '3 x %d rows, shared transforms' % n, factor=0., chunk=1)
+
+
+def _presented(array, how, dev, transposed=False):
+    """The values of `array` on the device as a plain tensor ('plain'), as a contiguous view that starts one float into its
+    buffer ('misaligned': 4 mod 16 bytes) or as a non-contiguous view ('strided': the leading columns of a wider buffer; with
+    `transposed`, for matrices, the transpose of a tensor that holds the transposed values)"""
+    t = torch.from_numpy(np.ascontiguousarray(array)).to(dev)
+    if how == 'plain':
+        return t
+    if how == 'misaligned':
+        flat = torch.zeros(t.numel() + 1, device=dev)
+        flat[1:] = t.reshape(-1)
+        view = flat[1:].view(t.shape)
+        assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+        return view
+    if transposed:
+        view = t.transpose(-1, -2).contiguous().transpose(-1, -2)
+    else:
+        buf = torch.full(t.shape[:-1] + (t.shape[-1] + 3,), 7., device=dev)
+        buf[..., :t.shape[-1]] = t
+        view = buf[..., :t.shape[-1]]
+    assert not view.is_contiguous() and torch.equal(view, t)
+    return view
+
+
+def _run_presented(kw, dev, how, grad):
+    """skin_vertices on the arrays of `kw` presented as `how`; grad: an array presented the same way, or 'expanded': the
+    stride-0 ones of posed.sum().backward().  -> (posed, leaves)"""
+    from dirt_amd import skinning
+    leaves = [_presented(kw[k], how, dev, transposed=k == 'transforms').detach().requires_grad_(True) for k in ('vertices', 'transforms', 'bone_weights')]
+    skin = skinning.SkinWeights(torch.from_numpy(kw['bone_indices']).to(dev), torch.from_numpy(kw['bone_weights']).to(dev), int(kw['transforms'].shape[-3]))
+    posed = skinning.skin_vertices(leaves[0], skin, leaves[1], weights=leaves[2])
+    if isinstance(grad, str):
+        posed.sum().backward()
+    else:
+        posed.backward(_presented(grad, how, dev))
+    return posed, leaves
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['v257', 'b3_per_scene_k5'])
+def test_misaligned_and_non_contiguous_operands(gpu, name):
+    """The same values as contiguous views 4 bytes past a 16-byte boundary (the kernels' 12- and 16-byte accesses to rows that
+    are only 4-byte aligned, the K = 4 path's 16-byte load of `weights` among them) and as non-contiguous views (the
+    wrapper's .contiguous() branches), the incoming gradient likewise -- a strided [.., :3] view is what the rasteriser's
+    state hands back, an expanded one what .sum() does: the kernels see the same numbers in the same order, so the output
+    and every gradient equal the plain run's to the bit, and every leaf's .grad has the leaf's shape."""
+    kw = case(name)
+    plain, plain_leaves = _run_presented(kw, gpu, 'plain', kw['grad'])
+    assert all(bool(l.grad.abs().max() > 0) for l in plain_leaves)
+    for how in ('misaligned', 'strided'):
+        posed, leaves = _run_presented(kw, gpu, how, kw['grad'])
+        assert torch.equal(plain, posed), how
+        for k, a, b in zip(R.GRAD_KINDS, plain_leaves, leaves):
+            assert b.grad.shape == b.shape and torch.equal(a.grad, b.grad), (how, k)
+    _, want = _run_presented(kw, gpu, 'plain', np.ones(plain.shape, np.float32))
+    _, got = _run_presented(kw, gpu, 'plain', 'expanded')
+    for k, a, b in zip(R.GRAD_KINDS, want, got):
+        assert b.grad.shape == b.shape and torch.equal(a.grad, b.grad) and bool(a.grad.abs().max() > 0), ('expanded', k)
 
 
 @pytest.mark.gpu
