@@ -9,4 +9,6 @@ from . import geometry  # noqa: F401  (the fused vertex stage in front of the ra
 from .geometry import MeshTopology, vertex_stage  # noqa: F401
 from . import skinning  # noqa: F401  (fused linear-blend skinning in front of the vertex stage: a blend of bone matrices per vertex)
 from .skinning import SkinWeights, skin_vertices  # noqa: F401
+from . import kinematics  # noqa: F401  (fused forward kinematics in front of the skinning stage: rotations and joints -> bone transforms)
+from .kinematics import Skeleton, pose_skeleton  # noqa: F401
 from .graphed import GraphedStep, backward  # noqa: F401  (a training step captured once as a HIP graph: the remedy for eager autograd's host cost)

@@ -225,7 +225,8 @@ def skin_vertices(vertices, skin, bone_transforms, weights=None):
         upstream) on the GPU; with three components w = 1 is appended.
     skin: the mesh's `SkinWeights`, on the same device.
     bone_transforms: float32 [J, 4, 4] or [B, J, 4, 4], in the row-vector convention of `dirt_amd.matrices` (v @ T,
-        translation in row 3); GPU tensors, never read on the host.  Forward kinematics is the caller's.
+        translation in row 3); GPU tensors, never read on the host.  `dirt_amd.kinematics.pose_skeleton` computes them from
+        joint rotations (the forward kinematics of a skeleton, fused).
     weights: float32 [V, K] that replaces skin.bone_weights for this call and may require a gradient (learned weights).
     The output is batched if either input is.  Per scene
         M[v] = sum over k in slot order of w[v, k] * T[idx[v, k]],     posed[v] = (v4 @ M[v])[:3]

@@ -401,6 +401,43 @@ int dirt_skin_backward(const float *vertices, int components, int vertex_scenes,
                        void *stream);
 
 /*
+ * Forward kinematics in front of the skinning stage, fused.  Extends the one matrices.rodrigues / compose per mesh of the
+ * reference's samples (samples/deferred.py:40-41; dirt/matrices.py:15-61,183-207) to a skeleton: a forest of J <=
+ * DIRT_KINEMATICS_MAX_JOINTS joints whose parents come before their children; specification in
+ * dirt_amd/csrc/dirt_kinematics.hip and DESIGN.md §7e.  Per scene, float32, row vectors:
+ *     R[j] = rodrigues(rotations[j]) (3 x 3, dirt/matrices.py:15-61 operation for operation),  tl[j] = p[j] - p[j] @ R[j]
+ *     root: S3[j] = R[j], t[j] = tl[j];   else: S3[j] = R[j] @ S3[parent],  t[j] = tl[j] @ S3[parent] + t[parent]
+ *     transforms[j] = [[S3[j], 0], [t[j], 1]],   posed_joints[j] = p[j] @ S3[j] + t[j]
+ *   rotations [rotation_scenes, J, 3] angle-axis vectors, joints [joint_scenes, J, 3] rest-pose positions p; each scene count
+ *   is 1 (shared by the scenes) or B; 4-byte alignment suffices.
+ *   parents int32 [J] (-1: a root), and the index dirt_amd.kinematics.Skeleton builds from it: order [J], the joints by
+ *   depth, then index; level_offsets [levels + 1], the joints of depth d being order[level_offsets[d] ..
+ *   level_offsets[d + 1]); 1 <= levels <= J.  The kernels trust the index arrays.
+ *   transforms [B, J, 4, 4] (what dirt_skin_forward takes; column 3 written as (0, 0, 0, 1)), posed_joints [B, J, 3]: each
+ *   may be NULL and is then not written.
+ * One launch of a workgroup per scene, no atomics.  B or J equal to 0: success, nothing is launched.  flags: none defined,
+ * must be 0.
+ * Backward: grad_transforms [B, J, 4, 4] (column 3 is ignored) and grad_posed_joints [B, J, 3], each may be NULL (zero), ->
+ * grad_rotations and grad_joints (shaped like the operands); each may be NULL and is then not computed; those given are
+ * fully written, an operand shared by the scenes receiving the sum over the scenes.  Needs, beside the above, the inverted
+ * index of parents: child_entries, the non-root joints ordered by parent, then index, and child_offsets [J + 1] (the
+ * children of j are child_entries[child_offsets[j] .. child_offsets[j + 1])).  `scratch`, caller-owned, of
+ * dirt_kinematics_scratch_bytes(B, J) = 4 * 6 * B * J bytes (0: invalid sizes), is needed -- and checked -- only where a
+ * wanted gradient belongs to an operand shared by B > 1 scenes: one row per (scene, joint), added by a second launch in a
+ * fixed order.  1 launch, + 1 for a shared operand; no atomics, the same bits on every run.  Failures: dirt_last_error().
+ */
+#define DIRT_KINEMATICS_MAX_JOINTS 256 /* the skinning stage's DIRT_SKIN_LDS_BONES: a scene's joints live in 12 KB of LDS */
+size_t dirt_kinematics_scratch_bytes(long long B, long long J);
+int dirt_kinematics_forward(const float *rotations, int rotation_scenes, const float *joints, int joint_scenes,
+                            const int32_t *parents, const int32_t *order, const int32_t *level_offsets, int levels,
+                            float *transforms, float *posed_joints, long long B, int J, unsigned flags, void *stream);
+int dirt_kinematics_backward(const float *rotations, int rotation_scenes, const float *joints, int joint_scenes,
+                             const int32_t *parents, const int32_t *order, const int32_t *level_offsets, int levels,
+                             const int32_t *child_entries, const int32_t *child_offsets, const float *grad_transforms,
+                             const float *grad_posed_joints, float *grad_rotations, float *grad_joints, void *scratch,
+                             size_t scratch_bytes, long long B, int J, unsigned flags, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
