@@ -81,6 +81,54 @@ SHAPES = {
     'b70_shared_joints': ('smpl', 70, None, (), None),           # more scenes than a wave has lanes, and a reduce over 70 rows
 }
 CASES = list(SHAPES)
+
+
+def _comb128():
+    parents = []
+    for link in range(128):           # as `comb`: link i is joint 2 i, its leaf joint 2 i + 1
+        parents += [2 * (link - 1) if link else -1, 2 * link]
+    return parents
+
+
+# Skeletons of the four-wave workgroup that the cases above leave out: every level count, level width and child list at its limit
+EXTRA_SKELETONS = {
+    'chain256': list(range(-1, 255)),                 # 256 levels: s_lo filled to its last entry, 256 barriers
+    'star256': [-1] + [0] * 255,                      # a child list of 255 entries
+    'comb128': _comb128(),                            # 256 joints, 129 levels of width 2 (the ends: 1): boundaries at every even lane of waves 1-3
+    'ladder3_255': [-1] * 3 + list(range(252)),       # parents[j] = j - 3: 85 levels of width 3, starts on every lane position mod 64
+    'roots256': [-1] * 256,                           # one level, no child entries at all
+    'forest200': [-1] * 70 + np.random.default_rng(79).integers(0, np.arange(70, 200)).tolist(),   # 70 roots, then parents[j] uniform in [0, j)
+}
+SKELETONS.update(EXTRA_SKELETONS)
+_FOREST_INNER = min(q for q in EXTRA_SKELETONS['forest200'] if q >= 70)       # the first non-root joint that has a child
+
+# Random inputs added after the F32 figures were measured: not part of tolerance_cases(); the float32 composition stays within
+# the committed figures on them (test_extra_cases_stay_within_the_committed_figures), so the kernel's bound rests on the same
+# ground.  name: (skeleton, scenes of the rotations, scenes of the joints, joints with an exact zero rotation, seed).  The
+# reduce kernel sums every 42nd scene per slot: 42 scenes are one turn, 43 one row into the second, 85 / 86 into the third.
+EXTRA_SHAPES = {
+    'chain256': ('chain256', None, None, (0, 100, 255), 9100),                 # zero rotations at the root, an inner joint, the leaf
+    'star256': ('star256', None, None, (), 9100),
+    'comb128': ('comb128', None, None, (), 9100),
+    'ladder3_255': ('ladder3_255', None, None, (), 9100),
+    'roots256': ('roots256', None, None, (), 9101),                            # (seeds 9100, 9102: float32's own transforms at 1.19 and 2.67 x F32)
+    'forest200': ('forest200', None, None, (3, _FOREST_INNER, 199), 9102),     # (9100, 9101: transforms at 1.05 and 1.56 x F32)
+    'b42_shared_rotations': ('smpl', None, 42, (), 9100),
+    'b43_shared_rotations': ('smpl', None, 43, (), 9100),
+    'b85_shared_rotations': ('smpl', None, 85, (), 9100),
+    'b43_shared_joints': ('smpl', 43, None, (), 9102),                         # (9100, 9101: posed_joints at 1.21 and 1.04 x F32)
+    'b86_shared_joints': ('smpl', 86, None, (), 9101),                         # (9100: transforms at 1.09 x F32)
+    # the four-wave backward with the reduce in its second turn.  11 008 joints under per-scene rotations: the float32 composition's
+    # own posed_joints were at 1.02 to 2.5 x F32 for every seed from 9100 to 9297 (the forest likewise, and its transforms at 2 to 100 x)
+    'b43_shared_joints_star256': ('star256', 43, None, (), 9298),
+    'b3_shared_joints_chain65': ('chain65', 3, None, (), 9100),                # 191 lanes without a joint, rows in scratch
+}
+EXTRA_CASES = list(EXTRA_SHAPES)
+SAME_BITS = ('chain256', 'star256', 'b85_shared_rotations')
+PATTERN_CASES = ('b43_shared_rotations', 'b43_shared_joints')      # the shared operand is the rotations / the joints
+# (case, scenes the mutated scene sum stops at): test_the_extra_cases_bite
+SCENE_SUMS = (('b43_shared_rotations', 42), ('b85_shared_rotations', 84), ('b43_shared_joints', 42), ('b86_shared_joints', 85),
+              ('b43_shared_joints_star256', 42))
 GRAD_PATTERNS = list(itertools.product((False, True), repeat=2))   # requires_grad of (rotations, joints)
 # (case, the output nobody used): the gradient through the other output alone
 ONE_OUTPUT = [(name, unused) for name in ('smpl', 'b3_shared_joints') for unused in ('grad_posed_joints', 'grad_transforms')]
@@ -99,10 +147,13 @@ _CASE_CACHE = {}
 def case(name):
     """The keyword arguments of kinematics_reference.compose for one comparison (the GPU runs get the same arrays)."""
     if name not in _CASE_CACHE:
-        skeleton, rb, pb, zeros, wide = SHAPES[name]
+        if name in EXTRA_SHAPES:
+            (skeleton, rb, pb, zeros, seed), wide = EXTRA_SHAPES[name], None
+        else:
+            (skeleton, rb, pb, zeros, wide), seed = SHAPES[name], 8300 + CASES.index(name)
         parents = SKELETONS[skeleton]
         J = len(parents)
-        rng = np.random.default_rng(8300 + CASES.index(name))
+        rng = np.random.default_rng(seed)
         lead_r, lead_p = ((rb,) if rb else ()), ((pb,) if pb else ())
         lead = ((rb or pb,) if (rb or pb) else ())
         axes = rng.standard_normal(lead_r + (J, 3))
@@ -249,6 +300,100 @@ def test_the_restatement_is_the_loop_of_compose_calls():
     assert sorted(set(np.round(np.linalg.norm(case('smpl_wide')['rotations'], axis=-1), 4).tolist())) == [4., 7.]
 
 
+def test_extra_cases_stay_within_the_committed_figures():
+    """EXTRA_CASES are not part of what F32 was measured on; the float32 composition's own error on each of them is within the
+    committed figures all the same, so 4 x F32 allows the kernel there what it allows it on tolerance_cases().  A case that
+    does not stay within them gets another seed (EXTRA_SHAPES names the seeds that were replaced), never a wider bound."""
+    for name in EXTRA_CASES:
+        measured = R.measure_f32([case(name)])
+        print(name, ' '.join('%s %.2f' % (k, v / F32[k]) for k, v in measured.items()))
+        for k, v in measured.items():
+            assert v <= F32[k], '%s %s: committed %.3e, measured on this case %.3e' % (name, k, F32[k], v)
+
+
+def test_the_extra_cases_hold_what_their_names_say():
+    """The level counts, level widths, child lists and roots the extra skeletons are for, the zero rotations, and the scene
+    counts around the reduce kernel's 42 slots: a change of KN_SLOTS or of the block sizes fails here instead of leaving the
+    cases short of the paths they are for."""
+    from dirt_amd import _lib, kinematics
+    source = open(os.path.join(ROOT, 'dirt_amd', 'csrc', 'dirt_kinematics.hip')).read()
+    assert 'constexpr int KN_SLOTS = 42;' in source and '#define DIRT_KINEMATICS_SMALL_BLOCK 64' in source and _lib.KINEMATICS_MAX_JOINTS == 256
+    #                              joints, levels, widest level, longest child list, roots
+    for name, want in (('chain256', (256, 256, 1, 1, 1)), ('star256', (256, 2, 255, 255, 1)), ('comb128', (256, 129, 2, 2, 1)),
+                       ('ladder3_255', (255, 85, 3, 1, 3)), ('roots256', (256, 1, 256, 0, 256)), ('forest200', (200, None, None, None, 70))):
+        s = kinematics.Skeleton(SKELETONS[name])
+        got = (s.num_joints, s.num_levels, int(s.level_offsets.diff().max()), int(s.child_offsets.diff().max()), int((s.parents < 0).sum()))
+        assert all(w is None or g == w for g, w in zip(got, want)), (name, got)
+        assert s.num_joints > 64        # the four-wave workgroup
+    s = kinematics.Skeleton(SKELETONS['roots256'])
+    assert s.child_entries.numel() == 0 and not s.child_entries.data_ptr() and s.child_offsets.tolist() == [0] * 257
+    # level boundaries inside waves 1-3: the comb's at every even position from 64 on, the ladder's on every lane position mod 64
+    lo = kinematics.Skeleton(SKELETONS['comb128']).level_offsets.tolist()
+    assert lo[:3] == [0, 1, 3] and lo[-2:] == [255, 256] and sum(64 <= x < 256 for x in lo) == 96
+    lo = kinematics.Skeleton(SKELETONS['ladder3_255']).level_offsets.tolist()
+    assert lo == list(range(0, 256, 3)) and {x % 64 for x in lo if x >= 64} == set(range(64))
+    forest = SKELETONS['forest200']
+    assert forest[:70] == [-1] * 70 and all(0 <= q < j for j, q in enumerate(forest) if j >= 70) and kinematics.Skeleton(forest).num_levels > 2
+    assert forest[3] == -1 and forest[_FOREST_INNER] >= 0 and _FOREST_INNER in forest and 199 not in forest
+    for name in EXTRA_CASES:
+        kw = case(name)
+        skeleton, rb, pb, zeros, _ = EXTRA_SHAPES[name]
+        J = len(SKELETONS[skeleton])
+        assert kw['rotations'].shape == ((rb,) if rb else ()) + (J, 3) and kw['joints'].shape == ((pb,) if pb else ()) + (J, 3), name
+        angles = np.linalg.norm(kw['rotations'], axis=-1)
+        assert (angles[angles > 0] >= 0.3 - 1e-6).all() and sorted(np.nonzero(angles.reshape(-1, J).min(0) == 0)[0].tolist()) == sorted(zeros), name
+    slots = 42
+    turns = lambda scenes: -(-scenes // slots)   # noqa: E731
+    assert [turns(EXTRA_SHAPES[n][2]) for n in ('b42_shared_rotations', 'b43_shared_rotations', 'b85_shared_rotations')] == [1, 2, 3]
+    assert [turns(EXTRA_SHAPES[n][1]) for n in ('b3_shared_joints_chain65', 'b43_shared_joints', 'b86_shared_joints')] == [1, 2, 3]
+    assert EXTRA_SHAPES['b43_shared_joints_star256'][:3] == ('star256', 43, None)
+
+
+def _moved(mutated, ref, mass, kind):
+    """whether some element of `mutated` lies beyond the bound the GPU comparison applies to `kind` around `ref`"""
+    return R.worst_ratio(mutated, ref, mass) > KERNEL * F32[kind]
+
+
+def test_the_extra_cases_bite():
+    """What each extra case is for, left out of the float64 restatement (its inputs or its sums, never the kernel), moves some
+    element past the bound the GPU test applies.
+      - star256's root gathers 255 children; without the last one: the root's gradients with child 255's incoming gradients
+        zeroed (the child's own rows change too; only the root's are looked at).
+      - chain256 without its last level, backward: likewise, joint 254 without the block of joint 255; forward: joint 255 never
+        composed with its parent, i.e. what it has as a root -- seen in d_joints[255], not in its own transform (below).
+      - the scene sum of a shared operand stopped one row early (42 of 43, 84 of 85, 85 of 86): the per-scene rows are those
+        of the same inputs with the shared operand repeated per scene, and the sum of all of them is the restatement's.
+    Not expressible through the restatement: a lane without a joint writing somewhere (the C entry point test's sentinels
+    check that), and a wrong barrier count, which shows as a race, not as a value of the composition."""
+    for name, parent, child in (('star256', 0, 255), ('chain256', 254, 255)):
+        kw, ref = case(name), reference(name)
+        cut = dict(kw, grad_transforms=kw['grad_transforms'].copy(), grad_posed_joints=kw['grad_posed_joints'].copy())
+        cut['grad_transforms'][child], cut['grad_posed_joints'][child] = 0., 0.
+        mutated = R.compose(masses=False, **cut)
+        for k in R.GRAD_KINDS:
+            assert _moved(mutated[k][parent], ref[k][parent], ref['mass_' + k][parent], k), (name, k)
+    # joint 255 as a root: its own transform moves by O(1), yet NOT past its bound -- the L1 mass of a transform grows with every
+    # level (|R| has a norm of up to 1.7) and is beyond 1e70 at the end of this chain, so the values of the deep joints are bound
+    # loosely.  What the walk left in LDS is bound tightly through d_joints all the same: d p[j] = S3[j] @ gq[j] + ... has the mass
+    # of the actual |S3[j]| (the backward kernel recomputes the forward with the same walk), and that is where the mutation shows
+    kw, ref = case('chain256'), reference('chain256')
+    alone = R.compose(masses=False, **dict(kw, parents=kw['parents'][:255] + [-1]))
+    assert float((alone['transforms'][255] - ref['transforms'][255]).abs().max()) > 1. and float(ref['mass_transforms'][255, :3, :3].min()) > 1e70
+    assert float(ref['mass_d_joints'].max()) < 1e4
+    assert _moved(alone['d_joints'][255], ref['d_joints'][255], ref['mass_d_joints'][255], 'd_joints')
+    for k in R.VALUE_KINDS:
+        assert torch.equal(alone[k][:255], ref[k][:255])
+    for name, stop in SCENE_SUMS:
+        kw, ref = case(name), reference(name)
+        operand, k = ('rotations', 'd_rotations') if kw['rotations'].ndim == 2 else ('joints', 'd_joints')
+        B = kw['grad_posed_joints'].shape[0]
+        assert kw[operand].ndim == 2 and stop < B and -(-stop // 42) <= -(-B // 42)
+        rows = R.compose(masses=False, **dict(kw, **{operand: np.broadcast_to(kw[operand], (B,) + kw[operand].shape).copy()}))[k]
+        assert rows.shape == (B,) + tuple(ref[k].shape)
+        assert R.worst_ratio(rows.sum(0), ref[k], ref['mass_' + k]) <= 1e-13, name
+        assert _moved(rows[:stop].sum(0), ref[k], ref['mass_' + k], k), (name, stop)
+
+
 def test_skeleton_is_the_brute_force_construction():
     from dirt_amd import kinematics
     rng = np.random.default_rng(21)
@@ -393,6 +538,111 @@ def test_values_and_gradients_against_the_restatement(gpu, name):
 @pytest.mark.parametrize('requires', GRAD_PATTERNS, ids=[''.join(n for n, on in zip('rp', r) if on) or 'none' for r in GRAD_PATTERNS])
 def test_every_pattern_of_requires_grad(gpu, name, requires):
     compare(case(name), gpu, '%s requires_grad=%s' % (name, requires), requires=requires, ref=reference(name))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', EXTRA_CASES)
+def test_extra_cases_against_the_restatement(gpu, name):
+    """The four-wave workgroup at its limits (256 levels, a child list of 255, level boundaries inside waves 1-3, a forest,
+    256 roots without a child entry) and scene counts of one, two and three turns of the reduce kernel's 42 slots, for either
+    shared operand and with the four-wave backward: values, both gradients, both outputs used."""
+    (T, q), grads, ref = compare(case(name), gpu, name, ref=reference(name))
+    if name == 'roots256':      # no child entries (a NULL pointer at the C entry point): the gradients are the restatement's all the same
+        assert all(bool(grads[k].abs().min() > 0) for k in R.GRAD_KINDS)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', PATTERN_CASES)
+@pytest.mark.parametrize('requires', GRAD_PATTERNS, ids=[''.join(n for n, on in zip('rp', r) if on) or 'none' for r in GRAD_PATTERNS])
+def test_every_pattern_of_requires_grad_at_43_scenes(gpu, name, requires):
+    """One operand shared by 43 scenes, the other per scene: the shared one wanted and the other too (half of every scratch row
+    unused, the other gradient stored directly), the shared one alone, and the per-scene one alone (no reduce, no scratch)."""
+    compare(case(name), gpu, '%s requires_grad=%s' % (name, requires), requires=requires, ref=reference(name))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', SAME_BITS)
+def test_two_runs_of_the_extra_cases_give_the_same_bits(gpu, name):
+    kw = case(name)
+    (o1, g1), (o2, g2) = run_fused(kw, gpu), run_fused(kw, gpu)
+    assert torch.equal(o1[0], o2[0]) and torch.equal(o1[1], o2[1])
+    for k in R.GRAD_KINDS:
+        assert torch.equal(g1[k], g2[k]) and bool(g1[k].abs().max() > 0), k
+
+
+SENTINEL = -1234.5
+PAD = 64     # floats in front and behind: 256 bytes, the alignment of the allocations the wrapper makes
+
+
+def _padded(count, dev):
+    """-> (buffer of PAD + count + PAD sentinels, the address of its middle, which keeps the buffer's own 256-byte alignment)"""
+    buf = torch.full((count + 2 * PAD,), SENTINEL, dtype=torch.float32, device=dev)
+    assert buf.data_ptr() % 256 == 0
+    return buf, buf.data_ptr() + 4 * PAD
+
+
+def _middle(buf, what):
+    """the floats between the paddings, after checking that both paddings still hold the sentinel"""
+    assert bool((buf[:PAD] == SENTINEL).all()) and bool((buf[-PAD:] == SENTINEL).all()), '%s: a write outside the output' % what
+    return buf[PAD:-PAD]
+
+
+def _c_operands(kw, dev):
+    from dirt_amd import kinematics
+    r, p = (torch.from_numpy(kw[k]).to(dev) for k in ('rotations', 'joints'))
+    skeleton = kinematics.Skeleton(kw['parents'], device=dev)
+    return r, p, skeleton, kinematics._operands(r, p) + kinematics._index_operands(skeleton)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['chain65', 'b3_shared_joints'])
+def test_the_c_forward_with_one_output(gpu, name):
+    """dirt_kinematics_forward with transforms = NULL, then with posed_joints = NULL (the wrapper always passes both): the
+    output asked for equals the wrapper's to the bit, and the 64 floats in front of it and behind it are untouched -- with
+    65 joints, 191 lanes of the workgroup have no joint and must write nothing."""
+    from dirt_amd import _lib, rasterise_ops as ops
+    lib = _lib.load()
+    kw = case(name)
+    (T, q), _ = run_fused(kw, gpu, requires=(False, False))
+    r, p, skeleton, operands = _c_operands(kw, gpu)
+    B, J = (kw['rotations'].shape[0] if kw['rotations'].ndim == 3 else 1), len(kw['parents'])
+    for what, want, width in (('posed_joints alone', q, 3), ('transforms alone', T, 16)):
+        buf, address = _padded(B * J * width, gpu)
+        with ops._on_device(gpu):
+            rc = lib.dirt_kinematics_forward(*operands, None if width == 3 else address, address if width == 3 else None, B, J, 0,
+                                             ops._stream_handle(gpu))
+        assert rc == 0, lib.dirt_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(_middle(buf, what), want.reshape(-1)), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['chain65', 'b3_shared_joints_chain65'])
+def test_the_c_backward_writes_inside_its_outputs_only(gpu, name):
+    """dirt_kinematics_backward on 65 joints (191 lanes without one), one scene and three scenes with shared joints: both
+    gradients equal the wrapper's to the bit, and the paddings around them -- and around the scratch the shared joints' rows
+    go to -- are untouched."""
+    from dirt_amd import _lib, rasterise_ops as ops
+    lib = _lib.load()
+    kw = case(name)
+    _, grads = run_fused(kw, gpu)
+    r, p, skeleton, operands = _c_operands(kw, gpu)
+    B, J = (kw['rotations'].shape[0] if kw['rotations'].ndim == 3 else 1), len(kw['parents'])
+    gT, gq = (torch.from_numpy(kw[g]).to(gpu) for g in ('grad_transforms', 'grad_posed_joints'))
+    nbytes = lib.dirt_kinematics_scratch_bytes(B, J) if B > 1 else 0
+    assert nbytes == (4 * 6 * B * J if B > 1 else 0)
+    (gr, gr_at), (gp, gp_at), (scratch, scratch_at) = _padded(r.numel(), gpu), _padded(p.numel(), gpu), _padded(nbytes // 4, gpu)
+    with ops._on_device(gpu):
+        rc = lib.dirt_kinematics_backward(*operands, skeleton.child_entries.data_ptr(), skeleton.child_offsets.data_ptr(), gT.data_ptr(), gq.data_ptr(),
+                                          gr_at, gp_at, scratch_at if nbytes else None, nbytes, B, J, 0, ops._stream_handle(gpu))
+    assert rc == 0, lib.dirt_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(_middle(gr, 'grad_rotations'), grads['d_rotations'].reshape(-1))
+    assert torch.equal(_middle(gp, 'grad_joints'), grads['d_joints'].reshape(-1))
+    rows = _middle(scratch, 'scratch')
+    if nbytes:      # rotations per scene: stored directly, so columns 0-2 of every scratch row stay as they were
+        rows = rows.reshape(B, J, 6)
+        assert bool((rows[..., :3] == SENTINEL).all()) and bool((rows[..., 3:] != SENTINEL).all())
 
 
 @pytest.mark.gpu
