@@ -11,4 +11,6 @@ from . import skinning  # noqa: F401  (fused linear-blend skinning in front of t
 from .skinning import SkinWeights, skin_vertices  # noqa: F401
 from . import kinematics  # noqa: F401  (fused forward kinematics in front of the skinning stage: rotations and joints -> bone transforms)
 from .kinematics import Skeleton, pose_skeleton  # noqa: F401
+from . import blendshapes  # noqa: F401  (fused blend shapes at the head of the chain: template and coefficients -> rest vertices and joints)
+from .blendshapes import BlendShapes, blend_shapes  # noqa: F401
 from .graphed import GraphedStep, backward  # noqa: F401  (a training step captured once as a HIP graph: the remedy for eager autograd's host cost)

@@ -40,6 +40,7 @@ GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
 SKIN_MAX_INFLUENCES, SKIN_MAX_BONES, SKIN_LDS_BONES, SKIN_MAX_VERTICES, SKIN_MAX_ENTRIES = 8, 65536, 256, 1 << 28, 1 << 30   # up to SKIN_LDS_BONES the bone blocks are staged in LDS
 
 KINEMATICS_MAX_JOINTS = 256   # = SKIN_LDS_BONES: a scene's joints live in LDS
+BLEND_MAX_SHAPES, BLEND_MAX_VERTICES, BLEND_MAX_JOINTS, BLEND_MAX_ENTRIES = 4096, 1 << 26, 256, 1 << 30   # BLEND_MAX_JOINTS = KINEMATICS_MAX_JOINTS
 
 E_INVALID_ARGUMENT = -1
 E_TOO_MANY_VERTICES = -2
@@ -58,7 +59,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward',
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
-           'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward')
+           'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward',
+           'dirt_blend_scratch_bytes', 'dirt_blend_forward', 'dirt_blend_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -152,6 +154,13 @@ def load():
         lib.dirt_kinematics_forward.restype = i
         lib.dirt_kinematics_backward.argtypes = [fp, i, fp, i, ip, ip, ip, i, ip, ip, fp, fp, fp, fp, vp, sz, ll, i, u, vp]
         lib.dirt_kinematics_backward.restype = i
+    if hasattr(lib, 'dirt_blend_forward') or not override:   # fused blend shapes (ABI 4, additive)
+        lib.dirt_blend_scratch_bytes.argtypes = [ll, ll, ll]
+        lib.dirt_blend_scratch_bytes.restype = sz
+        lib.dirt_blend_forward.argtypes = [fp, i, fp, i, fp, ll, ip, ip, fp, fp, fp, fp, ll, ll, i, i, i, u, vp]
+        lib.dirt_blend_forward.restype = i
+        lib.dirt_blend_backward.argtypes = [i, i, fp, ll, ip, ip, fp, fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, u, vp]
+        lib.dirt_blend_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -3,9 +3,10 @@
 //   G-buffer lighting (dirt_shade.hip);
 //   vertex stage      (dirt_geometry.hip);
 //   skinning          (dirt_skin.hip: Float3 / Float4 / load3 / store3, dot3, the wave sum, the four-wave fold, the error channel, the scratch check);
-//   kinematics        (dirt_kinematics.hip: Float4 / load3 / store3, dot3, the error channel, the scratch check).
+//   kinematics        (dirt_kinematics.hip: Float4 / load3 / store3, dot3, the error channel, the scratch check);
+//   blend shapes      (dirt_blend.hip: Float4 / load3 / store3, load_quad / store_quad, the wave sum, the four-wave fold, the error channel, the scratch check).
 // Device side: the 12- and 16-byte accesses to rows that are only 4-byte aligned (Float3 of dirt_device.h, Float4, load3 /
-// store3: all four), dot3 / cross3 (shade, geometry), the all-lanes wave sum, the fold of a workgroup's four waves into its
+// store3: all four; load_quad / store_quad, a quad of a row with its zero-padded tail: blend shapes), dot3 / cross3 (shade, geometry), the all-lanes wave sum, the fold of a workgroup's four waves into its
 // row of partial sums and the fixed-order sum of a column of such rows (shade, geometry: their parameter and matrix gradients).
 // Host side: the two error channels and the helpers that report into either (all four, and dirt_capi.hip for the first
 // channel), the scratch check (shade, geometry), the channel-count dispatch and the capped grid of a grid-stride launch
@@ -34,6 +35,30 @@ __device__ __forceinline__ void load3(const float* __restrict__ p, float (&v)[3]
     v[0] = t.x; v[1] = t.y; v[2] = t.z;
 }
 __device__ __forceinline__ void store3(float* p, const float (&v)[3]) { *reinterpret_cast<Float3*>(p) = Float3{v[0], v[1], v[2]}; }
+
+// four consecutive elements e .. e + 3 of a 4-byte aligned row of E floats in one 16-byte access; at the end of the row the
+// elements past it read as zero and are not written
+__device__ __forceinline__ void load_quad(const float* __restrict__ row, int e, int E, float (&x)[4])
+{
+    if (e + 4 <= E) {
+        const Float4 q = *reinterpret_cast<const Float4*>(row + e);
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = e + i < E ? row[e + i] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void store_quad(float* row, int e, int E, const float (&x)[4])
+{
+    if (e + 4 <= E) {
+        *reinterpret_cast<Float4*>(row + e) = Float4{x[0], x[1], x[2], x[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (e + i < E) row[e + i] = x[i];
+    }
+}
 
 __device__ __forceinline__ float dot3(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 

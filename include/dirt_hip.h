@@ -438,6 +438,51 @@ int dirt_kinematics_backward(const float *rotations, int rotation_scenes, const 
                              size_t scratch_bytes, long long B, int J, unsigned flags, void *stream);
 
 /*
+ * Blend shapes in front of the kinematics and skinning stages, fused.  Extends the one fixed mesh per scene of the
+ * reference's samples (samples/deferred.py:40-41 moves it with one matrix) to the rest mesh of a body, hand or face model:
+ * template + sum of coefficient x direction, and the joints regressed from it; specification in
+ * dirt_amd/csrc/dirt_blend.hip and DESIGN.md §7f.  Per scene, float32:
+ *     vertices[v] = template[v] + sum over k < K of c[k] * directions[k, v]
+ *     joints[j]   = sum over the non-zeros (j, v) of the regressor of w[j, v] * template[v]
+ *                 + sum over k < Ks of c[k] * joint_directions[k, j]
+ *   template_vertices [template_scenes, V, 3], coefficients [coefficient_scenes, K]: each scene count is 1 (shared by the
+ *   scenes) or B; 4-byte alignment suffices.  V <= DIRT_BLEND_MAX_VERTICES, 0 <= K <= DIRT_BLEND_MAX_SHAPES.
+ *   directions: the packed table [K, stride] dirt_amd.blendshapes.BlendShapes builds -- row k holds directions[k] as 3 V
+ *   floats, then zeros up to `stride`, a multiple of 4 floats; the base 16-byte aligned (checked): every row starts 16-byte
+ *   aligned and is read 16 bytes per lane.
+ *   The regressor [J, V], J <= DIRT_BLEND_MAX_JOINTS, as its non-zeros ordered by joint, then vertex (CSR): row_offsets
+ *   [J + 1], row_vertices and row_weights (the non-zeros of joint j are row_offsets[j] .. row_offsets[j + 1]); at most
+ *   DIRT_BLEND_MAX_ENTRIES non-zeros.  joint_directions [Ks, J, 3] = regressor @ directions[k] for the first Ks <= K
+ *   directions, the ones that move the joints (computed once, in float64, by the caller).  The kernels trust the index arrays.
+ *   vertices [B, V, 3], joints [B, J, 3]: each may be NULL and is then not computed.
+ * One launch, no atomics.  B or V equal to 0: success, nothing is launched; K = 0 copies the template.  flags: none
+ * defined, must be 0.
+ * Backward: grad_vertices [B, V, 3] and grad_joints [B, J, 3], each may be NULL (zero), -> grad_template and
+ * grad_coefficients (shaped like the operands); each may be NULL and is then not computed; those given are fully written,
+ * an operand shared by the scenes receiving the sum over the scenes.  The directions, the regressor and joint_directions
+ * are constants: they receive no gradient.  grad_template gathers grad_joints over the regressor's inverted index (CSC):
+ * column_offsets [V + 1], column_joints and column_weights, the non-zeros ordered by vertex, then joint.  grad_coefficients
+ * needs `scratch`, caller-owned, of dirt_blend_scratch_bytes(B, V, K) = 4 * 32 * ceil(B / 4) * ceil(K / 8) * ceil(3 V / 1024)
+ * bytes (0: invalid sizes): one row of partial sums per workgroup of the first launch, added by a second launch in a
+ * fixed order.  At most 3 launches; no atomics, the same bits on every run.  Failures: dirt_last_error().
+ */
+#define DIRT_BLEND_MAX_SHAPES 4096
+#define DIRT_BLEND_MAX_VERTICES (1 << 26)
+#define DIRT_BLEND_MAX_JOINTS 256 /* DIRT_KINEMATICS_MAX_JOINTS: what the next stage takes */
+#define DIRT_BLEND_MAX_ENTRIES (1 << 30) /* the regressor's non-zeros: their offsets are int32 */
+size_t dirt_blend_scratch_bytes(long long B, long long V, long long K);
+int dirt_blend_forward(const float *template_vertices, int template_scenes, const float *coefficients,
+                       int coefficient_scenes, const float *directions, long long stride, const int32_t *row_offsets,
+                       const int32_t *row_vertices, const float *row_weights, const float *joint_directions,
+                       float *vertices, float *joints, long long B, long long V, int K, int Ks, int J, unsigned flags,
+                       void *stream);
+int dirt_blend_backward(int template_scenes, int coefficient_scenes, const float *directions, long long stride,
+                        const int32_t *column_offsets, const int32_t *column_joints, const float *column_weights,
+                        const float *joint_directions, const float *grad_vertices, const float *grad_joints,
+                        float *grad_template, float *grad_coefficients, void *scratch, size_t scratch_bytes, long long B,
+                        long long V, int K, int Ks, int J, unsigned flags, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
