@@ -18,11 +18,12 @@ zeros, with sums whose order the BLAS library chooses; here every sum has a fixe
 import torch
 
 from . import _lib
+from . import _stage
 from . import matrices
-from . import rasterise_ops as _ops
+from ._stage import ptr as _ptr
 
 
-class BlendShapes:
+class BlendShapes(_stage.StageIndex):
     """The direction table of a model, its joint regressor and what the kernels read of them, built once.
 
     directions: float32 [K, V, 3], 0 <= K <= 4096, V <= 2^26, on any one device.
@@ -76,10 +77,7 @@ class BlendShapes:
         by_joint, by_vertex = torch.nonzero(R), torch.nonzero(R.t())
         if by_joint.shape[0] > _lib.BLEND_MAX_ENTRIES:
             raise ValueError('BlendShapes: the joint_regressor has %d non-zeros, at most %d' % (by_joint.shape[0], _lib.BLEND_MAX_ENTRIES))
-        row_offsets = torch.zeros(J + 1, dtype=torch.int64, device=dev)
-        row_offsets[1:] = torch.cumsum(torch.bincount(by_joint[:, 0], minlength=J), 0)
-        column_offsets = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-        column_offsets[1:] = torch.cumsum(torch.bincount(by_vertex[:, 0], minlength=V), 0)
+        row_offsets, column_offsets = _stage.sort_offsets(by_joint[:, 0], J), _stage.sort_offsets(by_vertex[:, 0], V)
         self.num_shapes, self.num_vertices, self.num_joints, self.joint_shapes, self.stride = K, V, J, Ks, stride
         self.packed = packed
         self.row_offsets, self.row_vertices = row_offsets.to(torch.int32), by_joint[:, 1].to(torch.int32).contiguous()
@@ -89,18 +87,6 @@ class BlendShapes:
         self.joint_directions = torch.einsum('jv,kvc->kjc', R.double(), directions[:Ks].double()).to(torch.float32).contiguous()
 
     _TENSORS = ('packed', 'row_offsets', 'row_vertices', 'row_weights', 'column_offsets', 'column_joints', 'column_weights', 'joint_directions')
-
-    @property
-    def device(self):
-        return self.packed.device
-
-    def to(self, device):
-        """The same table and indices with their tensors on `device` (nothing is rebuilt or checked again)."""
-        other = object.__new__(BlendShapes)
-        other.__dict__.update(self.__dict__)
-        for name in self._TENSORS:
-            setattr(other, name, getattr(self, name).to(device))
-        return other
 
     def directions(self):
         """The [K, V, 3] table, out of the packed copy."""
@@ -114,10 +100,6 @@ class BlendShapes:
         return out
 
 
-def _ptr(t):
-    return t.data_ptr() or None if t is not None else None
-
-
 class _BlendShapes(torch.autograd.Function):
     @staticmethod
     def forward(ctx, template, coefficients, shapes, meta):
@@ -128,12 +110,10 @@ class _BlendShapes(torch.autograd.Function):
         vertices = torch.empty(lead + (V, 3), dtype=torch.float32, device=dev)
         joints = torch.empty(lead + (J, 3), dtype=torch.float32, device=dev)
         if B * V:
-            with _ops._on_device(dev):
-                rc = lib.dirt_blend_forward(_ptr(template), 1 if template.dim() == 2 else B, _ptr(coefficients), 1 if coefficients.dim() == 1 else B,
-                                            _ptr(shapes.packed), shapes.stride, shapes.row_offsets.data_ptr(), _ptr(shapes.row_vertices),
-                                            _ptr(shapes.row_weights), _ptr(shapes.joint_directions), vertices.data_ptr(), _ptr(joints), B, V, K,
-                                            shapes.joint_shapes, J, 0, _ops._stream_handle(dev))
-            _lib.check(rc)
+            _stage.call(lib.dirt_blend_forward, dev, _ptr(template), 1 if template.dim() == 2 else B, _ptr(coefficients),
+                        1 if coefficients.dim() == 1 else B, _ptr(shapes.packed), shapes.stride, shapes.row_offsets.data_ptr(),
+                        _ptr(shapes.row_vertices), _ptr(shapes.row_weights), _ptr(shapes.joint_directions), vertices.data_ptr(), _ptr(joints),
+                        B, V, K, shapes.joint_shapes, J, 0)
         else:
             joints.zero_()   # no vertex: every sum is empty
         ctx.shapes, ctx.meta = shapes, meta
@@ -149,19 +129,16 @@ class _BlendShapes(torch.autograd.Function):
         B, V, K, J, batched = ctx.meta
         dev = shapes.device
         want = ctx.needs_input_grad[:2]
-        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
+        # (what _stage.grad_outputs makes, from the shapes: no operand is kept for the backward)
         grads = [torch.empty(s, dtype=torch.float32, device=dev) if on else None for s, on in zip(ctx.operand_shapes, want)]
         if not B * V:
             return tuple(g.zero_() if g is not None else None for g in grads) + (None, None)
-        gv, gj = (None if g is None else g.to(torch.float32).contiguous() for g in (grad_vertices, grad_joints))
+        gv, gj = _stage.float32_contiguous(grad_vertices, grad_joints)
         nbytes = lib.dirt_blend_scratch_bytes(B, V, K) if want[1] and K else 0
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-        with _ops._on_device(dev):
-            rc = lib.dirt_blend_backward(1 if len(ctx.operand_shapes[0]) == 2 else B, 1 if len(ctx.operand_shapes[1]) == 1 else B, _ptr(shapes.packed),
-                                         shapes.stride, shapes.column_offsets.data_ptr(), _ptr(shapes.column_joints), _ptr(shapes.column_weights),
-                                         _ptr(shapes.joint_directions), _ptr(gv), _ptr(gj), _ptr(grads[0]), _ptr(grads[1]), _ptr(scratch), nbytes,
-                                         B, V, K, shapes.joint_shapes, J, 0, _ops._stream_handle(dev))
-        _lib.check(rc)
+        _stage.call(lib.dirt_blend_backward, dev, 1 if len(ctx.operand_shapes[0]) == 2 else B, 1 if len(ctx.operand_shapes[1]) == 1 else B,
+                    _ptr(shapes.packed), shapes.stride, shapes.column_offsets.data_ptr(), _ptr(shapes.column_joints), _ptr(shapes.column_weights),
+                    _ptr(shapes.joint_directions), _ptr(gv), _ptr(gj), _ptr(grads[0]), _ptr(grads[1]), _ptr(_stage.scratch(dev, nbytes)), nbytes,
+                    B, V, K, shapes.joint_shapes, J, 0)
         return tuple(grads) + (None, None)
 
 
@@ -171,26 +148,11 @@ def _check_arguments(template, coefficients, shapes):
     if not isinstance(shapes, BlendShapes):
         raise ValueError('blend_shapes expects a BlendShapes (build it once per model), got %r' % type(shapes).__name__)
     V, K = shapes.num_vertices, shapes.num_shapes
-    if not isinstance(template, torch.Tensor) or template.dim() not in (2, 3) or tuple(template.shape[-2:]) != (V, 3):
-        raise ValueError('template must have shape [%d, 3] or [B, %d, 3], got %s' % (V, V, tuple(getattr(template, 'shape', ())),))
-    if template.dtype != torch.float32:
-        raise ValueError('template must be float32, got %s' % template.dtype)
-    c = coefficients
-    if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2) or int(c.shape[-1]) != K:
-        raise ValueError('coefficients must have shape [%d] or [B, %d], got %s' % (K, K, tuple(getattr(c, 'shape', ())),))
-    if c.dtype != torch.float32:
-        raise ValueError('coefficients must be float32, got %s' % c.dtype)
-    if c.device != template.device:
-        raise ValueError('coefficients is on %s, the template on %s' % (c.device, template.device))
-    if shapes.device != template.device:
-        raise ValueError('blend_shapes: the BlendShapes is on %s, the template on %s (use shapes.to(device))' % (shapes.device, template.device))
-    scenes = [int(t.shape[0]) for t, d in ((template, 3), (c, 2)) if t.dim() == d]
-    if len(scenes) == 2 and scenes[0] != scenes[1]:
-        raise ValueError('blend_shapes: %d scenes of template, %d of coefficients' % tuple(scenes))
-    B = scenes[0] if scenes else 1
-    if B > 65535:
-        raise ValueError('blend_shapes: %d scenes, at most 65535' % B)
-    return B, V, K, shapes.num_joints, bool(scenes)
+    _stage.check_operand('template', template, (V, 3))
+    _stage.check_operand('coefficients', coefficients, (K,), template, 'template')
+    _stage.check_index_device('blend_shapes', 'BlendShapes', 'shapes', shapes, 'template', template)
+    B, batched = _stage.scene_count('blend_shapes', ('template', template, 3), ('coefficients', coefficients, 2))
+    return B, V, K, shapes.num_joints, batched
 
 
 def blend_shapes(template, coefficients, shapes):
@@ -210,8 +172,7 @@ def blend_shapes(template, coefficients, shapes):
     shared by the scenes receives the sum over the scenes.  The directions and the regressor are constants: they receive no
     gradient.  No atomics.  Nothing in a call synchronises with the host."""
     meta = _check_arguments(template, coefficients, shapes)
-    if not template.is_cuda:
-        raise RuntimeError('dirt_amd.blendshapes.blend_shapes runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(template, 'dirt_amd.blendshapes.blend_shapes')
     return _BlendShapes.apply(template.contiguous(), coefficients.contiguous(), shapes, meta)
 
 

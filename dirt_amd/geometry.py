@@ -14,7 +14,7 @@ inverted index here: no atomics, one launch, and the same bits on every run.
 import torch
 
 from . import _lib
-from . import rasterise_ops as _ops
+from . import _stage
 
 _WANT = ('clip', 'world', 'normals')
 # Lists of more than this many entries are summed by a whole wave instead of their vertex's lane; None: the library's
@@ -22,7 +22,7 @@ _WANT = ('clip', 'world', 'normals')
 LONG_LIST = None
 
 
-class MeshTopology:
+class MeshTopology(_stage.StageIndex):
     """The faces of a mesh and their inverted index, built once (topology is constant across a fitting loop).
 
     faces: int32 / int64 [F, 3] on any device; num_vertices: V.  Indices outside [0, V), another shape or dtype raise
@@ -43,28 +43,14 @@ class MeshTopology:
         if num_vertices > _lib.GEOM_MAX_VERTICES or faces.shape[0] > _lib.GEOM_MAX_FACES:
             raise ValueError('MeshTopology: at most %d vertices and %d faces' % (_lib.GEOM_MAX_VERTICES, _lib.GEOM_MAX_FACES))
         flat = faces.reshape(-1).long()   # position 3 * face + corner
-        if flat.numel():
-            lo, hi = (int(x) for x in torch.stack([flat.min(), flat.max()]).cpu())
-            if lo < 0 or hi >= num_vertices:
-                raise ValueError('MeshTopology: faces name vertices %d..%d, outside [0, %d)' % (lo, hi, num_vertices))
+        _stage.check_index_range(flat, num_vertices, 'MeshTopology: faces name vertices %d..%d, outside [0, %d)')
         # a stable sort of the positions by vertex keeps them in order of face, then corner
         entries = torch.argsort(flat, stable=True).to(torch.int32)
-        counts = torch.bincount(flat, minlength=num_vertices)
-        offsets = torch.zeros(num_vertices + 1, dtype=torch.int64, device=faces.device)
-        offsets[1:] = torch.cumsum(counts, 0)
+        offsets = _stage.sort_offsets(flat, num_vertices)
         self.num_vertices, self.num_faces = num_vertices, int(faces.shape[0])
         self.faces, self.offsets, self.entries = faces.to(torch.int32).contiguous(), offsets.to(torch.int32), entries.contiguous()
 
-    @property
-    def device(self):
-        return self.faces.device
-
-    def to(self, device):
-        """The same topology with its three tensors on `device` (nothing is rebuilt or checked again)."""
-        other = object.__new__(MeshTopology)
-        other.num_vertices, other.num_faces = self.num_vertices, self.num_faces
-        other.faces, other.offsets, other.entries = (t.to(device) for t in (self.faces, self.offsets, self.entries))
-        return other
+    _TENSORS = ('faces', 'offsets', 'entries')
 
 
 class _VertexStage(torch.autograd.Function):
@@ -77,11 +63,9 @@ class _VertexStage(torch.autograd.Function):
         clip, world, normals = (torch.empty(lead + (w,), dtype=torch.float32, device=dev) if name in want else None
                                 for name, w in (('clip', 4), ('world', 4), ('normals', 3)))
         if B * V:
-            with _ops._on_device(dev):
-                rc = lib.dirt_geometry_forward(vertices.data_ptr(), C, *_index_pointers(topology), *_matrix_arguments(model, view_projection),
-                                               *(t.data_ptr() if t is not None else None for t in (clip, world, normals)),
-                                               B, V, topology.num_faces, flags, _ops._stream_handle(dev))
-            _lib.check(rc)
+            _stage.call(lib.dirt_geometry_forward, dev, vertices.data_ptr(), C, *_index_pointers(topology),
+                        *_matrix_arguments(model, view_projection), *(t.data_ptr() if t is not None else None for t in (clip, world, normals)),
+                        B, V, topology.num_faces, flags)
         ctx.save_for_backward(vertices, model, view_projection)
         ctx.topology, ctx.meta = topology, meta
         return clip, world, normals
@@ -94,23 +78,16 @@ class _VertexStage(torch.autograd.Function):
         topology = ctx.topology
         B, V, C, batched, want, flags = ctx.meta
         dev = vertices.device
-        want_v, want_m, want_p = ctx.needs_input_grad[:3]
-        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
-        grad_v = torch.empty_like(vertices) if want_v else None
-        grad_m = torch.empty_like(model) if want_m else None
-        grad_p = torch.empty_like(view_projection) if want_p else None
+        grads = _stage.grad_outputs((vertices, model, view_projection), ctx.needs_input_grad[:3], not B * V)
         if not B * V:
-            return grad_v, grad_m.zero_() if want_m else None, grad_p.zero_() if want_p else None, None, None
-        grads = [g.to(torch.float32).contiguous() if g is not None else None for g in (grad_clip, grad_world, grad_normals)]
+            return tuple(grads) + (None, None)
+        incoming = _stage.float32_contiguous(grad_clip, grad_world, grad_normals)
         nbytes = lib.dirt_geometry_scratch_bytes(B, V, topology.num_faces)
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        with _ops._on_device(dev):
-            rc = lib.dirt_geometry_backward(vertices.data_ptr(), C, *_index_pointers(topology), *_matrix_arguments(model, view_projection),
-                                            *(g.data_ptr() if g is not None else None for g in grads),
-                                            *(g.data_ptr() if g is not None else None for g in (grad_v, grad_m, grad_p)),
-                                            scratch.data_ptr(), nbytes, B, V, topology.num_faces, flags, _ops._stream_handle(dev))
-        _lib.check(rc)
-        return grad_v, grad_m, grad_p, None, None
+        _stage.call(lib.dirt_geometry_backward, dev, vertices.data_ptr(), C, *_index_pointers(topology),
+                    *_matrix_arguments(model, view_projection), *(g.data_ptr() if g is not None else None for g in incoming),
+                    *(g.data_ptr() if g is not None else None for g in grads), _stage.ptr(_stage.scratch(dev, nbytes)), nbytes,
+                    B, V, topology.num_faces, flags)
+        return tuple(grads) + (None, None)
 
 
 def _index_pointers(topology):
@@ -135,24 +112,18 @@ def _check_arguments(vertices, topology, model, view_projection, pre_split, want
         raise ValueError('vertex_stage expects float32 vertices, got %s' % vertices.dtype)
     if not isinstance(topology, MeshTopology):
         raise ValueError('vertex_stage expects a MeshTopology (build it once per mesh), got %r' % type(topology).__name__)
-    batched = vertices.dim() == 3
-    B, V, C = (int(vertices.shape[0]) if batched else 1), int(vertices.shape[-2]), int(vertices.shape[-1])
+    V, C = int(vertices.shape[-2]), int(vertices.shape[-1])
     if V != topology.num_vertices:
         raise ValueError('vertex_stage: %d vertices, the topology was built for %d' % (V, topology.num_vertices))
-    if B > 65535:
-        raise ValueError('vertex_stage: %d scenes, at most 65535' % B)
-    if topology.device != vertices.device:
-        raise ValueError('vertex_stage: the topology is on %s, the vertices on %s (use topology.to(device))' % (topology.device, vertices.device))
+    B, batched = _stage.scene_count('vertex_stage', ('vertices', vertices, 3))
+    _stage.check_index_device('vertex_stage', 'topology', 'topology', topology, 'vertices', vertices)
     for name, m in (('model', model), ('view_projection', view_projection)):
         if m is None:
             continue
-        shapes = [(4, 4), (B, 4, 4)] if batched else [(4, 4)]
+        shapes = [(4, 4), (B, 4, 4)] if batched else [(4, 4)]   # (a matrix per scene only with vertices per scene, and then B is known)
         if not isinstance(m, torch.Tensor) or tuple(m.shape) not in shapes:
             raise ValueError('%s must have shape %s, got %s' % (name, ' or '.join(str(list(s)) for s in shapes), tuple(getattr(m, 'shape', ()))))
-        if m.dtype != torch.float32:
-            raise ValueError('%s must be float32, got %s' % (name, m.dtype))
-        if m.device != vertices.device:
-            raise ValueError('%s is on %s, the vertices on %s' % (name, m.device, vertices.device))
+        _stage.check_float32(name, m, vertices, 'vertices')
     if isinstance(want, str) or any(w not in _WANT for w in want):
         raise ValueError('want must be a sequence of %s, got %r' % (_WANT, want))
     want = tuple(w for w in _WANT if w in want)
@@ -177,8 +148,7 @@ def vertex_stage(vertices, topology, model=None, view_projection=None, *, pre_sp
     matrices) are those of torch's autograd for it: the norm of a zero vector has gradient 0, so a zero-area face passes
     d n / 1e-12 to its cross product and nothing through the norm.  Nothing in a call synchronises with the host."""
     meta = _check_arguments(vertices, topology, model, view_projection, pre_split, want)
-    if not vertices.is_cuda:
-        raise RuntimeError('dirt_amd.geometry.vertex_stage runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(vertices, 'dirt_amd.geometry.vertex_stage')
     v = vertices.contiguous()
     model, view_projection = (m.contiguous() if m is not None else None for m in (model, view_projection))
     return _VertexStage.apply(v, model, view_projection, topology, meta)

@@ -15,10 +15,11 @@ on every run.
 import torch
 
 from . import _lib
-from . import rasterise_ops as _ops
+from . import _stage
+from ._stage import ptr as _ptr
 
 
-class Skeleton:
+class Skeleton(_stage.StageIndex):
     """The tree (or forest) of a rig and the index the kernels walk, built once.
 
     parents: a sequence of ints or an integer tensor [J], 0 <= J <= 256.  parents[j] == -1 marks a root (several are
@@ -61,29 +62,15 @@ class Skeleton:
         levels = max(depth) + 1 if J else 0
         # stable sorts keep the joints of a level, and the children of a parent, in order of index
         order = torch.argsort(dep, stable=True)
-        level_offsets = torch.zeros(levels + 1, dtype=torch.int64, device=dev)
-        level_offsets[1:] = torch.cumsum(torch.bincount(dep, minlength=levels), 0)
+        level_offsets = _stage.sort_offsets(dep, levels)
         children = torch.nonzero(par >= 0)[:, 0]
         child_entries = children[torch.argsort(par[children], stable=True)]
-        child_offsets = torch.zeros(J + 1, dtype=torch.int64, device=dev)
-        child_offsets[1:] = torch.cumsum(torch.bincount(par[children], minlength=J), 0)
+        child_offsets = _stage.sort_offsets(par[children], J)
         self.num_joints, self.num_levels = J, levels
         self.parents, self.order, self.level_offsets = par.to(torch.int32), order.to(torch.int32).contiguous(), level_offsets.to(torch.int32)
         self.child_entries, self.child_offsets = child_entries.to(torch.int32).contiguous(), child_offsets.to(torch.int32)
 
     _TENSORS = ('parents', 'order', 'level_offsets', 'child_entries', 'child_offsets')
-
-    @property
-    def device(self):
-        return self.parents.device
-
-    def to(self, device):
-        """The same skeleton with its tensors on `device` (nothing is rebuilt or checked again)."""
-        other = object.__new__(Skeleton)
-        other.__dict__.update(self.__dict__)
-        for name in self._TENSORS:
-            setattr(other, name, getattr(self, name).to(device))
-        return other
 
 
 def _index_operands(skeleton):
@@ -106,10 +93,8 @@ class _PoseSkeleton(torch.autograd.Function):
         transforms = torch.empty(lead + (J, 4, 4), dtype=torch.float32, device=dev)
         posed_joints = torch.empty(lead + (J, 3), dtype=torch.float32, device=dev)
         if B * J:
-            with _ops._on_device(dev):
-                rc = lib.dirt_kinematics_forward(*_operands(rotations, joints), *_index_operands(skeleton), transforms.data_ptr(),
-                                                 posed_joints.data_ptr(), B, J, 0, _ops._stream_handle(dev))
-            _lib.check(rc)
+            _stage.call(lib.dirt_kinematics_forward, dev, *_operands(rotations, joints), *_index_operands(skeleton), transforms.data_ptr(),
+                        posed_joints.data_ptr(), B, J, 0)
         ctx.save_for_backward(rotations, joints)
         ctx.skeleton, ctx.meta = skeleton, meta
         ctx.set_materialize_grads(False)   # an output nobody used arrives as None and contributes nothing
@@ -124,20 +109,14 @@ class _PoseSkeleton(torch.autograd.Function):
         B, J, batched = ctx.meta
         dev = rotations.device
         want = ctx.needs_input_grad[:2]
-        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
-        grads = [torch.empty_like(t) if on else None for t, on in zip((rotations, joints), want)]
+        grads = _stage.grad_outputs((rotations, joints), want, not B * J)
         if not B * J:
-            return tuple(g.zero_() if g is not None else None for g in grads) + (None, None)
-        gT, gq = (None if g is None else g.to(torch.float32).contiguous() for g in (grad_transforms, grad_posed_joints))
+            return tuple(grads) + (None, None)
+        incoming = _stage.float32_contiguous(grad_transforms, grad_posed_joints)
         shared = B > 1 and any(on and t.dim() == 2 for t, on in zip((rotations, joints), want))
         nbytes = lib.dirt_kinematics_scratch_bytes(B, J) if shared else 0
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-        with _ops._on_device(dev):
-            rc = lib.dirt_kinematics_backward(*_operands(rotations, joints), *_index_operands(skeleton), skeleton.child_entries.data_ptr() or None,
-                                              skeleton.child_offsets.data_ptr(), *(g.data_ptr() if g is not None else None for g in (gT, gq)),
-                                              *(g.data_ptr() if g is not None else None for g in grads),
-                                              scratch.data_ptr() if scratch is not None else None, nbytes, B, J, 0, _ops._stream_handle(dev))
-        _lib.check(rc)
+        _stage.call(lib.dirt_kinematics_backward, dev, *_operands(rotations, joints), *_index_operands(skeleton), _ptr(skeleton.child_entries),
+                    skeleton.child_offsets.data_ptr(), *map(_ptr, incoming), *map(_ptr, grads), _ptr(_stage.scratch(dev, nbytes)), nbytes, B, J, 0)
         return tuple(grads) + (None, None)
 
 
@@ -147,22 +126,11 @@ def _check_arguments(rotations, joints, skeleton):
     if not isinstance(skeleton, Skeleton):
         raise ValueError('pose_skeleton expects a Skeleton (build it once per rig), got %r' % type(skeleton).__name__)
     J = skeleton.num_joints
-    for name, t in (('rotations', rotations), ('joints', joints)):
-        if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (J, 3):
-            raise ValueError('%s must have shape [%d, 3] or [B, %d, 3], got %s' % (name, J, J, tuple(getattr(t, 'shape', ())),))
-        if t.dtype != torch.float32:
-            raise ValueError('%s must be float32, got %s' % (name, t.dtype))
-    if joints.device != rotations.device:
-        raise ValueError('joints is on %s, the rotations on %s' % (joints.device, rotations.device))
-    if skeleton.device != rotations.device:
-        raise ValueError('pose_skeleton: the Skeleton is on %s, the rotations on %s (use skeleton.to(device))' % (skeleton.device, rotations.device))
-    scenes = [int(t.shape[0]) for t in (rotations, joints) if t.dim() == 3]
-    if len(scenes) == 2 and scenes[0] != scenes[1]:
-        raise ValueError('pose_skeleton: %d scenes of rotations, %d of joints' % tuple(scenes))
-    B = scenes[0] if scenes else 1
-    if B > 65535:
-        raise ValueError('pose_skeleton: %d scenes, at most 65535' % B)
-    return B, J, bool(scenes)
+    _stage.check_operand('rotations', rotations, (J, 3))
+    _stage.check_operand('joints', joints, (J, 3), rotations, 'rotations')
+    _stage.check_index_device('pose_skeleton', 'Skeleton', 'skeleton', skeleton, 'rotations', rotations)
+    B, batched = _stage.scene_count('pose_skeleton', ('rotations', rotations, 3), ('joints', joints, 3))
+    return B, J, batched
 
 
 def pose_skeleton(rotations, joints, skeleton):
@@ -183,6 +151,5 @@ def pose_skeleton(rotations, joints, skeleton):
     rotation vector included) are those of torch's autograd for this composition; an operand shared by the scenes receives
     the sum over the scenes.  No atomics: the same bits on every run.  Nothing in a call synchronises with the host."""
     meta = _check_arguments(rotations, joints, skeleton)
-    if not rotations.is_cuda:
-        raise RuntimeError('dirt_amd.kinematics.pose_skeleton runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(rotations, 'dirt_amd.kinematics.pose_skeleton')
     return _PoseSkeleton.apply(rotations.contiguous(), joints.contiguous(), skeleton, meta)

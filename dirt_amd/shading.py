@@ -13,7 +13,8 @@ import numbers
 import torch
 
 from . import _lib
-from . import rasterise_ops as _ops
+from . import _stage
+from ._stage import ptr as _ptr
 
 _KINDS = _lib.SHADE_KINDS
 _NEEDS_POSITIONS = ('specular_directional', 'diffuse_point')
@@ -81,10 +82,8 @@ class _ShadeGBuffer(torch.autograd.Function):
         out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
         block = block.contiguous()
         if scenes * pixels:
-            with _ops._on_device(gbuffer.device):
-                rc = lib.dirt_shade_forward(gbuffer.data_ptr(), block.data_ptr(), out.data_ptr(), scenes, pixels, cg, *offsets,
-                                            int(block.shape[0]), nl, kinds, sided, lo, hi, flags, _ops._stream_handle(gbuffer.device))
-            _lib.check(rc)
+            _stage.call(lib.dirt_shade_forward, gbuffer.device, gbuffer.data_ptr(), block.data_ptr(), out.data_ptr(), scenes, pixels, cg,
+                        *offsets, int(block.shape[0]), nl, kinds, sided, lo, hi, flags)
         ctx.save_for_backward(gbuffer, block)
         ctx.meta = meta
         return out
@@ -96,21 +95,15 @@ class _ShadeGBuffer(torch.autograd.Function):
         gbuffer, block = ctx.saved_tensors
         scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = ctx.meta
         dev = gbuffer.device
-        want_g, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_p = ctx.needs_input_grad[1]
+        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
         if not scenes * pixels:
-            return (torch.zeros_like(gbuffer) if want_g else None, torch.zeros_like(block) if want_p else None, None)
+            return grad_g, grad_p, None
         grad_out = grad_out.to(torch.float32).contiguous()
-        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
-        grad_g = torch.empty_like(gbuffer) if want_g else None
-        grad_p = torch.empty_like(block) if want_p else None
         nbytes = lib.dirt_shade_scratch_bytes(scenes, pixels, nl) if want_p else 0
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if want_p else None
-        with _ops._on_device(dev):
-            rc = lib.dirt_shade_backward(gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(),
-                                         grad_g.data_ptr() if want_g else None, grad_p.data_ptr() if want_p else None,
-                                         scratch.data_ptr() if want_p else None, nbytes, scenes, pixels, cg, *offsets,
-                                         int(block.shape[0]), nl, kinds, sided, lo, hi, flags, _ops._stream_handle(dev))
-        _lib.check(rc)
+        _stage.call(lib.dirt_shade_backward, dev, gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_p),
+                    _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg, *offsets, int(block.shape[0]), nl, kinds, sided, lo, hi,
+                    flags)
         return grad_g, grad_p, None
 
 
@@ -136,8 +129,7 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
     gradient at their edges, abs gives 0 at 0).  A shininess below 1 at a zero cosine (0 * inf in torch) is not defined."""
     if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
         raise ValueError('shade_gbuffer expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
-    if not gbuffer.is_cuda:
-        raise RuntimeError('dirt_amd.shading.shade_gbuffer runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer')
     lights = list(lights)
     offsets, kinds, sided, lo, hi, flags, const, tensors = _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
                                                                             camera_position, background, clamp)

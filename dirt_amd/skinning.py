@@ -15,7 +15,7 @@ composition) is a gather over the inverted index here: no atomics, and the same 
 import torch
 
 from . import _lib
-from . import rasterise_ops as _ops
+from . import _stage
 
 # Entries of a chunk of the inverted index: the bone-gradient kernel gives one workgroup of 256 lanes to every (chunk,
 # scene), so a bone named by n entries is spread over ceil(n / CHUNK) workgroups: four entries per lane.  Measured (the last
@@ -25,7 +25,7 @@ from . import rasterise_ops as _ops
 CHUNK = 1024
 
 
-class SkinWeights:
+class SkinWeights(_stage.StageIndex):
     """The skinning weights of a mesh and the inverted index of their bone indices, built once.
 
     bone_indices: int32 / int64 [V, K], bone_weights: float32 [V, K], 1 <= K <= 8, on any one device; num_bones: J.
@@ -66,19 +66,13 @@ class SkinWeights:
             raise ValueError('SkinWeights: %d vertices x %d influences, at most %d entries' % (V, K, _lib.SKIN_MAX_ENTRIES))
         dev = bone_indices.device
         flat = bone_indices.reshape(-1).long()   # position v * K + k
-        if flat.numel():
-            lo, hi = (int(x) for x in torch.stack([flat.min(), flat.max()]).cpu())
-            if lo < 0 or hi >= num_bones:
-                raise ValueError('SkinWeights: bone_indices name bones %d..%d, outside [0, %d)' % (lo, hi, num_bones))
+        _stage.check_index_range(flat, num_bones, 'SkinWeights: bone_indices name bones %d..%d, outside [0, %d)')
         # a stable sort of the positions by bone keeps every bone's entries in order of position
         entries = torch.argsort(flat, stable=True).to(torch.int32)
-        counts = torch.bincount(flat, minlength=num_bones)
-        offsets = torch.zeros(num_bones + 1, dtype=torch.int64, device=dev)
-        offsets[1:] = torch.cumsum(counts, 0)
-        per_bone = (counts + (chunk - 1)) // chunk
-        chunk_offsets = torch.zeros(num_bones + 1, dtype=torch.int64, device=dev)
-        chunk_offsets[1:] = torch.cumsum(per_bone, 0)
+        offsets = _stage.sort_offsets(flat, num_bones)
+        per_bone = (torch.diff(offsets) + (chunk - 1)) // chunk
         bone = torch.repeat_interleave(torch.arange(num_bones, device=dev), per_bone)             # the bone of every chunk
+        chunk_offsets = _stage.sort_offsets(bone, num_bones)
         begin = offsets[bone] + (torch.arange(bone.numel(), device=dev) - chunk_offsets[bone]) * chunk
         end = torch.minimum(begin + chunk, offsets[bone + 1])
         self.num_vertices, self.num_bones, self.influences, self.chunk = V, num_bones, K, chunk
@@ -113,18 +107,6 @@ class SkinWeights:
         w = torch.where(kept, torch.gather(weights, 1, order), torch.zeros((), dtype=weights.dtype, device=weights.device))
         return cls(torch.where(kept, order, torch.zeros_like(order)).to(torch.int32), w, J, chunk)
 
-    @property
-    def device(self):
-        return self.bone_indices.device
-
-    def to(self, device):
-        """The same weights and index with their tensors on `device` (nothing is rebuilt or checked again)."""
-        other = object.__new__(SkinWeights)
-        other.__dict__.update(self.__dict__)
-        for name in self._TENSORS:
-            setattr(other, name, getattr(self, name).to(device))
-        return other
-
     def dense(self, weights=None):
         """The [V, J] matrix of the weights (of `weights` [V, K] instead, if given): slots naming one bone add up."""
         w = self.bone_weights if weights is None else weights
@@ -140,10 +122,8 @@ class _SkinVertices(torch.autograd.Function):
         dev = vertices.device
         posed = torch.empty(((B, V, 3) if batched else (V, 3)), dtype=torch.float32, device=dev)
         if B * V:
-            with _ops._on_device(dev):
-                rc = lib.dirt_skin_forward(*_operands(vertices, transforms, weights, skin), posed.data_ptr(), B, V, skin.influences,
-                                           skin.num_bones, 0, _ops._stream_handle(dev))
-            _lib.check(rc)
+            _stage.call(lib.dirt_skin_forward, dev, *_operands(vertices, transforms, weights, skin), posed.data_ptr(), B, V, skin.influences,
+                        skin.num_bones, 0)
         ctx.save_for_backward(vertices, transforms, weights)
         ctx.skin, ctx.meta = skin, meta
         return posed
@@ -157,20 +137,15 @@ class _SkinVertices(torch.autograd.Function):
         B, V, C, batched = ctx.meta
         dev = vertices.device
         want = ctx.needs_input_grad[:3]
-        # fresh outputs on every call: the node may be differentiated again (retain_graph=True)
-        grads = [torch.empty_like(t) if on else None for t, on in zip((vertices, transforms, weights), want)]
+        grads = _stage.grad_outputs((vertices, transforms, weights), want, not B * V)
         if not B * V:
-            return tuple(g.zero_() if g is not None else None for g in grads) + (None, None)
+            return tuple(grads) + (None, None)
         g = grad_posed.to(torch.float32).contiguous()
         nbytes = lib.dirt_skin_scratch_bytes(B, skin.num_chunks) if want[1] else 0
-        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-        with _ops._on_device(dev):
-            rc = lib.dirt_skin_backward(*_operands(vertices, transforms, weights, skin), skin.entries.data_ptr() or None,
-                                        skin.chunk_table.data_ptr() or None, skin.chunk_offsets.data_ptr(), g.data_ptr(),
-                                        *(t.data_ptr() if t is not None else None for t in grads),
-                                        scratch.data_ptr() if scratch is not None else None, nbytes, B, V, skin.influences, skin.num_bones,
-                                        skin.num_chunks, 0, _ops._stream_handle(dev))
-        _lib.check(rc)
+        _stage.call(lib.dirt_skin_backward, dev, *_operands(vertices, transforms, weights, skin), skin.entries.data_ptr() or None,
+                    skin.chunk_table.data_ptr() or None, skin.chunk_offsets.data_ptr(), g.data_ptr(),
+                    *(t.data_ptr() if t is not None else None for t in grads), _stage.ptr(_stage.scratch(dev, nbytes)), nbytes,
+                    B, V, skin.influences, skin.num_bones, skin.num_chunks, 0)
         return tuple(grads) + (None, None)
 
 
@@ -192,30 +167,14 @@ def _check_arguments(vertices, skin, bone_transforms, weights):
     V, C = int(vertices.shape[-2]), int(vertices.shape[-1])
     if V != skin.num_vertices:
         raise ValueError('skin_vertices: %d vertices, the SkinWeights was built for %d' % (V, skin.num_vertices))
-    if skin.device != vertices.device:
-        raise ValueError('skin_vertices: the SkinWeights is on %s, the vertices on %s (use skin.to(device))' % (skin.device, vertices.device))
-    T = bone_transforms
-    if not isinstance(T, torch.Tensor) or T.dim() not in (3, 4) or tuple(T.shape[-3:]) != (skin.num_bones, 4, 4):
-        raise ValueError('bone_transforms must have shape [%d, 4, 4] or [B, %d, 4, 4], got %s'
-                         % (skin.num_bones, skin.num_bones, tuple(getattr(T, 'shape', ())),))
-    if T.dtype != torch.float32:
-        raise ValueError('bone_transforms must be float32, got %s' % T.dtype)
-    if T.device != vertices.device:
-        raise ValueError('bone_transforms is on %s, the vertices on %s' % (T.device, vertices.device))
-    scenes = [int(t.shape[0]) for t, d in ((vertices, 3), (T, 4)) if t.dim() == d]
-    if len(scenes) == 2 and scenes[0] != scenes[1]:
-        raise ValueError('skin_vertices: %d scenes of vertices, %d of bone_transforms' % tuple(scenes))
-    B = scenes[0] if scenes else 1
-    if B > 65535:
-        raise ValueError('skin_vertices: %d scenes, at most 65535' % B)
+    _stage.check_index_device('skin_vertices', 'SkinWeights', 'skin', skin, 'vertices', vertices)
+    _stage.check_operand('bone_transforms', bone_transforms, (skin.num_bones, 4, 4), vertices, 'vertices')
+    B, batched = _stage.scene_count('skin_vertices', ('vertices', vertices, 3), ('bone_transforms', bone_transforms, 4))
     if weights is not None:
-        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (V, skin.influences):
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (V, skin.influences):   # (never per scene: no [B, ..] form)
             raise ValueError('weights must have shape [%d, %d], got %s' % (V, skin.influences, tuple(getattr(weights, 'shape', ())),))
-        if weights.dtype != torch.float32:
-            raise ValueError('weights must be float32, got %s' % weights.dtype)
-        if weights.device != vertices.device:
-            raise ValueError('weights is on %s, the vertices on %s' % (weights.device, vertices.device))
-    return B, V, C, bool(scenes)
+        _stage.check_float32('weights', weights, vertices, 'vertices')
+    return B, V, C, batched
 
 
 def skin_vertices(vertices, skin, bone_transforms, weights=None):
@@ -235,7 +194,6 @@ def skin_vertices(vertices, skin, bone_transforms, weights=None):
     an operand shared by the scenes receives the sum over the scenes.  No atomics: the same bits on every run.  Nothing
     in a call synchronises with the host."""
     meta = _check_arguments(vertices, skin, bone_transforms, weights)
-    if not vertices.is_cuda:
-        raise RuntimeError('dirt_amd.skinning.skin_vertices runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(vertices, 'dirt_amd.skinning.skin_vertices')
     w = skin.bone_weights if weights is None else weights.contiguous()
     return _SkinVertices.apply(vertices.contiguous(), bone_transforms.contiguous(), w, skin, meta)
