@@ -240,8 +240,9 @@ int dirt_texture_sample_backward_image(const float* texture, const float* uvs, c
     if (rc) return rc;
     if (n > 0 && (!grad_out || !grad_texture)) TEX_FAIL("%s: grad_out / grad_texture is NULL", who);
     if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
+    if (!grad_texture) return dirt::stage_ok(report);   // (n == 0 without a gradient buffer: nothing to clear, nothing to launch)
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(grad_texture, 0, sizeof(float) * (size_t)Ht * Wt * Ct, s);
+    hipError_t e = dirt::clear_floats(grad_texture, (long long)Ht * Wt * Ct, s);
     if (e == hipSuccess) {
         dirt::TexParams p{};
         p.texture = texture; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.guv_stride = grad_uv_stride;

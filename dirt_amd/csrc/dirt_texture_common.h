@@ -64,4 +64,29 @@ __device__ __forceinline__ Taps bilinear_taps(float row, float col, int Ht, int 
     return t;
 }
 
+// ---- p[0 .. n) = 0 on `stream`: how the backward entry points clear the buffer their kernels add into.  A kernel of the
+// library's own, NOT hipMemsetAsync: captured in a graph (hipGraph, torch.cuda.graph), the runtime's memset node cleared the
+// buffer on the first replay only -- from the second replay on, one float in four came back holding the float count
+// (tests/test_texture_edges.py::test_a_captured_lookup_and_backward_replay_on_new_textures).  The floats before the first
+// 16-byte boundary (`head`, < 4) and after the last one are stored one by one, the rest as float4.
+static __global__ __launch_bounds__(256) void clear_floats_kernel(float* __restrict__ p, long long n, int head)
+{
+    const long long lane = (long long)blockIdx.x * 256 + threadIdx.x, lanes = (long long)gridDim.x * 256;
+    const long long quads = (n - head) / 4, tail = head + quads * 4;
+    float4* __restrict__ q = reinterpret_cast<float4*>(p + head);
+    for (long long i = lane; i < quads; i += lanes) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < head) p[lane] = 0.f;
+    if (lane < n - tail) p[tail + lane] = 0.f;
+}
+
+inline hipError_t clear_floats(float* p, long long n, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const long long to_boundary = (4 - (long long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u)) & 3;
+    const int head = (int)(to_boundary < n ? to_boundary : n);
+    const long long quads = (n - head) / 4;
+    hipLaunchKernelGGL(clear_floats_kernel, dim3(capped_blocks(quads > 0 ? quads : 1)), dim3(256), 0, stream, p, n, head);
+    return hipGetLastError();
+}
+
 }  // namespace dirt

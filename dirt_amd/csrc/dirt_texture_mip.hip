@@ -553,7 +553,7 @@ int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, con
     if (tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long long pyr_floats = p.off[levels - 1] + (long long)dirt::mip_dim(Ht, levels - 1) * dirt::mip_dim(Wt, levels - 1) * Ct;
-    hipError_t e = hipMemsetAsync(grad_pyramid, 0, sizeof(float) * (size_t)pyr_floats, s);
+    hipError_t e = dirt::clear_floats(grad_pyramid, pyr_floats, s);
     if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (n > 0) {
         const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);

@@ -217,8 +217,12 @@ int dirt_state_grad_buffers(void *workspace, size_t workspace_bytes, int B, int 
  * the last texel is used.
  *   texture [Ht,Wt,Ct]; uvs: n pairs (u, v) `uv_stride` >= 2 floats apart -- read in place from a G-buffer [H,W,C] with
  *   uv_stride = C and the pointer at the u channel; out [n,Ct].
- * Backward: grad_out [n,Ct] -> grad_texture [Ht,Wt,Ct] (cleared by the call, then accumulated with float atomics) and
- * grad_uvs (n pairs `grad_uv_stride` apart; may be NULL).
+ * Backward: grad_out [n,Ct] -> grad_texture [Ht,Wt,Ct] (cleared by the call -- by a kernel on `stream`, so the call can be
+ * captured in a graph -- then accumulated with float atomics) and grad_uvs (n pairs `grad_uv_stride` >= 2 apart, only those
+ * two floats of each pair written; may be NULL, and grad_uv_stride is then ignored).  Float32 denormals are kept, in the
+ * look-up and in both gradients.  n == 0 is not an error: nothing is read, every pointer may be NULL, and a grad_texture
+ * that is given is still cleared.  Arguments are checked before any device work; a pixel grid with more than 2^31 - 1 rows,
+ * columns or tiles is refused with DIRT_E_HIP after the clear.
  * dirt_texture_last_error(): thread-local description of the last failure of these calls (and of the trilinear ones below).
  */
 #define DIRT_TEX_CLAMP 1u   /* mode 'clamp' instead of 'repeat' (samples/textured.py:21-24) */
