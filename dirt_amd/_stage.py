@@ -1,5 +1,5 @@
 """What the Python wrappers of the fused stages share (geometry, skinning, kinematics, blendshapes; of shading the call and
-the backward plumbing).  Private: the stages' own modules are the interface.
+the backward plumbing; of the texture look-up the call, the pointers and the CPU refusal).  Private: the stages' own modules are the interface.
 """
 import torch
 
@@ -92,11 +92,11 @@ def ptr(t):
     return t.data_ptr() or None if t is not None else None
 
 
-def call(function, dev, *arguments):
-    """One call into the C ABI: on `dev`, with its current stream as the last argument; a failure raises (_lib.check)."""
+def call(function, dev, *arguments, check=_lib.check):
+    """One call into the C ABI: on `dev`, with its current stream as the last argument; a failure raises (`check`; texture has its own)."""
     with _ops._on_device(dev):
         rc = function(*arguments, _ops._stream_handle(dev))
-    _lib.check(rc)
+    check(rc)
 
 
 def grad_outputs(operands, want, empty_call):

@@ -54,40 +54,25 @@ __global__ __launch_bounds__(256) void texture_forward_kernel(TexParams p)
             float a[NV], b[NV], c[NV], d[NV], o[NV];
             load_ch<CT>(tl, Ct, a, ch); load_ch<CT>(tr, Ct, b, ch); load_ch<CT>(bl, Ct, c, ch); load_ch<CT>(br, Ct, d, ch);
 #pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                // top_left * (1 - fc) * (1 - fr) + top_right * fc * (1 - fr) + bottom_left * (1 - fc) * fr + bottom_right * fc * fr
-                const float ta = (a[j] * k.wc0) * k.wr0, tb = (b[j] * k.fc) * k.wr0, tc = (c[j] * k.wc0) * k.fr, td = (d[j] * k.fc) * k.fr;
-                o[j] = ((ta + tb) + tc) + td;
-            }
+            for (int j = 0; j < NV; ++j) o[j] = bilinear_blend(a[j], b[j], c[j], d[j], k);
             store_ch<CT>(out, o, ch);
         }
     }
 }
 
-// ---- backward: a workgroup takes a TW x TH tile of the pixel grid (16 x 16 of an image `cols` wide; 256 x 1 of a flat list).
-// The texels a tile's look-ups touch are a compact patch of the texture wherever (u, v) is smooth (a G-buffer: a rendered
-// surface): the four products of every pixel are summed in an LDS copy of that patch (ds_add_f32) and each texel of the
-// patch goes to memory ONCE, as one float atomic per channel, consecutive lanes on consecutive floats.  The reference's
-// gather_nd gradient -- and rounds 2-5 here -- scatter 4 Ct atomics per pixel straight at the texture: at 16 pixels per texel
-// that is 64 same-address atomics per texel and channel, serialised by the memory system (2.8 ms for a 2048 x 2048 frame);
-// tiles whose patch does not fit (a (u, v) seam, `repeat` wrapping inside the tile) still do.
-constexpr int TEX_PATCH = 1600;   // texels of a tile's patch held in LDS (x Ct floats: 19 KB at 3 channels)
-
+// ---- backward: the tile scheme of dirt_texture_common.h with one patch, the bounding box of the tile's taps
 template <int CT>
 __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int rows, int cols, int tw, int th, int tiles_x)
 {
-    constexpr int NV = CT ? CT : 1;
     constexpr int LCT = CT ? CT : 4;                 // channels per LDS patch pass (any count: passes of 4)
     __shared__ float s_acc[TEX_PATCH * LCT];
     __shared__ int s_box[4];                         // rmin, rmax, cmin, cmax of the tile's taps
     const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0, nearest = (p.flags & DIRT_TEX_NEAREST) != 0;
     const int Ct = CT ? CT : p.Ct;
     const int tid = threadIdx.x;
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int px = tile_x * tw + tid % tw, py = tile_y * th + tid / tw;
-    const bool active = px < cols && py < rows;
-    const long long i = active ? (long long)py * cols + px : 0;
-    if (tid == 0) { s_box[0] = 0x7fffffff; s_box[1] = -1; s_box[2] = 0x7fffffff; s_box[3] = -1; }
+    long long i;
+    const bool active = tile_pixel(tid, tw, th, tiles_x, rows, cols, i);
+    if (tid == 0) box_clear(s_box);
     float u = 0.f, v = 0.f;
     if (active) { u = p.uvs[i * p.uv_stride]; v = p.uvs[i * p.uv_stride + 1]; }
     float row, col, drow_dv, dcol_du;
@@ -98,47 +83,40 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
         k.fr = 0.f; k.fc = 0.f; k.wr0 = 1.f; k.wc0 = 1.f;
     }
     __syncthreads();
-    if (active) {
-        atomicMin(&s_box[0], k.r0); atomicMax(&s_box[1], k.r1);
-        atomicMin(&s_box[2], k.c0); atomicMax(&s_box[3], k.c1);
-    }
+    if (active) box_add(s_box, k);
     __syncthreads();
     const int rmin = s_box[0], cmin = s_box[2];
     const int bh = s_box[1] - rmin + 1, bw = s_box[3] - cmin + 1;
     const bool patch = bh > 0 && bw > 0 && (long long)bh * bw <= TEX_PATCH;   // (workgroup-uniform)
-    const float w_tl = k.wc0 * k.wr0, w_tr = k.fc * k.wr0, w_bl = k.wc0 * k.fr, w_br = k.fc * k.fr;
+    const Four<float> w = {k.wc0 * k.wr0, k.fc * k.wr0, k.wc0 * k.fr, k.fc * k.fr};
     float d_fr = 0.f, d_fc = 0.f;
     const float* __restrict__ gout = p.grad_out + i * Ct;
     for (int c0 = 0; c0 < Ct; c0 += LCT) {          // (CT = 1, 3, 4: one pass; any other count: passes of four channels)
         const int nc = CT ? CT : min(LCT, Ct - c0);
         if (patch) {
-            for (int e = tid; e < bh * bw * LCT; e += 256) s_acc[e] = 0.f;
+            clear_patch(s_acc, bh * bw * LCT, tid);
             __syncthreads();
         }
         if (active) {
             float g[LCT];
-            if constexpr (CT != 0) { float q[NV]; load_ch<CT>(gout, Ct, q); for (int j = 0; j < NV; ++j) g[j] = q[j]; }
-            else { for (int j = 0; j < LCT; ++j) g[j] = j < nc ? gout[c0 + j] : 0.f; }
-            const size_t o_tl = ((size_t)k.r0 * p.Wt + k.c0) * Ct + c0, o_tr = ((size_t)k.r0 * p.Wt + k.c1) * Ct + c0;
-            const size_t o_bl = ((size_t)k.r1 * p.Wt + k.c0) * Ct + c0, o_br = ((size_t)k.r1 * p.Wt + k.c1) * Ct + c0;
-            const int l_tl = ((k.r0 - rmin) * bw + (k.c0 - cmin)) * LCT, l_tr = ((k.r0 - rmin) * bw + (k.c1 - cmin)) * LCT;
-            const int l_bl = ((k.r1 - rmin) * bw + (k.c0 - cmin)) * LCT, l_br = ((k.r1 - rmin) * bw + (k.c1 - cmin)) * LCT;
+            load_grad_out<CT>(gout, Ct, c0, nc, g);
+            // (tap_offsets written out: through the function, <4> came out with other registers and its autograd figure 0.1 % past the margin)
+            const Four<size_t> o = {((size_t)k.r0 * p.Wt + k.c0) * Ct + c0, ((size_t)k.r0 * p.Wt + k.c1) * Ct + c0, ((size_t)k.r1 * p.Wt + k.c0) * Ct + c0, ((size_t)k.r1 * p.Wt + k.c1) * Ct + c0};
+            const Four<int> l = patch_offsets(k, rmin, cmin, bw, LCT);
 #pragma unroll
             for (int j = 0; j < LCT; ++j) {
                 if (j >= nc) break;
                 if (!nearest) {
-                    const float t_tl = p.texture[o_tl + j], t_tr = p.texture[o_tr + j], t_bl = p.texture[o_bl + j], t_br = p.texture[o_br + j];
-                    d_fr += g[j] * ((t_bl - t_tl) * k.wc0 + (t_br - t_tr) * k.fc);
-                    d_fc += g[j] * ((t_tr - t_tl) * k.wr0 + (t_br - t_bl) * k.fr);
+                    float e_fr, e_fc;
+                    tap_gradients(g[j], {p.texture[o.tl + j], p.texture[o.tr + j], p.texture[o.bl + j], p.texture[o.br + j]}, k, e_fr, e_fc);
+                    d_fr += e_fr; d_fc += e_fc;
                 }
                 if (patch) {
-                    if (nearest) { atomicAdd(&s_acc[l_tl + j], g[j]); continue; }
-                    atomicAdd(&s_acc[l_tl + j], g[j] * w_tl); atomicAdd(&s_acc[l_tr + j], g[j] * w_tr);
-                    atomicAdd(&s_acc[l_bl + j], g[j] * w_bl); atomicAdd(&s_acc[l_br + j], g[j] * w_br);
+                    if (nearest) { atomicAdd(&s_acc[l.tl + j], g[j]); continue; }
+                    add_taps(s_acc, l, j, g[j], w);
                 } else {
-                    if (nearest) { atomicAdd(&p.grad_texture[o_tl + j], g[j]); continue; }
-                    atomicAdd(&p.grad_texture[o_tl + j], g[j] * w_tl); atomicAdd(&p.grad_texture[o_tr + j], g[j] * w_tr);
-                    atomicAdd(&p.grad_texture[o_bl + j], g[j] * w_bl); atomicAdd(&p.grad_texture[o_br + j], g[j] * w_br);
+                    if (nearest) { atomicAdd(&p.grad_texture[o.tl + j], g[j]); continue; }
+                    add_taps(p.grad_texture, o, j, g[j], w);
                 }
             }
         }
@@ -148,10 +126,7 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
             for (int e = tid; e < bh * bw * LCT; e += 256) {
                 const float val = s_acc[e];
                 const int j = e % LCT, t = e / LCT;
-                if (val != 0.f && j < nc) {
-                    const int pr = t / bw, pc = t - pr * bw;
-                    atomicAdd(&p.grad_texture[((size_t)(rmin + pr) * p.Wt + (cmin + pc)) * Ct + c0 + j], val);
-                }
+                if (val != 0.f && j < nc) atomicAdd(&p.grad_texture[box_texel(t, rmin, cmin, bw, p.Wt, Ct) + c0 + j], val);
             }
             __syncthreads();
         }
@@ -175,14 +150,11 @@ hipError_t launch_texture_forward(const TexParams& p, hipStream_t stream)
 hipError_t launch_texture_backward(const TexParams& p, long long rows, long long cols, hipStream_t stream)
 {
     if (p.n == 0) return hipSuccess;
-    // the pixel grid: an image `cols` wide in 16 x 16 tiles, or a flat list (rows == 1) in runs of 256
-    const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
-    const long long tiles_x = (cols + tw - 1) / tw, tiles_y = (rows + th - 1) / th;
-    if (tiles_x * tiles_y > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
+    const TileGrid t = tile_grid(rows, cols);
+    if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) return hipErrorInvalidValue;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.grad_out) & 15u) == 0;
     dispatch_channels(p.Ct, a16, [&](auto ct) {
-        hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, grid, block, 0, stream, p, (int)rows, (int)cols, tw, th, (int)tiles_x);
+        hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
     });
     return hipGetLastError();
 }
@@ -234,10 +206,10 @@ int dirt_texture_sample_backward_image(const float* texture, const float* uvs, c
                                        void* stream)
 {
     const char* who = "dirt_texture_sample_backward";   // (the flat-list entry point's name: it forwards here)
-    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) TEX_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
-    const long long n = rows * cols;
-    int rc = tex_check(who, texture, uvs, n, Ht, Wt, Ct, uv_stride);
+    int rc = dirt::check_pixel_grid(who, rows, cols);
+    if (!rc) rc = tex_check(who, texture, uvs, rows * cols, Ht, Wt, Ct, uv_stride);
     if (rc) return rc;
+    const long long n = rows * cols;
     if (n > 0 && (!grad_out || !grad_texture)) TEX_FAIL("%s: grad_out / grad_texture is NULL", who);
     if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
     if (!grad_texture) return dirt::stage_ok(report);   // (n == 0 without a gradient buffer: nothing to clear, nothing to launch)

@@ -1,6 +1,6 @@
-// dirt_texture_common.h -- the per-look-up arithmetic shared by the texture kernels (dirt_texture.hip: nearest / bilinear;
-// dirt_texture_mip.hip: trilinear over a mip pyramid): (u, v) -> fractional (row, column) index of the reference's
-// samples/textured.py:16-26, the four bilinear taps of :36-60 and the channel-vector loads / stores.
+// dirt_texture_common.h -- what the texture kernels share (dirt_texture.hip: nearest / bilinear; dirt_texture_mip.hip: trilinear over a
+// mip pyramid).  Per look-up: (u, v) -> fractional (row, column) index of the reference's samples/textured.py:16-26, the four bilinear taps of
+// :36-60, the channel-vector loads / stores, the blend.  The pieces of the backward tile scheme.  Host: the pixel grid, the clear of a buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +62,89 @@ __device__ __forceinline__ Taps bilinear_taps(float row, float col, int Ht, int 
     t.c0 = texel_index(fc0, Wt); t.c1 = min(t.c0 + 1, Wt - 1);
     t.wc0 = 1.f - t.fc; t.wr0 = 1.f - t.fr;
     return t;
+}
+
+// The bilinear blend of four texels' values at the taps `k` (samples/textured.py:50-60), in the reference's order of operations.  (The
+// four loads stay with the forward kernels: sampling through one function cost texture_forward_kernel<3> and <4> 2 us, 7 %.)
+__device__ __forceinline__ float bilinear_blend(float tl, float tr, float bl, float br, const Taps& k)
+{
+    const float ta = (tl * k.wc0) * k.wr0, tb = (tr * k.fc) * k.wr0, tc = (bl * k.wc0) * k.fr, td = (br * k.fc) * k.fr;
+    return ((ta + tb) + tc) + td;
+}
+
+// ---- backward: a workgroup takes a tw x th tile of the pixel grid (16 x 16 of an image `cols` wide; 256 x 1 of a flat list).  The
+// texels a tile's look-ups touch are a compact patch of the texture wherever (u, v) is smooth (a G-buffer: a rendered surface): the
+// four products of every pixel are summed in an LDS copy of that patch (ds_add_f32) and each texel of the patch goes to memory ONCE,
+// as one float atomic per channel, consecutive lanes on consecutive floats.  Scattering 4 Ct atomics per pixel straight at the texture,
+// as the reference's gather_nd gradient does, is 64 same-address atomics per texel and channel at 16 pixels per texel, serialised by
+// the memory system (2.8 ms for a 2048 x 2048 frame); tiles whose patch does not fit (a (u, v) seam, `repeat` wrapping) still do.
+constexpr int TEX_PATCH = 1600;   // texels of a tile's patch (trilinear: of its two levels' patches) held in LDS (x Ct floats: 19 KB at 3 channels)
+
+// lane `tid` of tile blockIdx.x -> the index i of its pixel in the rows x cols grid (of integer type I); false, and i = 0, outside it
+template <class I> __device__ __forceinline__ bool tile_pixel(int tid, int tw, int th, int tiles_x, I rows, I cols, long long& i)
+{
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const I px = (I)tile_x * tw + tid % tw, py = (I)tile_y * th + tid / tw;
+    i = px < cols && py < rows ? (long long)py * cols + px : 0;
+    return px < cols && py < rows;
+}
+
+// the bounding box (rmin, rmax, cmin, cmax) of tap sets, in LDS: empty, and grown by one set
+__device__ __forceinline__ void box_clear(int* box) { box[0] = 0x7fffffff; box[1] = -1; box[2] = 0x7fffffff; box[3] = -1; }
+__device__ __forceinline__ void box_add(int* box, const Taps k) { atomicMin(&box[0], k.r0); atomicMax(&box[1], k.r1); atomicMin(&box[2], k.c0); atomicMax(&box[3], k.c1); }
+
+// grad_out of a pixel from channel c0 on, as registers: CT = 1, 3, 4: all CT channels; any count: four, zero from the nc-th on
+template <int CT> __device__ __forceinline__ void load_grad_out(const float* __restrict__ gout, int Ct, int c0, int nc, float (&g)[CT ? CT : 4])
+{
+    if constexpr (CT != 0) load_ch<CT>(gout, Ct, g);
+    else { for (int j = 0; j < 4; ++j) g[j] = j < nc ? gout[c0 + j] : 0.f; }
+}
+
+// The four texels of a tap set as offsets: of channel c0 in a level W texels wide; in the LDS patch (lct floats a texel) of the box at (rmin, cmin), bw wide
+template <class T> struct Four { T tl, tr, bl, br; };
+__device__ __forceinline__ Four<size_t> tap_offsets(const Taps k, int W, int Ct, int c0)
+{
+    return {((size_t)k.r0 * W + k.c0) * Ct + c0, ((size_t)k.r0 * W + k.c1) * Ct + c0, ((size_t)k.r1 * W + k.c0) * Ct + c0, ((size_t)k.r1 * W + k.c1) * Ct + c0};
+}
+__device__ __forceinline__ Four<int> patch_offsets(const Taps k, int rmin, int cmin, int bw, int lct)
+{
+    return {((k.r0 - rmin) * bw + (k.c0 - cmin)) * lct, ((k.r0 - rmin) * bw + (k.c1 - cmin)) * lct, ((k.r1 - rmin) * bw + (k.c0 - cmin)) * lct, ((k.r1 - rmin) * bw + (k.c1 - cmin)) * lct};
+}
+
+// g * d sample / d fr and g * d sample / d fc of one channel with the texels `t`
+__device__ __forceinline__ void tap_gradients(float g, const Four<float>& t, const Taps k, float& e_fr, float& e_fc)
+{
+    e_fr = g * ((t.bl - t.tl) * k.wc0 + (t.br - t.tr) * k.fc);
+    e_fc = g * ((t.tr - t.tl) * k.wr0 + (t.br - t.bl) * k.fr);
+}
+
+// g times a tap set's four weights, added to channel j at its four offsets of `dst`: the LDS patch, or the gradient in memory
+template <class T> __device__ __forceinline__ void add_taps(float* dst, const Four<T>& o, int j, float g, const Four<float>& w)
+{
+    atomicAdd(&dst[o.tl + j], g * w.tl); atomicAdd(&dst[o.tr + j], g * w.tr); atomicAdd(&dst[o.bl + j], g * w.bl); atomicAdd(&dst[o.br + j], g * w.br);
+}
+
+__device__ __forceinline__ void clear_patch(float* s_acc, int n, int tid) { for (int e = tid; e < n; e += 256) s_acc[e] = 0.f; }
+
+// Texel t of the patch of the box with top-left (rmin, cmin) and width bw -> its offset in a level W texels wide.  The flush loop
+// stays in each kernel: handed this mapping as a function, the trilinear kernel (one of two boxes) kept its boxes in 4 KB of LDS.
+__device__ __forceinline__ size_t box_texel(int t, int rmin, int cmin, int bw, int W, int Ct)
+{
+    const int pr = t / bw, pc = t - pr * bw;
+    return ((size_t)(rmin + pr) * W + (cmin + pc)) * Ct;
+}
+
+// ---- host: the pixel grid.  rows x cols must not overflow; its tiles of 256 pixels are 16 x 16 of an image, 256 x 1 of a flat list (rows == 1)
+inline int check_pixel_grid(const char* who, long long rows, long long cols)
+{
+    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) TEX_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
+    return DIRT_OK;
+}
+struct TileGrid { int tw, th; long long tiles_x, tiles; };
+inline TileGrid tile_grid(long long rows, long long cols)
+{
+    const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
+    return {tw, th, (cols + tw - 1) / tw, ((cols + tw - 1) / tw) * ((rows + th - 1) / th)};
 }
 
 // ---- p[0 .. n) = 0 on `stream`: how the backward entry points clear the buffer their kernels add into.  A kernel of the

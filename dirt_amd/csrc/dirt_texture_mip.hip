@@ -39,7 +39,6 @@ namespace dirt {
 
 constexpr int MIP_MAX = 32;        // levels of a pyramid (a dimension of 2^31 halves 31 times)
 constexpr int MIP_TILE_LEVELS = 5; // levels reduced in LDS by the block kernel (a 32 x 32 block -> 1 x 1)
-constexpr int MIP_PATCH = 1600;    // texels of a tile's patches (both levels) held in LDS
 
 struct MipParams {
     const float* pyr;        // packed pyramid (level 0 = the texture)
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(256) void mip_collapse_kernel(const float* __restri
     }
 }
 
-// the bilinear sample of one level, the arithmetic of texture_forward_kernel
+// the bilinear sample of one level [*, Wk, Ct]
 template <int CT>
 __device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk, const Taps& k, int Ct, int ch, float (&o)[CT ? CT : 1])
 {
@@ -221,10 +220,7 @@ __device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk
     load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c0) * Ct, Ct, a, ch); load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c1) * Ct, Ct, b, ch);
     load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c0) * Ct, Ct, c, ch); load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c1) * Ct, Ct, d, ch);
 #pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const float ta = (a[j] * k.wc0) * k.wr0, tb = (b[j] * k.fc) * k.wr0, tc = (c[j] * k.wc0) * k.fr, td = (d[j] * k.fc) * k.fr;
-        o[j] = ((ta + tb) + tc) + td;
-    }
+    for (int j = 0; j < NV; ++j) o[j] = bilinear_blend(a[j], b[j], c[j], d[j], k);
 }
 
 // the taps of level l for a level-0 index (and the derivatives of the level's index)
@@ -274,27 +270,23 @@ __global__ __launch_bounds__(256) void mip_forward_kernel(MipParams p)
     }
 }
 
-// ---- backward: the 16 x 16-tile scheme of texture_backward_kernel with one LDS patch per touched level.  A lane's look-up
-// has up to two tap sets: level l with weight 1 - f and level l + 1 with weight f (when f != 0).  Where the tile's sets span at
-// most two adjacent levels and both bounding boxes fit MIP_PATCH texels together, each set sums into its level's patch and
-// every patch texel goes to the scratch pyramid once; otherwise the sets scatter float atomics straight into it.
+// ---- backward: the tile scheme of dirt_texture_common.h with one LDS patch per touched level.  A lane's look-up has up to two tap
+// sets: level l with weight 1 - f and level l + 1 with weight f (when f != 0).  Where the tile's sets span at most two adjacent levels
+// and both bounding boxes fit TEX_PATCH texels together, each set sums into its level's patch; otherwise they scatter into memory.
 template <int CT>
 __global__ __launch_bounds__(256) void mip_backward_kernel(MipParams p, int tw, int th, int tiles_x)
 {
-    constexpr int NV = CT ? CT : 1;
     constexpr int LCT = CT ? CT : 4;
-    __shared__ float s_acc[MIP_PATCH * LCT];
+    __shared__ float s_acc[TEX_PATCH * LCT];
     __shared__ int s_box[10];   // lmin, lmax, then rmin, rmax, cmin, cmax of the two levels' taps
     const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0;
     const int Ct = CT ? CT : p.Ct;
     const int tid = threadIdx.x;
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const long long px = (long long)tile_x * tw + tid % tw, py = (long long)tile_y * th + tid / tw;
-    const bool active = px < p.cols && py < p.rows;
-    const long long i = active ? py * p.cols + px : 0;
+    long long i;
+    const bool active = tile_pixel(tid, tw, th, tiles_x, p.rows, p.cols, i);
     if (tid == 0) {
         s_box[0] = 0x7fffffff; s_box[1] = -1;
-        for (int s = 0; s < 2; ++s) { s_box[2 + 4 * s] = 0x7fffffff; s_box[3 + 4 * s] = -1; s_box[4 + 4 * s] = 0x7fffffff; s_box[5 + 4 * s] = -1; }
+        for (int s = 0; s < 2; ++s) box_clear(&s_box[2 + 4 * s]);
     }
     float u = 0.f, v = 0.f;
     if (active) mip_uv(p, i, u, v);
@@ -318,12 +310,8 @@ __global__ __launch_bounds__(256) void mip_backward_kernel(MipParams p, int tw, 
     const int lmin = s_box[0];
     const bool span = s_box[1] - lmin <= 1;
     if (active && span) {
-        int* b0 = &s_box[2 + 4 * (l - lmin)];
-        atomicMin(&b0[0], k0.r0); atomicMax(&b0[1], k0.r1); atomicMin(&b0[2], k0.c0); atomicMax(&b0[3], k0.c1);
-        if (two) {
-            int* b1 = &s_box[2 + 4 * (l + 1 - lmin)];
-            atomicMin(&b1[0], k1.r0); atomicMax(&b1[1], k1.r1); atomicMin(&b1[2], k1.c0); atomicMax(&b1[3], k1.c1);
-        }
+        box_add(&s_box[2 + 4 * (l - lmin)], k0);
+        if (two) box_add(&s_box[2 + 4 * (l + 1 - lmin)], k1);
     }
     __syncthreads();
     int pr0[2], pc0[2], pw[2], pbase[2];
@@ -333,76 +321,62 @@ __global__ __launch_bounds__(256) void mip_backward_kernel(MipParams p, int tw, 
         pr0[s] = s_box[2 + 4 * s]; pc0[s] = s_box[4 + 4 * s];
         pw[s] = bh > 0 && bw > 0 ? bw : 0;
         pbase[s] = used;
-        if (bh > 0 && bw > 0) used += (long long)bh * bw > MIP_PATCH ? MIP_PATCH + 1 : bh * bw;
+        if (bh > 0 && bw > 0) used += (long long)bh * bw > TEX_PATCH ? TEX_PATCH + 1 : bh * bw;
     }
-    const bool patch = span && used > 0 && used <= MIP_PATCH;   // (workgroup-uniform)
+    const bool patch = span && used > 0 && used <= TEX_PATCH;   // (workgroup-uniform)
     const float w0 = 1.f - f;
     const float* __restrict__ lv0 = p.pyr + p.off[l];
     const float* __restrict__ lv1 = p.pyr + p.off[read1 ? l + 1 : l];
     float* __restrict__ gv0 = p.grad_pyr + p.off[l];
     float* __restrict__ gv1 = p.grad_pyr + p.off[two ? l + 1 : l];
     const int W0 = mip_dim(p.Wt, l), W1 = mip_dim(p.Wt, read1 ? l + 1 : l);
-    const int s0 = l - lmin, s1 = l + 1 - lmin;
     float d_fr0 = 0.f, d_fc0 = 0.f, d_fr1 = 0.f, d_fc1 = 0.f, d_lod = 0.f;
     const float* __restrict__ gout = p.grad_out + i * Ct;
     for (int c0 = 0; c0 < Ct; c0 += LCT) {
         const int nc = CT ? CT : min(LCT, Ct - c0);
         if (patch) {
-            for (int e = tid; e < used * LCT; e += 256) s_acc[e] = 0.f;
+            clear_patch(s_acc, used * LCT, tid);
             __syncthreads();
         }
         if (active) {
             float g[LCT];
-            if constexpr (CT != 0) { float q[NV]; load_ch<CT>(gout, Ct, q); for (int j = 0; j < NV; ++j) g[j] = q[j]; }
-            else { for (int j = 0; j < LCT; ++j) g[j] = j < nc ? gout[c0 + j] : 0.f; }
+            load_grad_out<CT>(gout, Ct, c0, nc, g);
             for (int set = 0; set < 2; ++set) {
-                if (set == 1 && !read1) break;
+                if (set == 1 && !read1) break;   // the second set: read for the lod gradient, added only where it carries weight
                 const Taps& k = set ? k1 : k0;
                 const float* __restrict__ lv = set ? lv1 : lv0;
                 float* __restrict__ gv = set ? gv1 : gv0;
-                const int Wk = set ? W1 : W0;
                 const float w = set ? f : w0;
                 const bool scatter = set == 0 || two;
-                const int ps = set ? s1 : s0;
-                const float w_tl = (k.wc0 * k.wr0) * w, w_tr = (k.fc * k.wr0) * w, w_bl = (k.wc0 * k.fr) * w, w_br = (k.fc * k.fr) * w;
-                const size_t o_tl = ((size_t)k.r0 * Wk + k.c0) * Ct + c0, o_tr = ((size_t)k.r0 * Wk + k.c1) * Ct + c0;
-                const size_t o_bl = ((size_t)k.r1 * Wk + k.c0) * Ct + c0, o_br = ((size_t)k.r1 * Wk + k.c1) * Ct + c0;
-                int l_tl = 0, l_tr = 0, l_bl = 0, l_br = 0;
-                if (patch && scatter) {
-                    const int b = pbase[ps], r0 = pr0[ps], cc0 = pc0[ps], bw = pw[ps];
-                    l_tl = (b + (k.r0 - r0) * bw + (k.c0 - cc0)) * LCT; l_tr = (b + (k.r0 - r0) * bw + (k.c1 - cc0)) * LCT;
-                    l_bl = (b + (k.r1 - r0) * bw + (k.c0 - cc0)) * LCT; l_br = (b + (k.r1 - r0) * bw + (k.c1 - cc0)) * LCT;
-                }
+                const int ps = l + set - lmin;
+                const Four<float> wt = {(k.wc0 * k.wr0) * w, (k.fc * k.wr0) * w, (k.wc0 * k.fr) * w, (k.fc * k.fr) * w};
+                const Four<size_t> o = tap_offsets(k, set ? W1 : W0, Ct, c0);
+                Four<int> lo = {0, 0, 0, 0};
+                if (patch && scatter) lo = patch_offsets(k, pr0[ps], pc0[ps], pw[ps], LCT);
 #pragma unroll
                 for (int j = 0; j < LCT; ++j) {
                     if (j >= nc) break;
-                    const float t_tl = lv[o_tl + j], t_tr = lv[o_tr + j], t_bl = lv[o_bl + j], t_br = lv[o_br + j];
-                    const float e_fr = g[j] * ((t_bl - t_tl) * k.wc0 + (t_br - t_tr) * k.fc);
-                    const float e_fc = g[j] * ((t_tr - t_tl) * k.wr0 + (t_br - t_bl) * k.fr);
-                    const float smp = ((t_tl * k.wc0) * k.wr0 + (t_tr * k.fc) * k.wr0) + ((t_bl * k.wc0) * k.fr + (t_br * k.fc) * k.fr);
+                    const Four<float> t = {lv[o.tl + j], lv[o.tr + j], lv[o.bl + j], lv[o.br + j]};
+                    float e_fr, e_fc;
+                    tap_gradients(g[j], t, k, e_fr, e_fc);
+                    const float smp = ((t.tl * k.wc0) * k.wr0 + (t.tr * k.fc) * k.wr0) + ((t.bl * k.wc0) * k.fr + (t.br * k.fc) * k.fr);
                     if (set) { d_fr1 += e_fr; d_fc1 += e_fc; d_lod += g[j] * smp; }
                     else { d_fr0 += e_fr; d_fc0 += e_fc; d_lod -= g[j] * smp; }
                     if (!scatter) continue;
-                    if (patch) {
-                        atomicAdd(&s_acc[l_tl + j], g[j] * w_tl); atomicAdd(&s_acc[l_tr + j], g[j] * w_tr);
-                        atomicAdd(&s_acc[l_bl + j], g[j] * w_bl); atomicAdd(&s_acc[l_br + j], g[j] * w_br);
-                    } else {
-                        atomicAdd(&gv[o_tl + j], g[j] * w_tl); atomicAdd(&gv[o_tr + j], g[j] * w_tr);
-                        atomicAdd(&gv[o_bl + j], g[j] * w_bl); atomicAdd(&gv[o_br + j], g[j] * w_br);
-                    }
+                    if (patch) add_taps(s_acc + pbase[ps] * LCT, lo, j, g[j], wt);
+                    else add_taps(gv, o, j, g[j], wt);
                 }
             }
         }
         if (patch) {
             __syncthreads();
-            for (int e = tid; e < used * LCT; e += 256) {
+            for (int e = tid; e < used * LCT; e += 256) {   // (as texture_backward_kernel's; a texel lies in the first level's box or the second's)
                 const float val = s_acc[e];
                 const int j = e % LCT, t = e / LCT;
                 if (val != 0.f && j < nc) {
                     const int s = t >= pbase[1] && pw[1] > 0 ? 1 : 0;
-                    const int lt = t - pbase[s], r = lt / pw[s], c = lt - r * pw[s];
-                    const int lev = lmin + s;
-                    atomicAdd(&p.grad_pyr[p.off[lev] + ((size_t)(pr0[s] + r) * mip_dim(p.Wt, lev) + (pc0[s] + c)) * Ct + c0 + j], val);
+                    const int lev = lmin + s, W = mip_dim(p.Wt, lev);
+                    atomicAdd(&p.grad_pyr[p.off[lev] + box_texel(t - pbase[s], pr0[s], pc0[s], pw[s], W, Ct) + c0 + j], val);
                 }
             }
             __syncthreads();
@@ -437,6 +411,8 @@ void mip_offsets(MipParams& p)
     }
 }
 
+long long mip_floats(const MipParams& p) { return p.off[p.L - 1] + (long long)mip_dim(p.Ht, p.L - 1) * mip_dim(p.Wt, p.L - 1) * p.Ct; }
+
 }  // namespace dirt
 
 extern "C" {
@@ -449,7 +425,7 @@ int dirt_texture_mip_levels(int Ht, int Wt, int Ct, int max_level, long long* py
     dirt::MipParams p{};
     p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.L = dirt::mip_level_count(Ht, Wt, max_level);
     dirt::mip_offsets(p);
-    if (pyramid_floats) *pyramid_floats = p.L < dirt::MIP_MAX ? p.off[p.L] : p.off[p.L - 1] + (long long)dirt::mip_dim(Ht, p.L - 1) * dirt::mip_dim(Wt, p.L - 1) * Ct;
+    if (pyramid_floats) *pyramid_floats = dirt::mip_floats(p);
     dirt::stage_ok(report);
     return p.L;
 }
@@ -496,17 +472,18 @@ int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, in
 
 static int mip_sample_check(const char* who, const float* pyramid, const float* uvs, const float* lod, long long rows, long long cols,
                             int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride, const float* mask,
-                            dirt::MipParams& p)
+                            float lod_bias, unsigned flags, dirt::MipParams& p)
 {
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
+    if (!rc) rc = dirt::check_pixel_grid(who, rows, cols);
     if (rc) return rc;
-    if (rows < 0 || cols < 0 || (rows > 0 && cols > 0x7fffffffffffffffll / rows)) TEX_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
     if (image_rows < 1 || (rows > 0 && rows % image_rows)) TEX_FAIL("%s: image_rows=%d does not divide rows=%lld", who, image_rows, rows);
     if (uv_stride < 2) TEX_FAIL("%s: uv_stride < 2", who);
     if (mask && mask_stride < 1) TEX_FAIL("%s: mask_stride < 1", who);
     if (rows * cols > 0 && (!pyramid || !uvs)) TEX_FAIL("%s: pyramid / uvs is NULL", who);
+    if (flags & DIRT_TEX_NEAREST) TEX_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
     p.pyr = pyramid; p.uvs = uvs; p.lod = lod; p.mask = lod ? nullptr : mask; p.rows = rows; p.cols = cols; p.image_rows = image_rows;
-    p.uv_stride = uv_stride; p.mask_stride = mask_stride;
+    p.uv_stride = uv_stride; p.mask_stride = mask_stride; p.lod_bias = lod_bias; p.flags = flags;
     return DIRT_OK;
 }
 
@@ -516,13 +493,12 @@ int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, cons
 {
     const char* who = "dirt_texture_sample_mip_forward";
     dirt::MipParams p{};
-    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
+    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, lod_bias, flags, p);
     if (rc) return rc;
-    if (flags & DIRT_TEX_NEAREST) TEX_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
     const long long n = rows * cols;
     if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
     if (n == 0) return dirt::stage_ok(report);
-    p.lod_bias = lod_bias; p.flags = flags; p.out = out;
+    p.out = out;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
     dirt::dispatch_channels(Ct, a16, [&](auto ct) {
@@ -538,28 +514,23 @@ int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, con
 {
     const char* who = "dirt_texture_sample_mip_backward";
     dirt::MipParams p{};
-    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, p);
+    int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, lod_bias, flags, p);
     if (rc) return rc;
-    if (flags & DIRT_TEX_NEAREST) TEX_FAIL("%s: DIRT_TEX_NEAREST does not apply to a trilinear look-up", who);
     if (!grad_pyramid || !grad_texture) TEX_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
     const long long n = rows * cols;
     if (n > 0 && !grad_out) TEX_FAIL("%s: grad_out is NULL", who);
     if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
     if (grad_lod && !lod) TEX_FAIL("%s: grad_lod needs lod", who);
-    p.lod_bias = lod_bias; p.flags = flags; p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod;
-    p.guv_stride = grad_uv_stride;
-    const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
-    const long long tiles_x = (cols + tw - 1) / tw, tiles_y = (rows + th - 1) / th;
-    if (tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
+    p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod; p.guv_stride = grad_uv_stride;
+    const dirt::TileGrid t = dirt::tile_grid(rows, cols);
+    if (t.tiles > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long long pyr_floats = p.off[levels - 1] + (long long)dirt::mip_dim(Ht, levels - 1) * dirt::mip_dim(Wt, levels - 1) * Ct;
-    hipError_t e = dirt::clear_floats(grad_pyramid, pyr_floats, s);
+    hipError_t e = dirt::clear_floats(grad_pyramid, dirt::mip_floats(p), s);
     if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (n > 0) {
-        const dim3 grid((unsigned)(tiles_x * tiles_y)), block(256);
         const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
         dirt::dispatch_channels(Ct, a16, [&](auto ct) {
-            hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, grid, block, 0, s, p, tw, th, (int)tiles_x);
+            hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
         });
         e = hipGetLastError();
         if (e != hipSuccess) return dirt::stage_hip(report, who, e);

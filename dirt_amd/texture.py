@@ -9,11 +9,13 @@ the same values bit for bit.
 `filter='trilinear'` samples a mip pyramid (`mip_pyramid`) at a level of detail given per look-up or taken from the
 screen-space footprint of the (u, v) image (dirt_texture_mip.hip; specification in DESIGN.md §7)."""
 import ctypes
+import functools
+import math
 
 import torch
 
 from . import _lib
-from . import rasterise_ops as _ops
+from . import _stage
 
 
 def uvs_to_pixel_indices(uvs, texture_shape, mode='repeat'):
@@ -58,6 +60,36 @@ def _check(rc):
         raise ValueError(_lib.load().dirt_texture_last_error().decode())
 
 
+_call = functools.partial(_stage.call, check=_check)   # (entry point, device, its arguments but the stream): raises as `_check` says
+
+
+def _check_texture(texture, who):
+    if texture.dim() != 3:
+        raise ValueError('%s expects texture to be 3D [height, width, channels], got shape %s' % (who, tuple(texture.shape)))
+
+
+def _check_lookup(texture, uvs):
+    _check_texture(texture, 'sample_texture_uv')
+    if uvs.dim() < 1 or uvs.shape[-1] != 2:
+        raise ValueError('sample_texture_uv expects uvs of shape [..., 2], got %s' % (tuple(uvs.shape),))
+    if texture.device != uvs.device:
+        raise ValueError('texture and uvs must be on the same device (%s vs %s)' % (texture.device, uvs.device))
+
+
+def _check_max_level(max_level):
+    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
+        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+
+
+def _pixel_grid(uv_shape, footprint=False):
+    """The look-ups of a (u, v) shape as an image -> (rows, cols, image_rows): the last pixel axis is a row, everything before it stacks
+    rows ([H, W, 2]; [B, H, W, 2]); a flat [n, 2] list is one row.  `image_rows`: of each stacked image, for a `footprint` level of detail."""
+    n = math.prod(int(d) for d in uv_shape[:-1])
+    cols = int(uv_shape[-2]) if len(uv_shape) >= 3 else n
+    rows = n // cols if cols else 0
+    return rows, cols, int(uv_shape[-3]) if footprint and rows else 1
+
+
 def _pairs_in_place(uvs):
     """(tensor to pass, element stride between pairs) such that pair i starts at data_ptr + 4 * i * stride: a slice
     `gbuffer[..., a:a+2]` of a contiguous G-buffer is read in place, anything else is made contiguous."""
@@ -78,18 +110,12 @@ def _pairs_in_place(uvs):
 class _SampleTextureUV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, texture, uvs, flags):
-        lib = _lib.load()
-        if not (texture.is_cuda and uvs.is_cuda):
-            raise RuntimeError('dirt_amd.texture.sample_texture_uv runs on an MI355X only; there is no CPU fallback')
         texture = texture.contiguous()
         src, stride = _pairs_in_place(uvs)
         n = uvs.numel() // 2
         ht, wt, ct = (int(d) for d in texture.shape)
         out = torch.empty(tuple(uvs.shape[:-1]) + (ct,), dtype=torch.float32, device=texture.device)
-        with _ops._on_device(texture.device):
-            rc = lib.dirt_texture_sample_forward(texture.data_ptr(), src.data_ptr(), out.data_ptr(), n, ht, wt, ct, stride, flags,
-                                                 _ops._stream_handle(texture.device))
-        _check(rc)
+        _call(_lib.load().dirt_texture_sample_forward, texture.device, texture.data_ptr(), src.data_ptr(), out.data_ptr(), n, ht, wt, ct, stride, flags)
         ctx.save_for_backward(texture, src)
         ctx.meta = (stride, flags, tuple(uvs.shape))
         return out
@@ -97,25 +123,15 @@ class _SampleTextureUV(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        lib = _lib.load()
         texture, src = ctx.saved_tensors
         stride, flags, uv_shape = ctx.meta
         ht, wt, ct = (int(d) for d in texture.shape)
-        n = 1
-        for d in uv_shape[:-1]:
-            n *= int(d)
         grad_out = grad_out.contiguous().to(torch.float32)
         grad_texture = torch.empty_like(texture)
         grad_uvs = torch.empty(uv_shape, dtype=torch.float32, device=texture.device) if ctx.needs_input_grad[1] else None
-        # the look-ups as an image: the last pixel axis is a row, everything before it stacks rows ([H, W, 2]; [B, H, W, 2]);
-        # a flat [n, 2] list is one row
-        cols = int(uv_shape[-2]) if len(uv_shape) >= 3 else n
-        rows = n // cols if cols else 0
-        with _ops._on_device(texture.device):
-            rc = lib.dirt_texture_sample_backward_image(texture.data_ptr(), src.data_ptr(), grad_out.data_ptr(), grad_texture.data_ptr(),
-                                                        grad_uvs.data_ptr() if grad_uvs is not None else None, rows, cols, ht, wt, ct, stride, 2,
-                                                        flags, _ops._stream_handle(texture.device))
-        _check(rc)
+        rows, cols, _ = _pixel_grid(uv_shape)
+        _call(_lib.load().dirt_texture_sample_backward_image, texture.device, texture.data_ptr(), src.data_ptr(), grad_out.data_ptr(),
+              grad_texture.data_ptr(), _stage.ptr(grad_uvs), rows, cols, ht, wt, ct, stride, 2, flags)
         return grad_texture, grad_uvs, None
 
 
@@ -134,12 +150,8 @@ def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear', *, lod=Non
     if lod is not None or lod_bias != 0.0 or mask is not None or max_level is not None:
         raise ValueError("lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
     flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode] | {'bilinear': 0, 'nearest': _lib.TEX_NEAREST}[filter]
-    if texture.dim() != 3:
-        raise ValueError('sample_texture_uv expects texture to be 3D [height, width, channels], got shape %s' % (tuple(texture.shape),))
-    if uvs.dim() < 1 or uvs.shape[-1] != 2:
-        raise ValueError('sample_texture_uv expects uvs of shape [..., 2], got %s' % (tuple(uvs.shape),))
-    if texture.device != uvs.device:
-        raise ValueError('texture and uvs must be on the same device (%s vs %s)' % (texture.device, uvs.device))
+    _check_lookup(texture, uvs)
+    _stage.require_gpu(texture, 'dirt_amd.texture.sample_texture_uv')
     return _SampleTextureUV.apply(texture.to(torch.float32), uvs.to(torch.float32), flags)
 
 
@@ -147,8 +159,7 @@ def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear', *, lod=Non
 
 def _mip_geometry(ht, wt, ct, max_level):
     """-> (level count, packed floats, [(offset, H_k, W_k)] per level) of the pyramid of an ht x wt x ct texture."""
-    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
-        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+    _check_max_level(max_level)
     lib = _lib.load()
     floats = ctypes.c_longlong(0)
     levels = lib.dirt_texture_mip_levels(ht, wt, ct, -1 if max_level is None else max_level, ctypes.byref(floats))
@@ -162,36 +173,23 @@ def _mip_geometry(ht, wt, ct, max_level):
     return levels, floats.value, geo
 
 
-def _check_texture(texture, who):
-    if texture.dim() != 3:
-        raise ValueError('%s expects texture to be 3D [height, width, channels], got shape %s' % (who, tuple(texture.shape)))
-    if not texture.is_cuda:
-        raise RuntimeError('dirt_amd.texture.%s runs on an MI355X only; there is no CPU fallback' % who)
-
-
 class _MipPyramid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, texture, levels, floats):
-        lib = _lib.load()
         texture = texture.contiguous()
         ht, wt, ct = (int(d) for d in texture.shape)
         pyr = torch.empty(floats, dtype=torch.float32, device=texture.device)
-        with _ops._on_device(texture.device):
-            rc = lib.dirt_texture_mip_build(texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(texture.device))
-        _check(rc)
+        _call(_lib.load().dirt_texture_mip_build, texture.device, texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels)
         ctx.meta = (ht, wt, ct, levels)
         return pyr
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_pyr):
-        lib = _lib.load()
         ht, wt, ct, levels = ctx.meta
         grad_pyr = grad_pyr.contiguous().to(torch.float32)
         grad_texture = torch.empty((ht, wt, ct), dtype=torch.float32, device=grad_pyr.device)
-        with _ops._on_device(grad_pyr.device):
-            rc = lib.dirt_texture_mip_collapse(grad_pyr.data_ptr(), grad_texture.data_ptr(), ht, wt, ct, levels, _ops._stream_handle(grad_pyr.device))
-        _check(rc)
+        _call(_lib.load().dirt_texture_mip_collapse, grad_pyr.device, grad_pyr.data_ptr(), grad_texture.data_ptr(), ht, wt, ct, levels)
         return grad_texture, None, None
 
 
@@ -200,6 +198,7 @@ def mip_pyramid(texture, max_level=None):
     means of the one below, while every dimension is even or 1 and up to `max_level`.  The levels are views
     into one packed buffer (level 0 a copy of the texture); differentiable with respect to the texture."""
     _check_texture(texture, 'mip_pyramid')
+    _stage.require_gpu(texture, 'dirt_amd.texture.mip_pyramid')
     ht, wt, ct = (int(d) for d in texture.shape)
     levels, floats, geo = _mip_geometry(ht, wt, ct, max_level)
     packed = _MipPyramid.apply(texture.to(torch.float32), levels, floats)
@@ -226,27 +225,18 @@ def _scalars_in_place(x):
 class _SampleTextureMip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, texture, uvs, lod, mask, flags, lod_bias, max_level):
-        lib = _lib.load()
         texture = texture.contiguous()
         ht, wt, ct = (int(d) for d in texture.shape)
         levels, floats, _ = _mip_geometry(ht, wt, ct, max_level)
         src, stride = _pairs_in_place(uvs)
-        n = uvs.numel() // 2
-        cols = int(uvs.shape[-2]) if uvs.dim() >= 3 else n
-        rows = n // cols if cols else 0
-        image_rows = int(uvs.shape[-3]) if lod is None and rows else 1
+        rows, cols, image_rows = _pixel_grid(uvs.shape, footprint=lod is None)
         lod_t = lod.to(torch.float32).contiguous() if lod is not None else None
         mask_t, mask_stride = _scalars_in_place(mask) if mask is not None else (None, 1)
         pyr = torch.empty(floats, dtype=torch.float32, device=texture.device)
         out = torch.empty(tuple(uvs.shape[:-1]) + (ct,), dtype=torch.float32, device=texture.device)
-        stream = _ops._stream_handle(texture.device)
-        with _ops._on_device(texture.device):
-            rc = lib.dirt_texture_mip_build(texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels, stream)
-            if not rc:
-                rc = lib.dirt_texture_sample_mip_forward(pyr.data_ptr(), src.data_ptr(), lod_t.data_ptr() if lod_t is not None else None,
-                                                         mask_t.data_ptr() if mask_t is not None else None, out.data_ptr(), rows, cols,
-                                                         image_rows, ht, wt, ct, levels, stride, mask_stride, float(lod_bias), flags, stream)
-        _check(rc)
+        _call(_lib.load().dirt_texture_mip_build, texture.device, texture.data_ptr(), pyr.data_ptr(), ht, wt, ct, levels)
+        _call(_lib.load().dirt_texture_sample_mip_forward, texture.device, pyr.data_ptr(), src.data_ptr(), _stage.ptr(lod_t), _stage.ptr(mask_t),
+              out.data_ptr(), rows, cols, image_rows, ht, wt, ct, levels, stride, mask_stride, float(lod_bias), flags)
         ctx.save_for_backward(pyr, src, lod_t, mask_t)
         ctx.meta = (stride, mask_stride, flags, float(lod_bias), tuple(uvs.shape), rows, cols, image_rows, ht, wt, ct, levels, floats)
         return out
@@ -254,7 +244,6 @@ class _SampleTextureMip(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        lib = _lib.load()
         pyr, src, lod_t, mask_t = ctx.saved_tensors
         stride, mask_stride, flags, lod_bias, uv_shape, rows, cols, image_rows, ht, wt, ct, levels, floats = ctx.meta
         dev = pyr.device
@@ -263,26 +252,16 @@ class _SampleTextureMip(torch.autograd.Function):
         grad_texture = torch.empty((ht, wt, ct), dtype=torch.float32, device=dev)
         grad_uvs = torch.empty(uv_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         grad_lod = torch.empty(uv_shape[:-1], dtype=torch.float32, device=dev) if lod_t is not None and ctx.needs_input_grad[2] else None
-        with _ops._on_device(dev):
-            rc = lib.dirt_texture_sample_mip_backward(pyr.data_ptr(), src.data_ptr(), lod_t.data_ptr() if lod_t is not None else None,
-                                                      mask_t.data_ptr() if mask_t is not None else None, grad_out.data_ptr(), scratch.data_ptr(),
-                                                      grad_texture.data_ptr(), grad_uvs.data_ptr() if grad_uvs is not None else None,
-                                                      grad_lod.data_ptr() if grad_lod is not None else None, rows, cols, image_rows,
-                                                      ht, wt, ct, levels, stride, 2, mask_stride, lod_bias, flags, _ops._stream_handle(dev))
-        _check(rc)
+        _call(_lib.load().dirt_texture_sample_mip_backward, dev, pyr.data_ptr(), src.data_ptr(), _stage.ptr(lod_t), _stage.ptr(mask_t),
+              grad_out.data_ptr(), scratch.data_ptr(), grad_texture.data_ptr(), _stage.ptr(grad_uvs), _stage.ptr(grad_lod), rows, cols, image_rows,
+              ht, wt, ct, levels, stride, 2, mask_stride, lod_bias, flags)
         return grad_texture, grad_uvs, grad_lod, None, None, None, None
 
 
 def _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level):
     flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode]
-    if texture.dim() != 3:
-        raise ValueError('sample_texture_uv expects texture to be 3D [height, width, channels], got shape %s' % (tuple(texture.shape),))
-    if uvs.dim() < 1 or uvs.shape[-1] != 2:
-        raise ValueError('sample_texture_uv expects uvs of shape [..., 2], got %s' % (tuple(uvs.shape),))
-    if texture.device != uvs.device:
-        raise ValueError('texture and uvs must be on the same device (%s vs %s)' % (texture.device, uvs.device))
-    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
-        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+    _check_lookup(texture, uvs)
+    _check_max_level(max_level)
     for name, x in (('lod', lod), ('mask', mask)):
         if x is None:
             continue
@@ -295,6 +274,5 @@ def _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level):
                          "[..., H, W, 2], got %s" % (tuple(uvs.shape),))
     if lod is not None and mask is not None:
         raise ValueError('mask marks the neighbours of the footprint level of detail; it does not apply with an explicit lod')
-    if not (texture.is_cuda and uvs.is_cuda):
-        raise RuntimeError('dirt_amd.texture.sample_texture_uv runs on an MI355X only; there is no CPU fallback')
+    _stage.require_gpu(texture, 'dirt_amd.texture.sample_texture_uv')
     return _SampleTextureMip.apply(texture.to(torch.float32), uvs.to(torch.float32), lod, mask, flags, float(lod_bias), max_level)

@@ -1,5 +1,5 @@
 """The full text of what the fused stages refuse (`vertex_stage`, `skin_vertices`, `pose_skeleton`, `blend_shapes`,
-`shade_gbuffer`), and `to(device)` of their built-once index objects.  The stage test files match substrings of these
+`shade_gbuffer`, and the texture look-up `sample_texture_uv` / `mip_pyramid`), and `to(device)` of their built-once index objects.  The stage test files match substrings of these
 messages; this table pins every character, so that the code the wrappers share cannot change a text unnoticed.  Nothing here
 needs the library or a GPU: every refusal comes from types, shapes, dtypes and devices alone.
 """
@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from dirt_amd import blendshapes, geometry, kinematics, shading, skinning
+from dirt_amd import texture as texture_module
 
 TOPOLOGY = geometry.MeshTopology(torch.tensor([[0, 1, 2], [0, 2, 3]]), 4)                                  # V = 4, F = 2
 SKIN = skinning.SkinWeights(torch.tensor([[0, 1], [1, 0], [0, 0]]), torch.full((3, 2), .5), 2)             # V = 3, K = 2, J = 2
@@ -19,6 +20,7 @@ W = torch.full((3, 2), .5)                   # replacement weights of SKIN
 R, P = torch.zeros(3, 3), torch.zeros(3, 3)  # rotations and joints of SKELETON
 TEMPLATE, C = torch.zeros(5, 3), torch.zeros(4)
 G = torch.zeros(4, 4, 10)
+TEX, UV, UV_LIST = torch.zeros(8, 8, 3), torch.zeros(4, 5, 2), torch.zeros(5, 2)   # a texture, an image of look-ups, a flat list
 
 
 def many(t):
@@ -29,6 +31,10 @@ def many(t):
 def shade_checks(gbuffer, lights=(), ambient=(0., 0., 0.)):
     """the checks of `shade_gbuffer` behind its device check, which every CPU tensor fails"""
     return shading._check_arguments(gbuffer, list(lights), 4, 7, 1, 0, ambient, None, (0., 0., 0.), (0., 1.))
+
+
+def trilinear(texture=TEX, uvs=UV, **keywords):
+    return texture_module.sample_texture_uv(texture, uvs, filter='trilinear', **keywords)
 
 
 CPU = ' runs on an MI355X only; there is no CPU fallback'
@@ -120,6 +126,39 @@ REFUSALS = [
     (lambda: shade_checks(torch.zeros(2, 4, 4, 10), ambient=torch.zeros(3, 3)), ValueError, 'ambient must have shape [3] or [2, 3], got [3, 3]'),
     (lambda: shading.shade_gbuffer(G, [], colors=4, normals=7), RuntimeError, 'dirt_amd.shading.shade_gbuffer' + CPU),
     (lambda: shading.shade_gbuffer(G.to('meta'), [], colors=4, normals=7), RuntimeError, 'dirt_amd.shading.shade_gbuffer' + CPU),
+    # sample_texture_uv, mip_pyramid: what both filters check, in the order they check it; then what 'trilinear' alone does --------
+    (lambda: texture_module.sample_texture_uv(torch.zeros(8, 8), UV), ValueError,
+     'sample_texture_uv expects texture to be 3D [height, width, channels], got shape (8, 8)'),
+    (lambda: trilinear(torch.zeros(8, 8)), ValueError, 'sample_texture_uv expects texture to be 3D [height, width, channels], got shape (8, 8)'),
+    (lambda: texture_module.sample_texture_uv(TEX, torch.zeros(4, 5, 3)), ValueError, 'sample_texture_uv expects uvs of shape [..., 2], got (4, 5, 3)'),
+    (lambda: texture_module.sample_texture_uv(TEX, torch.zeros(()), filter='nearest'), ValueError, 'sample_texture_uv expects uvs of shape [..., 2], got ()'),
+    (lambda: trilinear(uvs=torch.zeros(4, 5, 3)), ValueError, 'sample_texture_uv expects uvs of shape [..., 2], got (4, 5, 3)'),
+    (lambda: texture_module.sample_texture_uv(TEX.to('meta'), UV), ValueError, 'texture and uvs must be on the same device (meta vs cpu)'),
+    (lambda: trilinear(uvs=UV.to('meta')), ValueError, 'texture and uvs must be on the same device (cpu vs meta)'),
+] + [
+    (lambda filt=filt, kw=kw: texture_module.sample_texture_uv(TEX, UV_LIST, filter=filt, **kw), ValueError,
+     "lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % filt)
+    for filt in ('bilinear', 'nearest') for kw in ({'lod': torch.zeros(5)}, {'lod_bias': 1.0}, {'mask': torch.ones(5)}, {'max_level': 2})
+] + [
+    (lambda: trilinear(max_level=-1), ValueError, 'max_level must be a non-negative int or None, got -1'),
+    (lambda: trilinear(max_level=True), ValueError, 'max_level must be a non-negative int or None, got True'),
+    (lambda: trilinear(max_level=1.5), ValueError, 'max_level must be a non-negative int or None, got 1.5'),
+    (lambda: trilinear(lod=torch.zeros(4, 4)), ValueError, 'lod must be a tensor shaped like uvs[..., 0] (4, 5), got (4, 4)'),
+    (lambda: trilinear(mask=torch.ones(5, 4)), ValueError, 'mask must be a tensor shaped like uvs[..., 0] (4, 5), got (5, 4)'),
+    (lambda: trilinear(lod=[[0.] * 5] * 4), ValueError, 'lod must be a tensor shaped like uvs[..., 0] (4, 5), got ()'),
+    (lambda: trilinear(mask=torch.ones(4, 5).numpy()), ValueError, 'mask must be a tensor shaped like uvs[..., 0] (4, 5), got (4, 5)'),
+    (lambda: trilinear(lod=torch.zeros(4, 5, device='meta')), ValueError, 'lod and uvs must be on the same device (meta vs cpu)'),
+    (lambda: trilinear(mask=torch.ones(4, 5, device='meta')), ValueError, 'mask and uvs must be on the same device (meta vs cpu)'),
+    (lambda: trilinear(uvs=UV_LIST), ValueError,
+     "filter='trilinear' without lod takes the level of detail from neighbouring pixels: uvs must be images [..., H, W, 2], got (5, 2)"),
+    (lambda: trilinear(lod=torch.zeros(4, 5), mask=torch.ones(4, 5)), ValueError,
+     'mask marks the neighbours of the footprint level of detail; it does not apply with an explicit lod'),
+    (lambda: texture_module.sample_texture_uv(TEX, UV), RuntimeError, 'dirt_amd.texture.sample_texture_uv' + CPU),
+    (lambda: texture_module.sample_texture_uv(TEX, UV_LIST, 'clamp', 'nearest'), RuntimeError, 'dirt_amd.texture.sample_texture_uv' + CPU),
+    (lambda: trilinear(), RuntimeError, 'dirt_amd.texture.sample_texture_uv' + CPU),
+    (lambda: trilinear(uvs=UV_LIST, lod=torch.zeros(5), max_level=0), RuntimeError, 'dirt_amd.texture.sample_texture_uv' + CPU),
+    (lambda: texture_module.mip_pyramid(TEX), RuntimeError, 'dirt_amd.texture.mip_pyramid' + CPU),
+    (lambda: texture_module.mip_pyramid(torch.zeros(8, 8)), ValueError, 'mip_pyramid expects texture to be 3D [height, width, channels], got shape (8, 8)'),
 ]
 
 
