@@ -26,6 +26,12 @@
 //     its masked partial sums (3 vertices x {x, y, w, colours}), the <= 21 sums are reduced across the wave with a
 //     transposing butterfly (~80 instructions: 21 totals land in 21 different lanes), and ONE global_atomic_add_f32
 //     instruction adds them to the face's three vertices.  No LDS accumulators, no hash table, no fixed point.
+// Memory trips of a wave: ONE burst of loads at its head -- state plane A, the planes' pixels, grad_pixels, the own barycentrics,
+// in the order of their use, every wait before the barrier a counted vmcnt(N) -- then, after the dilation, the barycentrics of
+// the ring cells that received something, the face loop's vertex indices and atomics, and the second read of grad_pixels for
+// grad_background's whole-line stores.  That is the plain 4-channel kernel; every other shape keeps the earlier two-trip order (BURST below).
+// The counted waits are the compiler's own, given the order of the source and stores it cannot sink a load into: nothing pins
+// them -- after a compiler update, read grad_kernel<4>'s ISA again: no vmcnt(0) between the first load and the barrier.
 // Variable names in the per-pixel arithmetic follow the CUDA source.
 #include "dirt_device.h"
 #include "dirt_launch.h"
@@ -86,6 +92,11 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
     constexpr int RING_E1 = 6 * 64, RING_E1_LANES = RING - 64;
     static_assert(RING_E1 + 6 * RING_E1_LANES <= 2 * ICELLS, "the ring factors fit in the inbox");
     static_assert(!ALIAS_INBOX || sizeof(float2) * (GTHREADS / 64) * ICELLS <= sizeof(float) * NPLANES * PR * PS, "the inboxes fit in the planes");
+
+    // BURST: every load of the wave in one burst (run_pass): the plain 4-channel kernel, where it was measured (K3; pairs, rows).
+    // The {3,3} shape, which sits at exactly 128 registers, and the aliased form, which is allocated for five waves per SIMD (96),
+    // spill with it; the 1- and 3-channel and the strided shapes compile with it but have not been timed: all keep the earlier order.
+    constexpr bool BURST = CSPEC == 4 && !STRIDED && !AI;
 
     GRAD_TRACE_BEGIN();
     GMARK();  // 0 start
@@ -228,31 +239,48 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
     //      neighbours are inside the frame. ----
     float stage_v[PITEMS][PC];
     const int nch_live = CSPEC == 6 ? (second_mode == 0 ? 6 : (second_mode == 1 ? 4 : 3)) : (single_on ? CSPEC : 3);   // channels the pass reads
-    stage_load(nch_live, stage_v);
-    {
-        // (the same sweep: column x0 - 1 + tid % 34, rows tid / 34, + 7, ...; threads 238 .. 255 idle)
-        constexpr int VITEMS = (PR + PROWS - 1) / PROWS;
-        const int v_row = tid / PR, v_ci = tid - v_row * PR;
-        const bool v_on = tid < PROWS * PR;
+    // (the same sweep as the planes': column x0 - 1 + tid % 34, rows tid / 34, + 7, ...; threads 238 .. 255 idle)
+    constexpr int VITEMS = (PR + PROWS - 1) / PROWS;
+    // BURST: the stores are UNCONDITIONAL -- an idle thread, and a thread's item past the last row, repeat another item (same
+    // address, same value): behind a branch the compiler sinks the loads into it, next to the stores, where they are requested
+    // after everything else and waited for with vmcnt(0).
+    auto state_load = [&](float2 (&rec)[VITEMS]) {
+        const int tv = BURST ? min(tid, PROWS * PR - 1) : tid;
+        const int v_row = tv / PR, v_ci = tv - v_row * PR;
         const uint32_t v_xoff = (uint32_t)min(max(x0 - 1 + v_ci, 0), W - 1) * 8u;
-        float2 rec[VITEMS];
 #pragma unroll
         for (int k = 0; k < VITEMS; ++k) {
-            const int cy = min(max(y0 - 1 + v_row + PROWS * k, 0), H - 1);
+            const int row = BURST ? min(v_row + PROWS * k, PR - 1) : v_row + PROWS * k;
+            const int cy = min(max(y0 - 1 + row, 0), H - 1);
             rec[k] = ld_off<float2>(state_a, (uint32_t)(cy - row0) * ((uint32_t)W * 8u) + v_xoff);
         }
+    };
+    auto state_store = [&](const float2 (&rec)[VITEMS]) {
+        const int tv = BURST ? min(tid, PROWS * PR - 1) : tid;
+        const int v_row = tv / PR, v_ci = tv - v_row * PR;
+        const bool v_on = tid < PROWS * PR;
 #pragma unroll
         for (int k = 0; k < VITEMS; ++k) {
-            const int row = v_row + PROWS * k;
-            if (!v_on || row >= PR) continue;
+            const int row = BURST ? min(v_row + PROWS * k, PR - 1) : v_row + PROWS * k;
+            if (!BURST && (!v_on || row >= PR)) continue;
             s_vw[row][v_ci + 1] = rec[k];
         }
-    }
+    };
     // own barycentrics (two stored, the largest re-derived: decode_bary)
     float bk[4][3];
+    auto bary_load = [&](float2 (&braw)[4]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) decode_bary(ld_off<float2>(state_b, in_px[j] ? (own_rel + (uint32_t)j) * 8u : 0u), bk[j]);
-    if (!ALIAS_INBOX) zero_inbox();
+        for (int j = 0; j < 4; ++j) braw[j] = ld_off<float2>(state_b, in_px[j] ? (own_rel + (uint32_t)j) * 8u : 0u);
+    };
+    if constexpr (!BURST) {   // the earlier order: planes, state A and the state tile's stores, then the rest (run_pass: grad_pixels)
+        stage_load(nch_live, stage_v);
+        float2 rec[VITEMS];
+        state_load(rec);
+        state_store(rec);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) decode_bary(ld_off<float2>(state_b, in_px[j] ? (own_rel + (uint32_t)j) * 8u : 0u), bk[j]);
+        if (!ALIAS_INBOX) zero_inbox();
+    }
 
     // (fx, fy) sent to this strip's own pixels by themselves (see "position factors" below)
     using std::integral_constant;
@@ -500,6 +528,7 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
         // this strip's grad_pixels
         const uint32_t own_off = own_rel * pixel_bytes;
         float g[4][NCH];
+        auto gpix_load = [&]() {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t off = in_px[j] ? own_off + (uint32_t)j * pixel_bytes : 0u;  // outside the frame: any valid address
@@ -544,6 +573,23 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) g[j][ch] = ld_off<float>(gpix_t, off + 4u * ch);
             }
+        }
+        };
+        // ---- every load of the wave in ONE burst, in the order in which the data is needed: state plane A (the state tile's
+        //      stores wait for it alone, with a counted vmcnt, while everything behind it stays in flight), the planes' pixels,
+        //      grad_pixels and the own barycentrics.  In the earlier order -- planes, state A, state tile stores,
+        //      then the rest -- the compiler answered the stores with s_waitcnt vmcnt(0), and the rest became a second round trip
+        //      started when the first was over.  (BURST off: that order.) ----
+        float2 rec[VITEMS], braw[4];
+        if constexpr (BURST) {
+            state_load(rec);
+            stage_load(nch_live, stage_v);
+            gpix_load();
+            bary_load(braw);
+            state_store(rec);
+            if (!ALIAS_INBOX) zero_inbox();
+        } else {
+            gpix_load();
         }
         GMARK();  // 1 loads issued, state tile stored
         stage_store(nch_live, stage_v);
@@ -655,6 +701,10 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
             }
         }
         GMARK();  // 4 Scharr done
+        if constexpr (BURST) {   // (decoded here: two registers per pixel, not three, are live across the Scharr filter)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) decode_bary(braw[j], bk[j]);
+        }
         if (ALIAS_INBOX) {   // every wave is done with the planes: they become the inboxes
             __syncthreads();
             zero_inbox();
