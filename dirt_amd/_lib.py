@@ -56,6 +56,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_profile_read', 'dirt_profile_reset', 'dirt_texture_sample_forward', 'dirt_texture_sample_backward',
            'dirt_texture_sample_backward_image', 'dirt_texture_last_error', 'dirt_texture_mip_levels', 'dirt_texture_mip_build',
            'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
+           'dirt_texture_sample_batch_forward', 'dirt_texture_sample_batch_backward_image', 'dirt_texture_mip_build_batch',
+           'dirt_texture_mip_collapse_batch', 'dirt_texture_sample_mip_batch_forward', 'dirt_texture_sample_mip_batch_backward',
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward',
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
@@ -125,6 +127,20 @@ def load():
         lib.dirt_texture_sample_mip_forward.restype = i
         lib.dirt_texture_sample_mip_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, i, i, i, f32, u, vp]
         lib.dirt_texture_sample_mip_backward.restype = i
+    if hasattr(lib, 'dirt_texture_sample_batch_forward') or not override:   # a texture per scene (ABI 4, additive): `scenes` after the pointers
+        f32 = ctypes.c_float
+        lib.dirt_texture_sample_batch_forward.argtypes = [fp, fp, fp, ll, ll, i, i, i, i, u, vp]
+        lib.dirt_texture_sample_batch_forward.restype = i
+        lib.dirt_texture_sample_batch_backward_image.argtypes = [fp, fp, fp, fp, fp, ll, ll, ll, i, i, i, i, i, u, vp]
+        lib.dirt_texture_sample_batch_backward_image.restype = i
+        lib.dirt_texture_mip_build_batch.argtypes = [fp, fp, ll, i, i, i, i, vp]
+        lib.dirt_texture_mip_build_batch.restype = i
+        lib.dirt_texture_mip_collapse_batch.argtypes = [fp, fp, ll, i, i, i, i, vp]
+        lib.dirt_texture_mip_collapse_batch.restype = i
+        lib.dirt_texture_sample_mip_batch_forward.argtypes = [fp, fp, fp, fp, fp, ll, ll, ll, i, i, i, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_sample_mip_batch_forward.restype = i
+        lib.dirt_texture_sample_mip_batch_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, ll, ll, ll, i, i, i, i, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_sample_mip_batch_backward.restype = i
     if hasattr(lib, 'dirt_shade_forward') or not override:   # fused G-buffer lighting (ABI 4, additive)
         f32 = ctypes.c_float
         lib.dirt_shade_scratch_bytes.argtypes = [ll, ll, i]

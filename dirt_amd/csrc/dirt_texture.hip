@@ -8,6 +8,8 @@
 // dL/duv.  The arithmetic is the reference's, operation for operation in float32 (so the result equals the composed
 // torch / TF expression bit for bit); where the reference's gather would read row Ht or column Wt -- an index inside the
 // last texel -- the last texel is used.
+// A texture per scene (dirt_texture_sample_batch_*): the same two kernels, instantiated with BATCH, take the scene from
+// gridDim.y and move their base pointers to that scene's data before the per-look-up code (dirt_texture_common.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dirt_texture_common.h"
@@ -26,10 +28,19 @@ struct TexParams {
     float* grad_uvs;        // n pairs, `guv_stride` floats apart; or nullptr
 };
 
+// BATCH: `p` describes scene 0 of a batch and blockIdx.y is the scene (dirt_texture_common.h): its texture, look-ups, outputs and gradients
+__device__ __forceinline__ void tex_scene(TexParams& p)
+{
+    const size_t b = blockIdx.y, texels = (size_t)p.Ht * p.Wt * p.Ct, n = (size_t)p.n;
+    scene_shift(p.texture, b * texels); scene_shift(p.uvs, b * n * p.uv_stride); scene_shift(p.out, b * n * p.Ct);
+    scene_shift(p.grad_out, b * n * p.Ct); scene_shift(p.grad_texture, b * texels); scene_shift(p.grad_uvs, b * n * p.guv_stride);
+}
+
 // ---- forward: one thread per pixel, CT channels per access ----
-template <int CT>
+template <int CT, bool BATCH = false>
 __global__ __launch_bounds__(256) void texture_forward_kernel(TexParams p)
 {
+    if constexpr (BATCH) tex_scene(p);
     const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0, nearest = (p.flags & DIRT_TEX_NEAREST) != 0;
     const int Ct = CT ? CT : p.Ct;
     constexpr int NV = CT ? CT : 1;
@@ -61,9 +72,10 @@ __global__ __launch_bounds__(256) void texture_forward_kernel(TexParams p)
 }
 
 // ---- backward: the tile scheme of dirt_texture_common.h with one patch, the bounding box of the tile's taps
-template <int CT>
+template <int CT, bool BATCH = false>
 __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int rows, int cols, int tw, int th, int tiles_x)
 {
+    if constexpr (BATCH) tex_scene(p);
     constexpr int LCT = CT ? CT : 4;                 // channels per LDS patch pass (any count: passes of 4)
     __shared__ float s_acc[TEX_PATCH * LCT];
     __shared__ int s_box[4];                         // rmin, rmax, cmin, cmax of the tile's taps
@@ -137,24 +149,28 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
     }
 }
 
-hipError_t launch_texture_forward(const TexParams& p, hipStream_t stream)
+// (both launchers: scenes < 0 is a single-texture call; scenes >= 0 a batch of that many, the BATCH kernels with the scene in gridDim.y.
+// Four channels: every per-scene extent is a multiple of 16 bytes, so scene 0's alignment is every scene's.)
+hipError_t launch_texture_forward(const TexParams& p, hipStream_t stream, long long scenes = -1)
 {
-    if (p.n == 0) return hipSuccess;
+    if (p.n == 0 || scenes == 0) return hipSuccess;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.texture) & 15u) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15u) == 0;
     dispatch_channels(p.Ct, a16, [&](auto ct) {
-        hipLaunchKernelGGL(texture_forward_kernel<decltype(ct)::value>, dim3(capped_blocks(p.n)), dim3(256), 0, stream, p);
+        if (scenes < 0) hipLaunchKernelGGL(texture_forward_kernel<decltype(ct)::value>, dim3(capped_blocks(p.n)), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((texture_forward_kernel<decltype(ct)::value, true>), dim3(capped_blocks(p.n), (unsigned)scenes), dim3(256), 0, stream, p);
     });
     return hipGetLastError();
 }
 
-hipError_t launch_texture_backward(const TexParams& p, long long rows, long long cols, hipStream_t stream)
+hipError_t launch_texture_backward(const TexParams& p, long long rows, long long cols, hipStream_t stream, long long scenes = -1)
 {
-    if (p.n == 0) return hipSuccess;
+    if (p.n == 0 || scenes == 0) return hipSuccess;
     const TileGrid t = tile_grid(rows, cols);
     if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) return hipErrorInvalidValue;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.grad_out) & 15u) == 0;
     dispatch_channels(p.Ct, a16, [&](auto ct) {
-        hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
+        if (scenes < 0) hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
+        else hipLaunchKernelGGL((texture_backward_kernel<decltype(ct)::value, true>), dim3((unsigned)t.tiles, (unsigned)scenes), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
     });
     return hipGetLastError();
 }
@@ -229,6 +245,49 @@ int dirt_texture_sample_backward(const float* texture, const float* uvs, const f
 {
     // a flat list of n look-ups: one row of n pixels
     return dirt_texture_sample_backward_image(texture, uvs, grad_out, grad_texture, grad_uvs, 1, n, Ht, Wt, Ct, uv_stride, grad_uv_stride, flags, stream);
+}
+
+// ---- a texture per scene (dirt_texture_common.h: batched launches): the checks of the entry points above, then those of the scene count
+
+int dirt_texture_sample_batch_forward(const float* textures, const float* uvs, float* out, long long scenes, long long n, int Ht, int Wt, int Ct,
+                                      int uv_stride, unsigned flags, void* stream)
+{
+    const char* who = "dirt_texture_sample_batch_forward";
+    int rc = tex_check(who, textures, uvs, n, Ht, Wt, Ct, uv_stride);
+    if (rc) return rc;
+    if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
+    rc = dirt::check_scenes(who, scenes, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}});
+    if (rc) return rc;
+    dirt::TexParams p{};
+    p.texture = textures; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.flags = flags; p.out = out;
+    return dirt::stage_hip(report, who, dirt::launch_texture_forward(p, reinterpret_cast<hipStream_t>(stream), scenes));
+}
+
+int dirt_texture_sample_batch_backward_image(const float* textures, const float* uvs, const float* grad_out, float* grad_textures, float* grad_uvs,
+                                             long long scenes, long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride,
+                                             int grad_uv_stride, unsigned flags, void* stream)
+{
+    const char* who = "dirt_texture_sample_batch_backward_image";
+    int rc = dirt::check_pixel_grid(who, rows, cols);
+    if (!rc) rc = tex_check(who, textures, uvs, rows * cols, Ht, Wt, Ct, uv_stride);
+    if (rc) return rc;
+    const long long n = rows * cols;
+    if (n > 0 && (!grad_out || !grad_textures)) TEX_FAIL("%s: grad_out / grad_textures is NULL", who);
+    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
+    rc = dirt::check_scenes(who, scenes, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}, {n, grad_uvs ? grad_uv_stride : 0}});
+    if (rc) return rc;
+    if (!grad_textures || scenes == 0) return dirt::stage_ok(report);   // (nothing to clear, nothing to launch)
+    const dirt::TileGrid t = dirt::tile_grid(rows, cols);
+    if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large (rows=%lld cols=%lld)", who, rows, cols);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = dirt::clear_floats(grad_textures, scenes * ((long long)Ht * Wt * Ct), s);
+    if (e == hipSuccess) {
+        dirt::TexParams p{};
+        p.texture = textures; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.guv_stride = grad_uv_stride;
+        p.flags = flags; p.grad_out = grad_out; p.grad_texture = grad_textures; p.grad_uvs = grad_uvs;
+        e = dirt::launch_texture_backward(p, rows, cols, s, scenes);
+    }
+    return dirt::stage_hip(report, who, e);
 }
 
 }  // extern "C"

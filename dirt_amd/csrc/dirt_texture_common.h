@@ -1,9 +1,11 @@
 // dirt_texture_common.h -- what the texture kernels share (dirt_texture.hip: nearest / bilinear; dirt_texture_mip.hip: trilinear over a
 // mip pyramid).  Per look-up: (u, v) -> fractional (row, column) index of the reference's samples/textured.py:16-26, the four bilinear taps of
-// :36-60, the channel-vector loads / stores, the blend.  The pieces of the backward tile scheme.  Host: the pixel grid, the clear of a buffer.
+// :36-60, the channel-vector loads / stores, the blend.  The pieces of the backward tile scheme.  The rule of a batched launch (a texture per scene).
+// Host: the pixel grid, the scene count of a batch, the clear of a buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "dirt_stage.h"
 
 namespace dirt {
@@ -145,6 +147,27 @@ inline TileGrid tile_grid(long long rows, long long cols)
 {
     const int tw = rows > 1 ? 16 : 256, th = rows > 1 ? 16 : 1;
     return {tw, th, (cols + tw - 1) / tw, ((cols + tw - 1) / tw) * ((rows + th - 1) / th)};
+}
+
+// ---- batched launches (a texture per scene).  Scene b's texture, pyramid, coordinates, outputs and gradients start b per-scene extents
+// after scene 0's, the scene is gridDim.y, and blockIdx.x / gridDim.x mean what they mean in a single-texture launch: a tile or a
+// grid-stride loop never sees look-ups of two scenes.  A kernel's BATCH instantiation moves its base pointers to its scene's data once
+// (workgroup-uniform, in size_t), before the per-look-up code, which is the single-texture kernel's; a pointer that is missing stays so.
+constexpr long long TEX_MAX_SCENES = 65535;   // gridDim.y
+template <class T> __device__ __forceinline__ void scene_shift(T*& p, size_t floats) { if (p) p += floats; }
+
+// host: the scene count of a batched entry point and its per-scene extents in floats, each a count x a stride (both >= 0)
+struct SceneExtent { long long count, stride; };
+inline int check_scenes(const char* who, long long scenes, std::initializer_list<SceneExtent> extents)
+{
+    if (scenes < 0) TEX_FAIL("%s: bad scene count (scenes=%lld)", who, scenes);
+    for (const SceneExtent& e : extents) {
+        long long t;
+        if (__builtin_mul_overflow(e.count, e.stride, &t) || __builtin_mul_overflow(t, scenes, &t))
+            TEX_FAIL("%s: %lld scenes of %lld x %lld floats overflow", who, scenes, e.count, e.stride);
+    }
+    if (scenes > TEX_MAX_SCENES) TEX_FAIL("%s: %lld scenes, one launch addresses at most %lld", who, scenes, TEX_MAX_SCENES);
+    return DIRT_OK;
 }
 
 // ---- p[0 .. n) = 0 on `stream`: how the backward entry points clear the buffer their kernels add into.  A kernel of the

@@ -30,7 +30,9 @@
 // Kernels: the pyramid in one launch of 32 x 32-texel blocks reduced through levels 1-5 in LDS, plus one single-workgroup
 // launch for the levels above; the forward one look-up per lane (its (u, v) neighbours read through L1 / L2); the backward
 // on 16 x 16-pixel tiles that sum into an LDS patch per touched level (at most two adjacent levels) and fall back to float
-// atomics into the scratch pyramid where the footprint does not fit; then the collapse.
+// atomics into the scratch pyramid where the footprint does not fit; then the collapse.  A texture per scene
+// (dirt_texture_*_batch*): every kernel's BATCH instantiation, the scene in gridDim.y, pyramids and scratch [scenes, floats]
+// (dirt_texture_common.h: batched launches); the top build launch becomes one workgroup per scene.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dirt_texture_common.h"
@@ -40,7 +42,7 @@ namespace dirt {
 constexpr int MIP_MAX = 32;        // levels of a pyramid (a dimension of 2^31 halves 31 times)
 constexpr int MIP_TILE_LEVELS = 5; // levels reduced in LDS by the block kernel (a 32 x 32 block -> 1 x 1)
 
-struct MipParams {
+struct MipArgs {
     const float* pyr;        // packed pyramid (level 0 = the texture)
     const float* uvs;        // rows x cols pairs (u, v), `uv_stride` floats apart
     const float* lod;        // rows x cols levels of detail, or nullptr (footprint)
@@ -54,10 +56,37 @@ struct MipParams {
     float* grad_pyr;         // packed pyramid-shaped scratch (cleared by the caller of the kernel)
     float* grad_uvs;         // pairs `guv_stride` apart, or nullptr
     float* grad_lod;         // n, or nullptr
+};
+struct MipParams : MipArgs {
     long long off[MIP_MAX];  // float offset of each level in the packed buffers
 };
 
 __host__ __device__ __forceinline__ int mip_dim(int n0, int k) { const int d = n0 >> k; return d > 1 ? d : 1; }
+
+// the floats of the packed pyramid
+template <class P> __host__ __device__ __forceinline__ long long mip_floats(const P& p)
+{
+    return p.off[p.L - 1] + (long long)mip_dim(p.Ht, p.L - 1) * mip_dim(p.Wt, p.L - 1) * p.Ct;
+}
+
+// BATCH: the kernel's argument describes scene 0 of a batch and blockIdx.y is the scene (dirt_texture_common.h).  What that scene's look-ups
+// see: MipParams member for member, the pointers at the scene's pyramid, look-ups, outputs and gradients, the level offsets still the
+// argument's own table (a modified copy of the whole argument left the table, indexed by level, in scratch memory in the backward kernel).
+// The per-look-up functions below take either as `P`.
+struct MipScene : MipArgs {
+    const long long (&off)[MIP_MAX];
+    __device__ __forceinline__ MipScene(const MipParams& q) : MipArgs(q), off(q.off)
+    {
+        const size_t b = blockIdx.y, floats = (size_t)mip_floats(q), n = (size_t)(rows * cols);
+        scene_shift(pyr, b * floats); scene_shift(uvs, b * n * uv_stride); scene_shift(lod, b * n); scene_shift(mask, b * n * mask_stride);
+        scene_shift(out, b * n * Ct); scene_shift(grad_out, b * n * Ct); scene_shift(grad_pyr, b * floats);
+        scene_shift(grad_uvs, b * n * guv_stride); scene_shift(grad_lod, b * n);
+    }
+};
+template <bool BATCH> __device__ __forceinline__ std::conditional_t<BATCH, MipScene, const MipParams&> mip_scene(const MipParams& q)
+{
+    if constexpr (BATCH) return MipScene(q); else return q;
+}
 
 // the index of a level-0 fractional index at level k, per axis (spec 2), and its derivative with respect to the level-0 index
 __device__ __forceinline__ float mip_index(float idx0, int n0, int nk, float& d)
@@ -68,15 +97,15 @@ __device__ __forceinline__ float mip_index(float idx0, int n0, int nk, float& d)
     return x < 0.f ? 0.f : x;
 }
 
-__device__ __forceinline__ bool mip_valid(const MipParams& p, long long j) { return !p.mask || p.mask[j * p.mask_stride] != 0.f; }
+template <class P> __device__ __forceinline__ bool mip_valid(const P& p, long long j) { return !p.mask || p.mask[j * p.mask_stride] != 0.f; }
 
-__device__ __forceinline__ void mip_uv(const MipParams& p, long long j, float& u, float& v)
+template <class P> __device__ __forceinline__ void mip_uv(const P& p, long long j, float& u, float& v)
 {
     u = p.uvs[j * p.uv_stride]; v = p.uvs[j * p.uv_stride + 1];
 }
 
 // lambda of look-up i, before the clamp (spec 3)
-__device__ __forceinline__ float mip_lambda(const MipParams& p, long long i, float u, float v, bool clamp_mode)
+template <class P> __device__ __forceinline__ float mip_lambda(const P& p, long long i, float u, float v, bool clamp_mode)
 {
     if (p.lod) return p.lod[i] + p.lod_bias;
     if (!mip_valid(p, i)) return 0.f;
@@ -121,9 +150,11 @@ __device__ __forceinline__ float mip_reduce(const float* __restrict__ src, int s
     return (t00 + t1) * 0.5f;
 }
 
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void mip_build_blocks_kernel(const float* __restrict__ tex, float* __restrict__ pyr, MipParams p, int kt,
                                                                int tiles_x)
 {
+    if constexpr (BATCH) { tex += (size_t)blockIdx.y * p.Ht * p.Wt * p.Ct; pyr += (size_t)blockIdx.y * mip_floats(p); }
     __shared__ float s_a[32 * 32 * 4];
     __shared__ float s_b[16 * 16 * 4];
     const int tid = threadIdx.x, Ct = p.Ct;
@@ -160,9 +191,11 @@ __global__ __launch_bounds__(256) void mip_build_blocks_kernel(const float* __re
 }
 
 // the levels above kt: one workgroup, level after level from the packed buffer (a level kt of up to 64 x 64 texels for a
-// 2048 x 2048 texture)
+// 2048 x 2048 texture); BATCH: one workgroup per scene
+template <bool BATCH = false>
 __global__ __launch_bounds__(1024) void mip_build_top_kernel(float* __restrict__ pyr, MipParams p, int kt)
 {
+    if constexpr (BATCH) pyr += (size_t)blockIdx.y * mip_floats(p);
     const int Ct = p.Ct;
     for (int k = kt + 1; k < p.L; ++k) {
         const bool hr = mip_dim(p.Ht, k - 1) > 1, hc = mip_dim(p.Wt, k - 1) > 1;
@@ -190,8 +223,10 @@ __global__ __launch_bounds__(1024) void mip_build_top_kernel(float* __restrict__
 }
 
 // ---- collapse: dL/dtexture[r, c] = sum over levels k of dL/dlevel_k[ancestor] * (the product of the factors below k), top down
+template <bool BATCH = false>
 __global__ __launch_bounds__(256) void mip_collapse_kernel(const float* __restrict__ gp, float* __restrict__ gt, MipParams p)
 {
+    if constexpr (BATCH) { gp += (size_t)blockIdx.y * mip_floats(p); gt += (size_t)blockIdx.y * p.Ht * p.Wt * p.Ct; }
     const int Ct = p.Ct;
     const long long n = (long long)p.Ht * p.Wt * Ct;
     const int lgh = 31 - __clz(p.Ht), lgw = 31 - __clz(p.Wt);
@@ -224,7 +259,7 @@ __device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk
 }
 
 // the taps of level l for a level-0 index (and the derivatives of the level's index)
-__device__ __forceinline__ Taps mip_taps(const MipParams& p, int l, float row, float col, float& drow, float& dcol)
+template <class P> __device__ __forceinline__ Taps mip_taps(const P& p, int l, float row, float col, float& drow, float& dcol)
 {
     if (l == 0) { drow = 1.f; dcol = 1.f; return bilinear_taps(row, col, p.Ht, p.Wt); }
     const int Hk = mip_dim(p.Ht, l), Wk = mip_dim(p.Wt, l);
@@ -233,9 +268,10 @@ __device__ __forceinline__ Taps mip_taps(const MipParams& p, int l, float row, f
 }
 
 // ---- forward: one look-up per lane
-template <int CT>
-__global__ __launch_bounds__(256) void mip_forward_kernel(MipParams p)
+template <int CT, bool BATCH = false>
+__global__ __launch_bounds__(256) void mip_forward_kernel(MipParams args)
 {
+    const auto& p = mip_scene<BATCH>(args);
     const bool clamp_mode = (p.flags & DIRT_TEX_CLAMP) != 0;
     const int Ct = CT ? CT : p.Ct;
     constexpr int NV = CT ? CT : 1;
@@ -273,9 +309,10 @@ __global__ __launch_bounds__(256) void mip_forward_kernel(MipParams p)
 // ---- backward: the tile scheme of dirt_texture_common.h with one LDS patch per touched level.  A lane's look-up has up to two tap
 // sets: level l with weight 1 - f and level l + 1 with weight f (when f != 0).  Where the tile's sets span at most two adjacent levels
 // and both bounding boxes fit TEX_PATCH texels together, each set sums into its level's patch; otherwise they scatter into memory.
-template <int CT>
-__global__ __launch_bounds__(256) void mip_backward_kernel(MipParams p, int tw, int th, int tiles_x)
+template <int CT, bool BATCH = false>
+__global__ __launch_bounds__(256) void mip_backward_kernel(MipParams args, int tw, int th, int tiles_x)
 {
+    const auto& p = mip_scene<BATCH>(args);
     constexpr int LCT = CT ? CT : 4;
     __shared__ float s_acc[TEX_PATCH * LCT];
     __shared__ int s_box[10];   // lmin, lmax, then rmin, rmax, cmin, cmax of the two levels' taps
@@ -411,8 +448,6 @@ void mip_offsets(MipParams& p)
     }
 }
 
-long long mip_floats(const MipParams& p) { return p.off[p.L - 1] + (long long)mip_dim(p.Ht, p.L - 1) * mip_dim(p.Wt, p.L - 1) * p.Ct; }
-
 }  // namespace dirt
 
 extern "C" {
@@ -440,34 +475,69 @@ static int mip_check(const char* who, int Ht, int Wt, int Ct, int levels, dirt::
     return DIRT_OK;
 }
 
-int dirt_texture_mip_build(const float* texture, float* pyramid, int Ht, int Wt, int Ct, int levels, void* stream)
+// (every entry point below and its batched form are one function: without `batch` it is the single-texture call and launches the kernels'
+// single-texture instantiations; with it, `scenes` textures, checked by check_scenes, go to the BATCH kernels with the scene in gridDim.y)
+
+static int mip_build(const char* who, const float* texture, float* pyramid, bool batch, long long scenes, int Ht, int Wt, int Ct, int levels, void* stream)
 {
-    const char* who = "dirt_texture_mip_build";
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
     if (!texture || !pyramid) TEX_FAIL("%s: texture / pyramid is NULL", who);
+    if (batch && (rc = dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}}))) return rc;
+    if (batch && scenes == 0) return dirt::stage_ok(report);
+    const unsigned gy = batch ? (unsigned)scenes : 1u;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (levels == 1)
-        return dirt::stage_hip(report, who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct, hipMemcpyDeviceToDevice, s));
+    if (levels == 1)   // (a batch of one-level pyramids is the batch of textures)
+        return dirt::stage_hip(report, who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct * gy, hipMemcpyDeviceToDevice, s));
     const int kt = min(levels - 1, dirt::MIP_TILE_LEVELS);
     const int tiles_y = dirt::mip_dim(Ht, kt), tiles_x = dirt::mip_dim(Wt, kt);
     if ((long long)tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: texture too large", who);
-    hipLaunchKernelGGL(dirt::mip_build_blocks_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
-    if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel, dim3(1), dim3(1024), 0, s, pyramid, p, kt);
+    if (!batch) {
+        hipLaunchKernelGGL(dirt::mip_build_blocks_kernel<>, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
+        if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel<>, dim3(1), dim3(1024), 0, s, pyramid, p, kt);
+    } else {
+        hipLaunchKernelGGL(dirt::mip_build_blocks_kernel<true>, dim3((unsigned)(tiles_x * tiles_y), gy), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
+        if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel<true>, dim3(1, gy), dim3(1024), 0, s, pyramid, p, kt);
+    }
     return dirt::stage_hip(report, who, hipGetLastError());
 }
 
-int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
+static int mip_collapse(const char* who, const float* grad_pyramid, float* grad_texture, bool batch, long long scenes, int Ht, int Wt, int Ct, int levels,
+                        void* stream)
 {
-    const char* who = "dirt_texture_mip_collapse";
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
     if (!grad_pyramid || !grad_texture) TEX_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
+    if (batch && (rc = dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}}))) return rc;
+    if (batch && scenes == 0) return dirt::stage_ok(report);
     const long long n = (long long)Ht * Wt * Ct;
-    hipLaunchKernelGGL(dirt::mip_collapse_kernel, dim3(dirt::capped_blocks(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), grad_pyramid, grad_texture, p);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!batch) hipLaunchKernelGGL(dirt::mip_collapse_kernel<>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, grad_pyramid, grad_texture, p);
+    else hipLaunchKernelGGL(dirt::mip_collapse_kernel<true>, dim3(dirt::capped_blocks(n), (unsigned)scenes), dim3(256), 0, s, grad_pyramid, grad_texture, p);
     return dirt::stage_hip(report, who, hipGetLastError());
+}
+
+int dirt_texture_mip_build(const float* texture, float* pyramid, int Ht, int Wt, int Ct, int levels, void* stream)
+{
+    return mip_build("dirt_texture_mip_build", texture, pyramid, false, 1, Ht, Wt, Ct, levels, stream);
+}
+
+int dirt_texture_mip_build_batch(const float* textures, float* pyramids, long long scenes, int Ht, int Wt, int Ct, int levels, void* stream)
+{
+    return mip_build("dirt_texture_mip_build_batch", textures, pyramids, true, scenes, Ht, Wt, Ct, levels, stream);
+}
+
+int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
+{
+    return mip_collapse("dirt_texture_mip_collapse", grad_pyramid, grad_texture, false, 1, Ht, Wt, Ct, levels, stream);
+}
+
+int dirt_texture_mip_collapse_batch(const float* grad_pyramids, float* grad_textures, long long scenes, int Ht, int Wt, int Ct, int levels,
+                                    void* stream)
+{
+    return mip_collapse("dirt_texture_mip_collapse_batch", grad_pyramids, grad_textures, true, scenes, Ht, Wt, Ct, levels, stream);
 }
 
 static int mip_sample_check(const char* who, const float* pyramid, const float* uvs, const float* lod, long long rows, long long cols,
@@ -487,32 +557,39 @@ static int mip_sample_check(const char* who, const float* pyramid, const float* 
     return DIRT_OK;
 }
 
-int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, long long rows,
-                                    long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride,
-                                    float lod_bias, unsigned flags, void* stream)
+// the per-scene extents of a batched look-up (p as mip_sample_check and the entry point filled it)
+static int mip_sample_scenes(const char* who, long long scenes, const dirt::MipParams& p)
 {
-    const char* who = "dirt_texture_sample_mip_forward";
+    const long long n = p.rows * p.cols;
+    return dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}, {n, p.uv_stride}, {n, p.Ct}, {n, p.mask ? p.mask_stride : 0}, {n, p.grad_uvs ? p.guv_stride : 0}});
+}
+
+static int mip_sample_forward(const char* who, const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, bool batch,
+                              long long scenes, long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
+                              int mask_stride, float lod_bias, unsigned flags, void* stream)
+{
     dirt::MipParams p{};
     int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, lod_bias, flags, p);
     if (rc) return rc;
     const long long n = rows * cols;
     if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
-    if (n == 0) return dirt::stage_ok(report);
+    if (batch && (rc = mip_sample_scenes(who, scenes, p))) return rc;
+    if (n == 0 || (batch && scenes == 0)) return dirt::stage_ok(report);
     p.out = out;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;   // (four channels: every scene's, as scene 0's)
     dirt::dispatch_channels(Ct, a16, [&](auto ct) {
-        hipLaunchKernelGGL(dirt::mip_forward_kernel<decltype(ct)::value>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, p);
+        if (!batch) hipLaunchKernelGGL(dirt::mip_forward_kernel<decltype(ct)::value>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((dirt::mip_forward_kernel<decltype(ct)::value, true>), dim3(dirt::capped_blocks(n), (unsigned)scenes), dim3(256), 0, s, p);
     });
     return dirt::stage_hip(report, who, hipGetLastError());
 }
 
-int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
-                                     float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, long long rows, long long cols,
-                                     int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
-                                     float lod_bias, unsigned flags, void* stream)
+static int mip_sample_backward(const char* who, const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
+                               float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, bool batch, long long scenes, long long rows,
+                               long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
+                               float lod_bias, unsigned flags, void* stream)
 {
-    const char* who = "dirt_texture_sample_mip_backward";
     dirt::MipParams p{};
     int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, lod_bias, flags, p);
     if (rc) return rc;
@@ -522,20 +599,59 @@ int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, con
     if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
     if (grad_lod && !lod) TEX_FAIL("%s: grad_lod needs lod", who);
     p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod; p.guv_stride = grad_uv_stride;
+    if (batch && (rc = mip_sample_scenes(who, scenes, p))) return rc;
     const dirt::TileGrid t = dirt::tile_grid(rows, cols);
     if (t.tiles > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
+    if (batch && scenes == 0) return dirt::stage_ok(report);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = dirt::clear_floats(grad_pyramid, dirt::mip_floats(p), s);
+    hipError_t e = dirt::clear_floats(grad_pyramid, dirt::mip_floats(p) * (batch ? scenes : 1), s);
     if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (n > 0) {
         const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
         dirt::dispatch_channels(Ct, a16, [&](auto ct) {
-            hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
+            if (!batch) hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
+            else hipLaunchKernelGGL((dirt::mip_backward_kernel<decltype(ct)::value, true>), dim3((unsigned)t.tiles, (unsigned)scenes), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
         });
         e = hipGetLastError();
         if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     }
+    if (batch) return dirt_texture_mip_collapse_batch(grad_pyramid, grad_texture, scenes, Ht, Wt, Ct, levels, stream);
     return dirt_texture_mip_collapse(grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
+}
+
+int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, long long rows,
+                                    long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride,
+                                    float lod_bias, unsigned flags, void* stream)
+{
+    return mip_sample_forward("dirt_texture_sample_mip_forward", pyramid, uvs, lod, mask, out, false, 1, rows, cols, image_rows, Ht, Wt, Ct, levels,
+                              uv_stride, mask_stride, lod_bias, flags, stream);
+}
+
+int dirt_texture_sample_mip_batch_forward(const float* pyramids, const float* uvs, const float* lod, const float* mask, float* out, long long scenes,
+                                          long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
+                                          int mask_stride, float lod_bias, unsigned flags, void* stream)
+{
+    return mip_sample_forward("dirt_texture_sample_mip_batch_forward", pyramids, uvs, lod, mask, out, true, scenes, rows, cols, image_rows, Ht, Wt, Ct,
+                              levels, uv_stride, mask_stride, lod_bias, flags, stream);
+}
+
+int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
+                                     float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, long long rows, long long cols,
+                                     int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
+                                     float lod_bias, unsigned flags, void* stream)
+{
+    return mip_sample_backward("dirt_texture_sample_mip_backward", pyramid, uvs, lod, mask, grad_out, grad_pyramid, grad_texture, grad_uvs, grad_lod,
+                               false, 1, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias, flags, stream);
+}
+
+int dirt_texture_sample_mip_batch_backward(const float* pyramids, const float* uvs, const float* lod, const float* mask, const float* grad_out,
+                                           float* grad_pyramids, float* grad_textures, float* grad_uvs, float* grad_lod, long long scenes,
+                                           long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
+                                           int grad_uv_stride, int mask_stride, float lod_bias, unsigned flags, void* stream)
+{
+    return mip_sample_backward("dirt_texture_sample_mip_batch_backward", pyramids, uvs, lod, mask, grad_out, grad_pyramids, grad_textures, grad_uvs,
+                               grad_lod, true, scenes, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias,
+                               flags, stream);
 }
 
 }  // extern "C"

@@ -241,6 +241,20 @@ int dirt_texture_sample_backward_image(const float *texture, const float *uvs, c
                                        float *grad_uvs, long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride,
                                        int grad_uv_stride, unsigned flags, void *stream);
 const char *dirt_texture_last_error(void);
+/* A TEXTURE PER SCENE (extends samples/textured.py:16-61, whose shader_fn has one texture for the whole batch): `scenes`
+ * look-ups of the two calls above in one launch each.  textures [scenes,Ht,Wt,Ct]; scene b's n (rows x cols) look-ups read
+ * textures[b]: its pairs start b * n * uv_stride floats after scene 0's (a slice of a contiguous G-buffer [scenes,H,W,C] is
+ * read in place with uv_stride = C), its out / grad_out b * n * Ct, its grad_uvs b * n * grad_uv_stride, its grad_textures
+ * b * Ht * Wt * Ct.  rows and cols are PER SCENE (a flat list: rows = 1): a 16 x 16 tile, or a 256 x 1 run, of the backward
+ * holds look-ups of one scene only.  grad_textures is cleared by the call (a kernel on `stream`) and fully written.  The
+ * checks of the single-texture calls, then: scenes >= 0, scenes x every per-scene extent fits 63 bits, scenes <= 65535 (one
+ * launch addresses no more; refused, not truncated), and a pixel grid with more than 2^31 - 1 rows, columns or tiles -- all
+ * DIRT_E_INVALID_ARGUMENT before any device work.  scenes == 0 launches nothing. */
+int dirt_texture_sample_batch_forward(const float *textures, const float *uvs, float *out, long long scenes, long long n, int Ht,
+                                      int Wt, int Ct, int uv_stride, unsigned flags, void *stream);
+int dirt_texture_sample_batch_backward_image(const float *textures, const float *uvs, const float *grad_out, float *grad_textures,
+                                             float *grad_uvs, long long scenes, long long rows, long long cols, int Ht, int Wt,
+                                             int Ct, int uv_stride, int grad_uv_stride, unsigned flags, void *stream);
 
 /*
  * Trilinear (mipmapped) texture look-up.  Extends the bilinear look-up above (samples/textured.py:16-61) with a mip
@@ -276,6 +290,28 @@ int dirt_texture_sample_mip_backward(const float *pyramid, const float *uvs, con
                                      float *grad_lod, long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct,
                                      int levels, int uv_stride, int grad_uv_stride, int mask_stride, float lod_bias,
                                      unsigned flags, void *stream);
+/* A TEXTURE PER SCENE for the four calls above (extends samples/textured.py:16-61 as dirt_texture_sample_batch_forward does;
+ * the same layout rule and the same three extra checks).  pyramids / grad_pyramids [scenes, pyramid_floats]: scene b's packed
+ * pyramid after scene b - 1's, each laid out as dirt_texture_mip_levels says.  The build is one launch for levels 0-5 of every
+ * scene and one more, a workgroup per scene, for any above; the collapse is one launch. */
+int dirt_texture_mip_build_batch(const float *textures, float *pyramids, long long scenes, int Ht, int Wt, int Ct, int levels,
+                                 void *stream);
+int dirt_texture_mip_collapse_batch(const float *grad_pyramids, float *grad_textures, long long scenes, int Ht, int Wt, int Ct,
+                                    int levels, void *stream);
+/* The trilinear look-up of `scenes` textures (extends samples/textured.py:16-61): rows x cols look-ups PER SCENE, stacked
+ * images of `image_rows` rows each (image_rows divides rows; a flat list: rows = image_rows = 1); scene b's pairs, lod, mask,
+ * out and gradients start b per-scene extents after scene 0's (lod and grad_lod b * rows * cols, mask b * rows * cols *
+ * mask_stride).  The footprint never looks across images or scenes. */
+int dirt_texture_sample_mip_batch_forward(const float *pyramids, const float *uvs, const float *lod, const float *mask, float *out,
+                                          long long scenes, long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct,
+                                          int levels, int uv_stride, int mask_stride, float lod_bias, unsigned flags, void *stream);
+/* Its gradient (extends samples/textured.py:16-61's): one clear of grad_pyramids (caller-owned scratch, [scenes,
+ * pyramid_floats]), one launch over every scene's tiles, one collapse into grad_textures [scenes,Ht,Wt,Ct] (fully written). */
+int dirt_texture_sample_mip_batch_backward(const float *pyramids, const float *uvs, const float *lod, const float *mask,
+                                           const float *grad_out, float *grad_pyramids, float *grad_textures, float *grad_uvs,
+                                           float *grad_lod, long long scenes, long long rows, long long cols, int image_rows, int Ht,
+                                           int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
+                                           float lod_bias, unsigned flags, void *stream);
 
 /*
  * G-buffer lighting of a deferred shader, fused.  Replaces the torch composition of the reference's shader
