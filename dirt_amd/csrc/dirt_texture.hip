@@ -149,29 +149,31 @@ __global__ __launch_bounds__(256) void texture_backward_kernel(TexParams p, int 
     }
 }
 
-// (both launchers: scenes < 0 is a single-texture call; scenes >= 0 a batch of that many, the BATCH kernels with the scene in gridDim.y.
-// Four channels: every per-scene extent is a multiple of 16 bytes, so scene 0's alignment is every scene's.)
-hipError_t launch_texture_forward(const TexParams& p, hipStream_t stream, long long scenes = -1)
+// (both launchers: a batch goes to the BATCH kernels with the scene in gridDim.y.  Four channels: every per-scene extent is a multiple of
+// 16 bytes, so scene 0's alignment is every scene's.)
+hipError_t launch_texture_forward(const TexParams& p, Scenes sc, hipStream_t stream)
 {
-    if (p.n == 0 || scenes == 0) return hipSuccess;
+    if (p.n == 0 || sc.none()) return hipSuccess;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.texture) & 15u) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15u) == 0;
-    dispatch_channels(p.Ct, a16, [&](auto ct) {
-        if (scenes < 0) hipLaunchKernelGGL(texture_forward_kernel<decltype(ct)::value>, dim3(capped_blocks(p.n)), dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((texture_forward_kernel<decltype(ct)::value, true>), dim3(capped_blocks(p.n), (unsigned)scenes), dim3(256), 0, stream, p);
-    });
+    dispatch_channels(p.Ct, a16, [&](auto ct) { dispatch_scenes(sc, [&](auto b) {
+        hipLaunchKernelGGL((texture_forward_kernel<decltype(ct)::value, decltype(b)::value>), scene_grid(capped_blocks(p.n), sc), dim3(256), 0, stream, p);
+    }); });
     return hipGetLastError();
 }
 
-hipError_t launch_texture_backward(const TexParams& p, long long rows, long long cols, hipStream_t stream, long long scenes = -1)
+// what a launch of the backward kernel can address: the tile index and the kernel's `rows` and `cols` are ints
+inline bool tiles_fit(const TileGrid& t, long long rows, long long cols) { return t.tiles <= 0x7fffffffll && cols <= 0x7fffffffll && rows <= 0x7fffffffll; }
+
+hipError_t launch_texture_backward(const TexParams& p, Scenes sc, long long rows, long long cols, hipStream_t stream)
 {
-    if (p.n == 0 || scenes == 0) return hipSuccess;
+    if (p.n == 0 || sc.none()) return hipSuccess;
     const TileGrid t = tile_grid(rows, cols);
-    if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) return hipErrorInvalidValue;
+    if (!tiles_fit(t, rows, cols)) return hipErrorInvalidValue;
     const bool a16 = (reinterpret_cast<uintptr_t>(p.grad_out) & 15u) == 0;
-    dispatch_channels(p.Ct, a16, [&](auto ct) {
-        if (scenes < 0) hipLaunchKernelGGL(texture_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
-        else hipLaunchKernelGGL((texture_backward_kernel<decltype(ct)::value, true>), dim3((unsigned)t.tiles, (unsigned)scenes), dim3(256), 0, stream, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
-    });
+    dispatch_channels(p.Ct, a16, [&](auto ct) { dispatch_scenes(sc, [&](auto b) {
+        hipLaunchKernelGGL((texture_backward_kernel<decltype(ct)::value, decltype(b)::value>), scene_grid((unsigned)t.tiles, sc), dim3(256), 0, stream, p, (int)rows,
+                           (int)cols, t.tw, t.th, (int)t.tiles_x);
+    }); });
     return hipGetLastError();
 }
 
@@ -205,39 +207,60 @@ static int tex_check(const char* who, const void* texture, const void* uvs, long
     return DIRT_OK;
 }
 
-int dirt_texture_sample_forward(const float* texture, const float* uvs, float* out, long long n, int Ht, int Wt, int Ct, int uv_stride,
-                                unsigned flags, void* stream)
+// (every entry point below and its batched form are one function: a single texture, or `sc.count` of them, checked by check_scenes after
+// the checks the two have in common, each scene's data a per-scene extent after the one before)
+
+static int tex_forward(const char* who, dirt::Scenes sc, const float* texture, const float* uvs, float* out, long long n, int Ht, int Wt, int Ct,
+                       int uv_stride, unsigned flags, void* stream)
 {
-    const char* who = "dirt_texture_sample_forward";
     int rc = tex_check(who, texture, uvs, n, Ht, Wt, Ct, uv_stride);
     if (rc) return rc;
     if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
+    if (sc.batch && (rc = dirt::check_scenes(who, sc.count, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}}))) return rc;
     dirt::TexParams p{};
     p.texture = texture; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.flags = flags; p.out = out;
-    return dirt::stage_hip(report, who, dirt::launch_texture_forward(p, reinterpret_cast<hipStream_t>(stream)));
+    return dirt::stage_hip(report, who, dirt::launch_texture_forward(p, sc, reinterpret_cast<hipStream_t>(stream)));
+}
+
+static int tex_backward(const char* who, dirt::Scenes sc, const float* texture, const float* uvs, const float* grad_out, float* grad_texture,
+                        float* grad_uvs, long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride, int grad_uv_stride, unsigned flags,
+                        void* stream)
+{
+    int rc = dirt::check_pixel_grid(who, rows, cols);
+    if (!rc) rc = tex_check(who, texture, uvs, rows * cols, Ht, Wt, Ct, uv_stride);
+    if (rc) return rc;
+    const long long n = rows * cols;
+    if (n > 0 && (!grad_out || !grad_texture)) TEX_FAIL("%s: grad_out / %s is NULL", who, sc.batch ? "grad_textures" : "grad_texture");
+    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
+    if (sc.batch && (rc = dirt::check_scenes(who, sc.count, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}, {n, grad_uvs ? grad_uv_stride : 0}}))) return rc;
+    if (!grad_texture || sc.none()) return dirt::stage_ok(report);   // (n == 0 without a gradient buffer, or no scenes: nothing to clear, nothing to launch)
+    // a pixel grid the kernel cannot address: a batch is refused here, before any device work; a single texture has its gradient cleared
+    // and is then refused by the launcher (DIRT_E_HIP)
+    if (sc.batch && !dirt::tiles_fit(dirt::tile_grid(rows, cols), rows, cols)) TEX_FAIL("%s: pixel grid too large (rows=%lld cols=%lld)", who, rows, cols);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = dirt::clear_floats(grad_texture, sc.count * ((long long)Ht * Wt * Ct), s);
+    if (e == hipSuccess) {
+        dirt::TexParams p{};
+        p.texture = texture; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.guv_stride = grad_uv_stride;
+        p.flags = flags; p.grad_out = grad_out; p.grad_texture = grad_texture; p.grad_uvs = grad_uvs;
+        e = dirt::launch_texture_backward(p, sc, rows, cols, s);
+    }
+    return dirt::stage_hip(report, who, e);
+}
+
+int dirt_texture_sample_forward(const float* texture, const float* uvs, float* out, long long n, int Ht, int Wt, int Ct, int uv_stride,
+                                unsigned flags, void* stream)
+{
+    return tex_forward("dirt_texture_sample_forward", dirt::ONE_TEXTURE, texture, uvs, out, n, Ht, Wt, Ct, uv_stride, flags, stream);
 }
 
 int dirt_texture_sample_backward_image(const float* texture, const float* uvs, const float* grad_out, float* grad_texture, float* grad_uvs,
                                        long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride, int grad_uv_stride, unsigned flags,
                                        void* stream)
 {
-    const char* who = "dirt_texture_sample_backward";   // (the flat-list entry point's name: it forwards here)
-    int rc = dirt::check_pixel_grid(who, rows, cols);
-    if (!rc) rc = tex_check(who, texture, uvs, rows * cols, Ht, Wt, Ct, uv_stride);
-    if (rc) return rc;
-    const long long n = rows * cols;
-    if (n > 0 && (!grad_out || !grad_texture)) TEX_FAIL("%s: grad_out / grad_texture is NULL", who);
-    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
-    if (!grad_texture) return dirt::stage_ok(report);   // (n == 0 without a gradient buffer: nothing to clear, nothing to launch)
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = dirt::clear_floats(grad_texture, (long long)Ht * Wt * Ct, s);
-    if (e == hipSuccess) {
-        dirt::TexParams p{};
-        p.texture = texture; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.guv_stride = grad_uv_stride;
-        p.flags = flags; p.grad_out = grad_out; p.grad_texture = grad_texture; p.grad_uvs = grad_uvs;
-        e = dirt::launch_texture_backward(p, rows, cols, s);
-    }
-    return dirt::stage_hip(report, who, e);
+    // (reports under the flat-list entry point's name, which forwards here)
+    return tex_backward("dirt_texture_sample_backward", dirt::ONE_TEXTURE, texture, uvs, grad_out, grad_texture, grad_uvs, rows, cols, Ht, Wt, Ct, uv_stride,
+                        grad_uv_stride, flags, stream);
 }
 
 int dirt_texture_sample_backward(const float* texture, const float* uvs, const float* grad_out, float* grad_texture, float* grad_uvs,
@@ -247,47 +270,18 @@ int dirt_texture_sample_backward(const float* texture, const float* uvs, const f
     return dirt_texture_sample_backward_image(texture, uvs, grad_out, grad_texture, grad_uvs, 1, n, Ht, Wt, Ct, uv_stride, grad_uv_stride, flags, stream);
 }
 
-// ---- a texture per scene (dirt_texture_common.h: batched launches): the checks of the entry points above, then those of the scene count
-
 int dirt_texture_sample_batch_forward(const float* textures, const float* uvs, float* out, long long scenes, long long n, int Ht, int Wt, int Ct,
                                       int uv_stride, unsigned flags, void* stream)
 {
-    const char* who = "dirt_texture_sample_batch_forward";
-    int rc = tex_check(who, textures, uvs, n, Ht, Wt, Ct, uv_stride);
-    if (rc) return rc;
-    if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
-    rc = dirt::check_scenes(who, scenes, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}});
-    if (rc) return rc;
-    dirt::TexParams p{};
-    p.texture = textures; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.flags = flags; p.out = out;
-    return dirt::stage_hip(report, who, dirt::launch_texture_forward(p, reinterpret_cast<hipStream_t>(stream), scenes));
+    return tex_forward("dirt_texture_sample_batch_forward", {true, scenes}, textures, uvs, out, n, Ht, Wt, Ct, uv_stride, flags, stream);
 }
 
 int dirt_texture_sample_batch_backward_image(const float* textures, const float* uvs, const float* grad_out, float* grad_textures, float* grad_uvs,
                                              long long scenes, long long rows, long long cols, int Ht, int Wt, int Ct, int uv_stride,
                                              int grad_uv_stride, unsigned flags, void* stream)
 {
-    const char* who = "dirt_texture_sample_batch_backward_image";
-    int rc = dirt::check_pixel_grid(who, rows, cols);
-    if (!rc) rc = tex_check(who, textures, uvs, rows * cols, Ht, Wt, Ct, uv_stride);
-    if (rc) return rc;
-    const long long n = rows * cols;
-    if (n > 0 && (!grad_out || !grad_textures)) TEX_FAIL("%s: grad_out / grad_textures is NULL", who);
-    if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
-    rc = dirt::check_scenes(who, scenes, {{(long long)Ht * Wt, Ct}, {n, uv_stride}, {n, Ct}, {n, grad_uvs ? grad_uv_stride : 0}});
-    if (rc) return rc;
-    if (!grad_textures || scenes == 0) return dirt::stage_ok(report);   // (nothing to clear, nothing to launch)
-    const dirt::TileGrid t = dirt::tile_grid(rows, cols);
-    if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large (rows=%lld cols=%lld)", who, rows, cols);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = dirt::clear_floats(grad_textures, scenes * ((long long)Ht * Wt * Ct), s);
-    if (e == hipSuccess) {
-        dirt::TexParams p{};
-        p.texture = textures; p.uvs = uvs; p.n = n; p.Ht = Ht; p.Wt = Wt; p.Ct = Ct; p.uv_stride = uv_stride; p.guv_stride = grad_uv_stride;
-        p.flags = flags; p.grad_out = grad_out; p.grad_texture = grad_textures; p.grad_uvs = grad_uvs;
-        e = dirt::launch_texture_backward(p, rows, cols, s, scenes);
-    }
-    return dirt::stage_hip(report, who, e);
+    return tex_backward("dirt_texture_sample_batch_backward_image", {true, scenes}, textures, uvs, grad_out, grad_textures, grad_uvs, rows, cols, Ht, Wt,
+                        Ct, uv_stride, grad_uv_stride, flags, stream);
 }
 
 }  // extern "C"

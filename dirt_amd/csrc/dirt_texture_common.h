@@ -1,7 +1,7 @@
 // dirt_texture_common.h -- what the texture kernels share (dirt_texture.hip: nearest / bilinear; dirt_texture_mip.hip: trilinear over a
 // mip pyramid).  Per look-up: (u, v) -> fractional (row, column) index of the reference's samples/textured.py:16-26, the four bilinear taps of
 // :36-60, the channel-vector loads / stores, the blend.  The pieces of the backward tile scheme.  The rule of a batched launch (a texture per scene).
-// Host: the pixel grid, the scene count of a batch, the clear of a buffer.
+// Host: the pixel grid, a launch for one texture or a batch (Scenes), the scene count of a batch, the clear of a buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -153,10 +153,19 @@ inline TileGrid tile_grid(long long rows, long long cols)
 // after scene 0's, the scene is gridDim.y, and blockIdx.x / gridDim.x mean what they mean in a single-texture launch: a tile or a
 // grid-stride loop never sees look-ups of two scenes.  A kernel's BATCH instantiation moves its base pointers to its scene's data once
 // (workgroup-uniform, in size_t), before the per-look-up code, which is the single-texture kernel's; a pointer that is missing stays so.
+// Host: an entry point and its batched form are one function that takes a `Scenes`; it checks the count of a batch with check_scenes and
+// launches through dispatch_scenes on scene_grid, so each kernel's two instantiations share one launch statement.
 constexpr long long TEX_MAX_SCENES = 65535;   // gridDim.y
 template <class T> __device__ __forceinline__ void scene_shift(T*& p, size_t floats) { if (p) p += floats; }
 
-// host: the scene count of a batched entry point and its per-scene extents in floats, each a count x a stride (both >= 0)
+// host: what a call works on -- one texture (`count` 1), or a batch of `count` of them (the caller's number, for check_scenes to judge)
+struct Scenes { bool batch; long long count; bool none() const { return batch && count == 0; } };   // none(): a batch of zero scenes
+constexpr Scenes ONE_TEXTURE{false, 1};
+inline dim3 scene_grid(unsigned blocks, Scenes s) { return s.batch ? dim3(blocks, (unsigned)s.count) : dim3(blocks); }
+// f(std::false_type) for a single texture, f(std::true_type) for a batch: a kernel's BATCH argument, as dispatch_channels hands over CT
+template <class F> inline void dispatch_scenes(Scenes s, F&& f) { if (!s.batch) f(std::false_type{}); else f(std::true_type{}); }
+
+// the scene count of a batched entry point and its per-scene extents in floats, each a count x a stride (both >= 0)
 struct SceneExtent { long long count, stride; };
 inline int check_scenes(const char* who, long long scenes, std::initializer_list<SceneExtent> extents)
 {

@@ -475,69 +475,65 @@ static int mip_check(const char* who, int Ht, int Wt, int Ct, int levels, dirt::
     return DIRT_OK;
 }
 
-// (every entry point below and its batched form are one function: without `batch` it is the single-texture call and launches the kernels'
-// single-texture instantiations; with it, `scenes` textures, checked by check_scenes, go to the BATCH kernels with the scene in gridDim.y)
+// (every entry point below and its batched form are one function that takes a dirt::Scenes: a single texture launches the kernels'
+// single-texture instantiations; a batch of `sc.count` textures, checked by check_scenes, their BATCH ones with the scene in gridDim.y)
 
-static int mip_build(const char* who, const float* texture, float* pyramid, bool batch, long long scenes, int Ht, int Wt, int Ct, int levels, void* stream)
+static int mip_build(const char* who, dirt::Scenes sc, const float* texture, float* pyramid, int Ht, int Wt, int Ct, int levels, void* stream)
 {
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
     if (!texture || !pyramid) TEX_FAIL("%s: texture / pyramid is NULL", who);
-    if (batch && (rc = dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}}))) return rc;
-    if (batch && scenes == 0) return dirt::stage_ok(report);
-    const unsigned gy = batch ? (unsigned)scenes : 1u;
+    if (sc.batch && (rc = dirt::check_scenes(who, sc.count, {{dirt::mip_floats(p), 1}}))) return rc;
+    if (sc.none()) return dirt::stage_ok(report);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (levels == 1)   // (a batch of one-level pyramids is the batch of textures)
-        return dirt::stage_hip(report, who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct * gy, hipMemcpyDeviceToDevice, s));
+        return dirt::stage_hip(report, who, hipMemcpyAsync(pyramid, texture, sizeof(float) * (size_t)Ht * Wt * Ct * sc.count, hipMemcpyDeviceToDevice, s));
     const int kt = min(levels - 1, dirt::MIP_TILE_LEVELS);
     const int tiles_y = dirt::mip_dim(Ht, kt), tiles_x = dirt::mip_dim(Wt, kt);
     if ((long long)tiles_x * tiles_y > 0x7fffffffll) TEX_FAIL("%s: texture too large", who);
-    if (!batch) {
-        hipLaunchKernelGGL(dirt::mip_build_blocks_kernel<>, dim3((unsigned)(tiles_x * tiles_y)), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
-        if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel<>, dim3(1), dim3(1024), 0, s, pyramid, p, kt);
-    } else {
-        hipLaunchKernelGGL(dirt::mip_build_blocks_kernel<true>, dim3((unsigned)(tiles_x * tiles_y), gy), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
-        if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel<true>, dim3(1, gy), dim3(1024), 0, s, pyramid, p, kt);
-    }
+    dirt::dispatch_scenes(sc, [&](auto b) {
+        hipLaunchKernelGGL(dirt::mip_build_blocks_kernel<decltype(b)::value>, dirt::scene_grid(tiles_x * tiles_y, sc), dim3(256), 0, s, texture, pyramid, p, kt, tiles_x);
+        if (levels - 1 > kt) hipLaunchKernelGGL(dirt::mip_build_top_kernel<decltype(b)::value>, dirt::scene_grid(1, sc), dim3(1024), 0, s, pyramid, p, kt);
+    });
     return dirt::stage_hip(report, who, hipGetLastError());
 }
 
-static int mip_collapse(const char* who, const float* grad_pyramid, float* grad_texture, bool batch, long long scenes, int Ht, int Wt, int Ct, int levels,
-                        void* stream)
+static int mip_collapse(const char* who, dirt::Scenes sc, const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
 {
     dirt::MipParams p{};
     int rc = mip_check(who, Ht, Wt, Ct, levels, p);
     if (rc) return rc;
     if (!grad_pyramid || !grad_texture) TEX_FAIL("%s: grad_pyramid / grad_texture is NULL", who);
-    if (batch && (rc = dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}}))) return rc;
-    if (batch && scenes == 0) return dirt::stage_ok(report);
+    if (sc.batch && (rc = dirt::check_scenes(who, sc.count, {{dirt::mip_floats(p), 1}}))) return rc;
+    if (sc.none()) return dirt::stage_ok(report);
     const long long n = (long long)Ht * Wt * Ct;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!batch) hipLaunchKernelGGL(dirt::mip_collapse_kernel<>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, grad_pyramid, grad_texture, p);
-    else hipLaunchKernelGGL(dirt::mip_collapse_kernel<true>, dim3(dirt::capped_blocks(n), (unsigned)scenes), dim3(256), 0, s, grad_pyramid, grad_texture, p);
+    dirt::dispatch_scenes(sc, [&](auto b) {
+        hipLaunchKernelGGL(dirt::mip_collapse_kernel<decltype(b)::value>, dirt::scene_grid(dirt::capped_blocks(n), sc), dim3(256), 0, s, grad_pyramid, grad_texture, p);
+    });
     return dirt::stage_hip(report, who, hipGetLastError());
 }
 
 int dirt_texture_mip_build(const float* texture, float* pyramid, int Ht, int Wt, int Ct, int levels, void* stream)
 {
-    return mip_build("dirt_texture_mip_build", texture, pyramid, false, 1, Ht, Wt, Ct, levels, stream);
+    return mip_build("dirt_texture_mip_build", dirt::ONE_TEXTURE, texture, pyramid, Ht, Wt, Ct, levels, stream);
 }
 
 int dirt_texture_mip_build_batch(const float* textures, float* pyramids, long long scenes, int Ht, int Wt, int Ct, int levels, void* stream)
 {
-    return mip_build("dirt_texture_mip_build_batch", textures, pyramids, true, scenes, Ht, Wt, Ct, levels, stream);
+    return mip_build("dirt_texture_mip_build_batch", {true, scenes}, textures, pyramids, Ht, Wt, Ct, levels, stream);
 }
 
 int dirt_texture_mip_collapse(const float* grad_pyramid, float* grad_texture, int Ht, int Wt, int Ct, int levels, void* stream)
 {
-    return mip_collapse("dirt_texture_mip_collapse", grad_pyramid, grad_texture, false, 1, Ht, Wt, Ct, levels, stream);
+    return mip_collapse("dirt_texture_mip_collapse", dirt::ONE_TEXTURE, grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
 }
 
 int dirt_texture_mip_collapse_batch(const float* grad_pyramids, float* grad_textures, long long scenes, int Ht, int Wt, int Ct, int levels,
                                     void* stream)
 {
-    return mip_collapse("dirt_texture_mip_collapse_batch", grad_pyramids, grad_textures, true, scenes, Ht, Wt, Ct, levels, stream);
+    return mip_collapse("dirt_texture_mip_collapse_batch", {true, scenes}, grad_pyramids, grad_textures, Ht, Wt, Ct, levels, stream);
 }
 
 static int mip_sample_check(const char* who, const float* pyramid, const float* uvs, const float* lod, long long rows, long long cols,
@@ -564,8 +560,8 @@ static int mip_sample_scenes(const char* who, long long scenes, const dirt::MipP
     return dirt::check_scenes(who, scenes, {{dirt::mip_floats(p), 1}, {n, p.uv_stride}, {n, p.Ct}, {n, p.mask ? p.mask_stride : 0}, {n, p.grad_uvs ? p.guv_stride : 0}});
 }
 
-static int mip_sample_forward(const char* who, const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, bool batch,
-                              long long scenes, long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
+static int mip_sample_forward(const char* who, dirt::Scenes sc, const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out,
+                              long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
                               int mask_stride, float lod_bias, unsigned flags, void* stream)
 {
     dirt::MipParams p{};
@@ -573,22 +569,21 @@ static int mip_sample_forward(const char* who, const float* pyramid, const float
     if (rc) return rc;
     const long long n = rows * cols;
     if (n > 0 && !out) TEX_FAIL("%s: out is NULL", who);
-    if (batch && (rc = mip_sample_scenes(who, scenes, p))) return rc;
-    if (n == 0 || (batch && scenes == 0)) return dirt::stage_ok(report);
+    if (sc.batch && (rc = mip_sample_scenes(who, sc.count, p))) return rc;
+    if (n == 0 || sc.none()) return dirt::stage_ok(report);
     p.out = out;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool a16 = (reinterpret_cast<uintptr_t>(pyramid) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;   // (four channels: every scene's, as scene 0's)
-    dirt::dispatch_channels(Ct, a16, [&](auto ct) {
-        if (!batch) hipLaunchKernelGGL(dirt::mip_forward_kernel<decltype(ct)::value>, dim3(dirt::capped_blocks(n)), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dirt::mip_forward_kernel<decltype(ct)::value, true>), dim3(dirt::capped_blocks(n), (unsigned)scenes), dim3(256), 0, s, p);
-    });
+    dirt::dispatch_channels(Ct, a16, [&](auto ct) { dirt::dispatch_scenes(sc, [&](auto b) {
+        hipLaunchKernelGGL((dirt::mip_forward_kernel<decltype(ct)::value, decltype(b)::value>), dirt::scene_grid(dirt::capped_blocks(n), sc), dim3(256), 0, s, p);
+    }); });
     return dirt::stage_hip(report, who, hipGetLastError());
 }
 
-static int mip_sample_backward(const char* who, const float* pyramid, const float* uvs, const float* lod, const float* mask, const float* grad_out,
-                               float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, bool batch, long long scenes, long long rows,
-                               long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
-                               float lod_bias, unsigned flags, void* stream)
+static int mip_sample_backward(const char* who, dirt::Scenes sc, const float* pyramid, const float* uvs, const float* lod, const float* mask,
+                               const float* grad_out, float* grad_pyramid, float* grad_texture, float* grad_uvs, float* grad_lod, long long rows, long long cols,
+                               int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride, float lod_bias,
+                               unsigned flags, void* stream)
 {
     dirt::MipParams p{};
     int rc = mip_sample_check(who, pyramid, uvs, lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, mask_stride, mask, lod_bias, flags, p);
@@ -599,31 +594,31 @@ static int mip_sample_backward(const char* who, const float* pyramid, const floa
     if (grad_uvs && grad_uv_stride < 2) TEX_FAIL("%s: grad_uv_stride < 2", who);
     if (grad_lod && !lod) TEX_FAIL("%s: grad_lod needs lod", who);
     p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_uvs = grad_uvs; p.grad_lod = grad_lod; p.guv_stride = grad_uv_stride;
-    if (batch && (rc = mip_sample_scenes(who, scenes, p))) return rc;
+    if (sc.batch && (rc = mip_sample_scenes(who, sc.count, p))) return rc;
     const dirt::TileGrid t = dirt::tile_grid(rows, cols);
     if (t.tiles > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large", who);
-    if (batch && scenes == 0) return dirt::stage_ok(report);
+    if (sc.none()) return dirt::stage_ok(report);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = dirt::clear_floats(grad_pyramid, dirt::mip_floats(p) * (batch ? scenes : 1), s);
+    hipError_t e = dirt::clear_floats(grad_pyramid, dirt::mip_floats(p) * sc.count, s);
     if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     if (n > 0) {
         const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
-        dirt::dispatch_channels(Ct, a16, [&](auto ct) {
-            if (!batch) hipLaunchKernelGGL(dirt::mip_backward_kernel<decltype(ct)::value>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
-            else hipLaunchKernelGGL((dirt::mip_backward_kernel<decltype(ct)::value, true>), dim3((unsigned)t.tiles, (unsigned)scenes), dim3(256), 0, s, p, t.tw, t.th, (int)t.tiles_x);
-        });
+        dirt::dispatch_channels(Ct, a16, [&](auto ct) { dirt::dispatch_scenes(sc, [&](auto b) {
+            hipLaunchKernelGGL((dirt::mip_backward_kernel<decltype(ct)::value, decltype(b)::value>), dirt::scene_grid((unsigned)t.tiles, sc), dim3(256), 0, s, p, t.tw,
+                               t.th, (int)t.tiles_x);
+        }); });
         e = hipGetLastError();
         if (e != hipSuccess) return dirt::stage_hip(report, who, e);
     }
-    if (batch) return dirt_texture_mip_collapse_batch(grad_pyramid, grad_texture, scenes, Ht, Wt, Ct, levels, stream);
-    return dirt_texture_mip_collapse(grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
+    // (the collapse reports under its own entry point's name)
+    return mip_collapse(sc.batch ? "dirt_texture_mip_collapse_batch" : "dirt_texture_mip_collapse", sc, grad_pyramid, grad_texture, Ht, Wt, Ct, levels, stream);
 }
 
 int dirt_texture_sample_mip_forward(const float* pyramid, const float* uvs, const float* lod, const float* mask, float* out, long long rows,
                                     long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int mask_stride,
                                     float lod_bias, unsigned flags, void* stream)
 {
-    return mip_sample_forward("dirt_texture_sample_mip_forward", pyramid, uvs, lod, mask, out, false, 1, rows, cols, image_rows, Ht, Wt, Ct, levels,
+    return mip_sample_forward("dirt_texture_sample_mip_forward", dirt::ONE_TEXTURE, pyramid, uvs, lod, mask, out, rows, cols, image_rows, Ht, Wt, Ct, levels,
                               uv_stride, mask_stride, lod_bias, flags, stream);
 }
 
@@ -631,7 +626,7 @@ int dirt_texture_sample_mip_batch_forward(const float* pyramids, const float* uv
                                           long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
                                           int mask_stride, float lod_bias, unsigned flags, void* stream)
 {
-    return mip_sample_forward("dirt_texture_sample_mip_batch_forward", pyramids, uvs, lod, mask, out, true, scenes, rows, cols, image_rows, Ht, Wt, Ct,
+    return mip_sample_forward("dirt_texture_sample_mip_batch_forward", {true, scenes}, pyramids, uvs, lod, mask, out, rows, cols, image_rows, Ht, Wt, Ct,
                               levels, uv_stride, mask_stride, lod_bias, flags, stream);
 }
 
@@ -640,8 +635,8 @@ int dirt_texture_sample_mip_backward(const float* pyramid, const float* uvs, con
                                      int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
                                      float lod_bias, unsigned flags, void* stream)
 {
-    return mip_sample_backward("dirt_texture_sample_mip_backward", pyramid, uvs, lod, mask, grad_out, grad_pyramid, grad_texture, grad_uvs, grad_lod,
-                               false, 1, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias, flags, stream);
+    return mip_sample_backward("dirt_texture_sample_mip_backward", dirt::ONE_TEXTURE, pyramid, uvs, lod, mask, grad_out, grad_pyramid, grad_texture, grad_uvs, grad_lod,
+                               rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias, flags, stream);
 }
 
 int dirt_texture_sample_mip_batch_backward(const float* pyramids, const float* uvs, const float* lod, const float* mask, const float* grad_out,
@@ -649,8 +644,8 @@ int dirt_texture_sample_mip_batch_backward(const float* pyramids, const float* u
                                            long long rows, long long cols, int image_rows, int Ht, int Wt, int Ct, int levels, int uv_stride,
                                            int grad_uv_stride, int mask_stride, float lod_bias, unsigned flags, void* stream)
 {
-    return mip_sample_backward("dirt_texture_sample_mip_batch_backward", pyramids, uvs, lod, mask, grad_out, grad_pyramids, grad_textures, grad_uvs,
-                               grad_lod, true, scenes, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias,
+    return mip_sample_backward("dirt_texture_sample_mip_batch_backward", {true, scenes}, pyramids, uvs, lod, mask, grad_out, grad_pyramids, grad_textures, grad_uvs,
+                               grad_lod, rows, cols, image_rows, Ht, Wt, Ct, levels, uv_stride, grad_uv_stride, mask_stride, lod_bias,
                                flags, stream);
 }
 

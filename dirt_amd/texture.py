@@ -66,9 +66,18 @@ def _check(rc):
 _call = functools.partial(_stage.call, check=_check)   # (entry point, device, its arguments but the stream): raises as `_check` says
 
 
-def _check_texture(texture, who):
-    if texture.dim() != 3:
-        raise ValueError('%s expects texture to be 3D [height, width, channels], got shape %s' % (who, tuple(texture.shape)))
+def _check_texture(texture, who, batch=False):
+    """One texture [height, width, channels], or with `batch` a texture per scene."""
+    name, dims, axes = ('textures', 4, 'scenes, height, width, channels') if batch else ('texture', 3, 'height, width, channels')
+    if texture.dim() != dims:
+        raise ValueError('%s expects %s to be %dD [%s], got shape %s' % (who, name, dims, axes, tuple(texture.shape)))
+
+
+def _lookup_flags(mode, filter, lod, lod_bias, mask, max_level):
+    """`mode` and `filter` as the entry points' flags; the four keyword arguments of a trilinear look-up are refused with any other filter."""
+    if filter != 'trilinear' and (lod is not None or lod_bias != 0.0 or mask is not None or max_level is not None):
+        raise ValueError("lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
+    return {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode] | {'bilinear': 0, 'trilinear': 0, 'nearest': _lib.TEX_NEAREST}[filter]
 
 
 def _check_lookup(texture, uvs):
@@ -168,11 +177,9 @@ def sample_texture_uv(texture, uvs, mode='repeat', filter='bilinear', *, lod=Non
     footprint of (u, v) + `lod_bias`, which needs `uvs` as images [..., H, W, 2]; `mask` [..., H, W] (e.g. gbuffer[..., 0],
     read in place) marks the pixels whose (u, v) count as neighbours.  `max_level` caps the pyramid.  Also differentiable
     with respect to `lod`; the footprint's level is held constant.  The four keyword arguments apply to 'trilinear' only."""
+    flags = _lookup_flags(mode, filter, lod, lod_bias, mask, max_level)
     if filter == 'trilinear':
-        return _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level)
-    if lod is not None or lod_bias != 0.0 or mask is not None or max_level is not None:
-        raise ValueError("lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
-    flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode] | {'bilinear': 0, 'nearest': _lib.TEX_NEAREST}[filter]
+        return _sample_trilinear(texture, uvs, flags, lod, lod_bias, mask, max_level)
     _check_lookup(texture, uvs)
     _stage.require_gpu(texture, 'dirt_amd.texture.sample_texture_uv')
     return _SampleTextureUV.apply(texture.to(torch.float32), uvs.to(torch.float32), flags, None)
@@ -302,8 +309,7 @@ def _check_trilinear(uvs, lod, mask, max_level, image_dims=3):
         raise ValueError('mask marks the neighbours of the footprint level of detail; it does not apply with an explicit lod')
 
 
-def _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level):
-    flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode]
+def _sample_trilinear(texture, uvs, flags, lod, lod_bias, mask, max_level):
     _check_lookup(texture, uvs)
     _check_trilinear(uvs, lod, mask, max_level)
     _stage.require_gpu(texture, 'dirt_amd.texture.sample_texture_uv')
@@ -311,11 +317,6 @@ def _sample_trilinear(texture, uvs, mode, lod, lod_bias, mask, max_level):
 
 
 # ---- a texture per scene: the same kernels, the scene a launch dimension -------------------------------------
-
-def _check_textures(textures, who):
-    if textures.dim() != 4:
-        raise ValueError('%s expects textures to be 4D [scenes, height, width, channels], got shape %s' % (who, tuple(textures.shape)))
-
 
 def _require_gpu_batch(t, name, who):
     if not t.is_cuda:
@@ -330,10 +331,8 @@ def sample_texture_uv_batch(textures, uvs, mode='repeat', filter='bilinear', *, 
     without `lod` needs uvs as images [B, ..., H, W, 2].  A slice gbuffer[..., a:a+2] of a contiguous [B, H, W, Cg] G-buffer
     and mask=gbuffer[..., 0] are read in place.  Differentiable with respect to textures, uvs and lod."""
     who = 'sample_texture_uv_batch'
-    if filter != 'trilinear' and (lod is not None or lod_bias != 0.0 or mask is not None or max_level is not None):
-        raise ValueError("lod, lod_bias, mask and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
-    flags = {'repeat': 0, 'clamp': _lib.TEX_CLAMP}[mode] | {'bilinear': 0, 'trilinear': 0, 'nearest': _lib.TEX_NEAREST}[filter]
-    _check_textures(textures, who)
+    flags = _lookup_flags(mode, filter, lod, lod_bias, mask, max_level)
+    _check_texture(textures, who, batch=True)
     if uvs.dim() < 2 or uvs.shape[-1] != 2:
         raise ValueError('%s expects uvs of shape [scenes, ..., 2], got %s' % (who, tuple(uvs.shape)))
     if uvs.shape[0] != textures.shape[0]:
@@ -353,7 +352,7 @@ def mip_pyramid_batch(textures, max_level=None):
     """`mip_pyramid` of B textures [B, Ht, Wt, C] in one launch per level group -> [level 0, level 1, ...], level k
     [B, max(Ht >> k, 1), max(Wt >> k, 1), C].  The levels are views into one packed buffer [B, pyramid floats]: scene b's
     pyramid after scene b - 1's, each laid out as `mip_pyramid`'s.  Differentiable with respect to the textures."""
-    _check_textures(textures, 'mip_pyramid_batch')
+    _check_texture(textures, 'mip_pyramid_batch', batch=True)
     _require_gpu_batch(textures, 'textures', 'mip_pyramid_batch')
     scenes, ht, wt, ct = (int(d) for d in textures.shape)
     levels, floats, geo = _mip_geometry(ht, wt, ct, max_level)
