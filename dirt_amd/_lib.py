@@ -58,7 +58,7 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
            'dirt_texture_sample_batch_forward', 'dirt_texture_sample_batch_backward_image', 'dirt_texture_mip_build_batch',
            'dirt_texture_mip_collapse_batch', 'dirt_texture_sample_mip_batch_forward', 'dirt_texture_sample_mip_batch_backward',
-           'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward',
+           'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward', 'dirt_shade_albedo_forward', 'dirt_shade_albedo_backward',
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
            'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward',
@@ -149,6 +149,12 @@ def load():
         lib.dirt_shade_forward.restype = i
         lib.dirt_shade_backward.argtypes = [fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
         lib.dirt_shade_backward.restype = i
+    if hasattr(lib, 'dirt_shade_albedo_forward') or not override:   # ... with the colours in an image of their own (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_shade_albedo_forward.argtypes = [fp, fp, fp, fp, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
+        lib.dirt_shade_albedo_forward.restype = i
+        lib.dirt_shade_albedo_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, i, i, i, i, u, u, f32, f32, u, vp]
+        lib.dirt_shade_albedo_backward.restype = i
     if hasattr(lib, 'dirt_geometry_forward') or not override:   # fused vertex stage (ABI 4, additive)
         lib.dirt_geometry_scratch_bytes.argtypes = [ll, ll, ll]
         lib.dirt_geometry_scratch_bytes.restype = sz

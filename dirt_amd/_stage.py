@@ -1,5 +1,5 @@
 """What the Python wrappers of the fused stages share (geometry, skinning, kinematics, blendshapes; of shading the call and
-the backward plumbing; of the texture look-up the call, the pointers and the CPU refusal).  Private: the stages' own modules are the interface.
+the backward plumbing; of the texture look-up the call, the pointers and the CPU refusal; of both the rule for rows read in place).  Private: the stages' own modules are the interface.
 """
 import torch
 
@@ -90,6 +90,24 @@ def require_gpu(t, function):
 def ptr(t):
     """The address of a tensor as the C ABI takes it: NULL for a missing or an empty one."""
     return t.data_ptr() or None if t is not None else None
+
+
+def rows_in_place(t, width):
+    """(tensor to pass, element stride between rows) such that row i of `width` floats starts at data_ptr + 4 * i * stride: a
+    slice `gbuffer[..., a:a + width]` of a contiguous G-buffer (or the first or last channels of an RGBA image) is read in
+    place, anything else is made contiguous.  The (u, v) pairs of the texture look-ups and the colours of `shade_gbuffer`."""
+    if t.stride(-1) == 1 and t.dim() >= 2:
+        step = t.stride(-2)
+        ok = step >= width
+        expect = step
+        for d in range(t.dim() - 2, -1, -1):
+            if t.stride(d) != expect:
+                ok = False
+                break
+            expect *= t.shape[d]
+        if ok:
+            return t, step
+    return t.contiguous(), width
 
 
 def call(function, dev, *arguments, check=_lib.check):

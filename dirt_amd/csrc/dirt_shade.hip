@@ -25,9 +25,21 @@
 // parameter gradients in registers; these are summed over the wave with DPP adds, over the four waves in LDS, and leave the
 // workgroup as ONE row of partial sums in caller-owned scratch.  shade_reduce_kernel adds the rows in a fixed order: no
 // atomics, and the same bits on every run.
+//
+// ALBEDO: the colour comes from a second image, [scenes, pixels, >= 3 floats apart], instead of three channels of the G-buffer,
+// and its gradient leaves as a second, dense image (dirt_shade_albedo_forward / _backward): the flag changes where px.c is
+// loaded from and where gc[3] is stored, nothing after the load.  This file is two translation units of the parallel build:
+// by itself the kernels and entry points of the channel path, and through dirt_shade_albedo.hip (which defines
+// DIRT_SHADE_ALBEDO_UNIT and includes it) the ALBEDO = true instantiations and their two entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dirt_stage.h"
+
+#ifdef DIRT_SHADE_ALBEDO_UNIT
+#define SHADE_UNIT_ALBEDO true
+#else
+#define SHADE_UNIT_ALBEDO false
+#endif
 
 namespace dirt {
 
@@ -49,6 +61,15 @@ struct ShadeParams {
     int clamp;
     float lo, hi;
 };
+
+// what the ALBEDO kernels take: in a struct of its own, so that the argument segment of the channel path's kernels (and with it
+// the offsets of their hidden arguments and the widths of their scalar loads) stays what it was
+struct ShadeAlbedoParams : ShadeParams {
+    const float* col;      // [scenes, pixels, cstride]: the first three floats of a pixel are its colour
+    float* gcol;           // [scenes, pixels, 3] or nullptr
+    int cstride;           // floats between consecutive pixels' colours, >= 3
+};
+template <bool ALBEDO> using ShadeArgs = std::conditional_t<ALBEDO, ShadeAlbedoParams, ShadeParams>;
 
 __device__ __forceinline__ float fold_cos(float c, bool ds) { return ds ? fabsf(c) : (c < 0.f ? 0.f : c); }
 
@@ -101,9 +122,12 @@ __device__ __forceinline__ float clamp_out(const ShadeParams& P, float pre)
 
 struct Pixel { float c[3], n[3], p[3], m; };
 
-__device__ __forceinline__ void load_pixel(const ShadeParams& P, const float* __restrict__ row, Pixel& px)
+template <bool ALBEDO>
+__device__ __forceinline__ void load_pixel(const ShadeArgs<ALBEDO>& P, long long pix, Pixel& px)
 {
-    load3(row + P.oc, px.c);
+    const float* __restrict__ row = P.g + pix * P.Cg;
+    if constexpr (ALBEDO) load3(P.col + pix * P.cstride, px.c);
+    else load3(row + P.oc, px.c);
     load3(row + P.on, px.n);
     px.p[0] = px.p[1] = px.p[2] = 0.f;
     if (P.op >= 0) load3(row + P.op, px.p);
@@ -111,14 +135,15 @@ __device__ __forceinline__ void load_pixel(const ShadeParams& P, const float* __
 }
 
 // ---- forward: one pixel per lane; the lights are a wave-uniform loop over the parameter block (scalar loads)
-__global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeParams P)
+template <bool ALBEDO = false>
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeArgs<ALBEDO> P)
 {
     const long long i = (long long)blockIdx.x * SHADE_BLOCK + threadIdx.x;
     if (i >= P.pixels) return;
     const long long pix = (long long)blockIdx.y * P.pixels + i;
     const float* __restrict__ prm = P.prm + (size_t)blockIdx.y * P.pstride;
     Pixel px;
-    load_pixel(P, P.g + pix * P.Cg, px);
+    load_pixel<ALBEDO>(P, pix, px);
     const float cam[3] = {prm[6], prm[7], prm[8]};
     float lit[3];
 #pragma unroll
@@ -137,10 +162,13 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeParams 
     store3(P.out + pix * 3, o);
 }
 
-// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (10: the row's zero)
+// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (10: the row's zero); with ALBEDO no channel is a colour
+// (oc is -1 there, which the range test below would take for channels 0 and 1)
+template <bool ALBEDO>
 __device__ __forceinline__ int shade_source(const ShadeParams& P, int ch)
 {
-    if ((unsigned)(ch - P.oc) < 3u) return ch - P.oc;
+    if constexpr (!ALBEDO)
+        if ((unsigned)(ch - P.oc) < 3u) return ch - P.oc;
     if ((unsigned)(ch - P.on) < 3u) return 3 + ch - P.on;
     if (P.op >= 0 && (unsigned)(ch - P.op) < 3u) return 6 + ch - P.op;
     if (ch == P.om) return 9;
@@ -148,9 +176,10 @@ __device__ __forceinline__ int shade_source(const ShadeParams& P, int ch)
 }
 
 // ---- backward.  NL: the number of lights (the per-lane parameter sums are registers, indexed at compile time);
-// PARAMS: whether the parameter block wants its gradient; GBUF: whether the G-buffer does.
-template <int NL, bool PARAMS, bool GBUF>
-__global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams P)
+// PARAMS: whether the parameter block wants its gradient; GBUF: whether the G-buffer does.  With ALBEDO the colours' gradient
+// leaves by one store per lane (a wave's rows are contiguous) where P.gcol is there, and the tile's dc[3] stay unused.
+template <int NL, bool PARAMS, bool GBUF, bool ALBEDO = false>
+__global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeArgs<ALBEDO> P)
 {
     constexpr int NP = SHADE_HEAD + SHADE_LIGHT * NL;
     constexpr int NA = PARAMS ? NP : 1;
@@ -167,7 +196,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams
     const int Cg = P.Cg, step_px = SHADE_BLOCK / Cg, step_ch = SHADE_BLOCK % Cg;
     const int px0 = tid / Cg, ch0 = tid % Cg;
     if constexpr (GBUF) {
-        for (int ch = tid; ch < Cg; ch += SHADE_BLOCK) s_src[ch] = (unsigned char)shade_source(P, ch);
+        for (int ch = tid; ch < Cg; ch += SHADE_BLOCK) s_src[ch] = (unsigned char)shade_source<ALBEDO>(P, ch);
         s_g[tid * SHADE_ROW + 10] = 0.f;
     }
     for (int it = 0; it < SHADE_ITER; ++it) {
@@ -177,7 +206,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams
         const long long pix = (long long)blockIdx.y * P.pixels + first + tid;
         if (tid < npx) {
             Pixel px;
-            load_pixel(P, P.g + pix * Cg, px);
+            load_pixel<ALBEDO>(P, pix, px);
             float go[3];
             load3(P.gout + pix * 3, go);
             // the forward again: every light's cosine and factor, and the value the clamp saw
@@ -271,10 +300,15 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams
                     }
                 }
             }
+            if constexpr (ALBEDO)
+                if (P.gcol) store3(P.gcol + pix * 3, gc);
             if constexpr (GBUF) {
                 float* __restrict__ r = s_g + tid * SHADE_ROW;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) { r[j] = gc[j]; r[3 + j] = gn[j]; r[6 + j] = gp[j]; }
+                for (int j = 0; j < 3; ++j) {
+                    if constexpr (!ALBEDO) r[j] = gc[j];
+                    r[3 + j] = gn[j]; r[6 + j] = gp[j];
+                }
                 r[9] = gm;
             }
         }
@@ -305,7 +339,10 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeParams
 }
 
 // ---- the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a fixed order:
-// workgroup (k, b) sums value k (block_column_sum)
+// workgroup (k, b) sums value k (block_column_sum).  One copy for both translation units: the ALBEDO one calls the launcher.
+void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
+
+#ifndef DIRT_SHADE_ALBEDO_UNIT
 __global__ __launch_bounds__(SHADE_BLOCK) void shade_reduce_kernel(const float* __restrict__ partial, float* __restrict__ grad_params,
                                                                    long long rows, int NP)
 {
@@ -315,12 +352,20 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_reduce_kernel(const float* 
     if (threadIdx.x == 0) grad_params[(size_t)blockIdx.y * NP + k] = total;
 }
 
-template <int NL>
-void shade_launch_backward(const ShadeParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
+void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s)
 {
-    if (params && gbuf) hipLaunchKernelGGL((shade_backward_kernel<NL, true, true>), grid, dim3(SHADE_BLOCK), 0, s, P);
-    else if (params) hipLaunchKernelGGL((shade_backward_kernel<NL, true, false>), grid, dim3(SHADE_BLOCK), 0, s, P);
-    else hipLaunchKernelGGL((shade_backward_kernel<NL, false, true>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    hipLaunchKernelGGL(shade_reduce_kernel, dim3((unsigned)NP, (unsigned)param_scenes), dim3(SHADE_BLOCK), 0, s, partial, grad_params, rows, NP);
+}
+#endif
+
+// (`params` and `gbuf` both false: the colours' gradient alone, an instantiation only ALBEDO has; the channel path is not called so)
+template <int NL, bool ALBEDO>
+void shade_launch_backward(const ShadeArgs<ALBEDO>& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
+{
+    if (params && gbuf) hipLaunchKernelGGL((shade_backward_kernel<NL, true, true, ALBEDO>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    else if (params) hipLaunchKernelGGL((shade_backward_kernel<NL, true, false, ALBEDO>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    else if (gbuf || !ALBEDO) hipLaunchKernelGGL((shade_backward_kernel<NL, false, true, ALBEDO>), grid, dim3(SHADE_BLOCK), 0, s, P);
+    else if constexpr (ALBEDO) hipLaunchKernelGGL((shade_backward_kernel<NL, false, false, true>), grid, dim3(SHADE_BLOCK), 0, s, P);
 }
 
 }  // namespace dirt
@@ -331,22 +376,29 @@ static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error
 
 static long long shade_blocks(long long pixels) { return (pixels + dirt::SHADE_BLOCK * dirt::SHADE_ITER - 1) / (dirt::SHADE_BLOCK * dirt::SHADE_ITER); }
 
-static int shade_check(const char* who, long long scenes, long long pixels, int Cg, int off_colors, int off_normals, int off_positions,
-                       int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned flags, float lo, float hi,
+// What the entry points of this translation unit take their colours from: channels off_colors.. of the G-buffer, or (ALBEDO) the
+// image `colors`, whose pixels are color_stride floats apart.  The checks and the launches below are written once for both;
+// what differs is written out where it does.
+static constexpr bool ALBEDO = SHADE_UNIT_ALBEDO;
+
+static int shade_check(const char* who, long long scenes, long long pixels, int Cg, int off_colors, int color_stride, int off_normals,
+                       int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned flags, float lo, float hi,
                        dirt::ShadeParams& P)
 {
     if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
     if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
     if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
     if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (ALBEDO && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
     if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) STAGE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_MAX_LIGHTS);
     if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
+    // ALBEDO: the G-buffer has no colour channels (off_colors is -1), so three channels of normals are the smallest one
     const int off[4] = {off_colors, off_normals, off_positions, off_mask}, width[4] = {3, 3, 3, 1};
     const char* const names[4] = {"colors", "normals", "positions", "mask"};
-    for (int a = 0; a < 4; ++a) {
+    for (int a = ALBEDO ? 1 : 0; a < 4; ++a) {
         if (off[a] == -1 && a >= 2) continue;
         if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
-        for (int b = 0; b < a; ++b)
+        for (int b = ALBEDO ? 1 : 0; b < a; ++b)
             if (off[b] >= 0 && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
                 STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
     }
@@ -358,11 +410,87 @@ static int shade_check(const char* who, long long scenes, long long pixels, int 
             STAGE_FAIL("%s: light %d is specular and needs a camera position (DIRT_SHADE_HAS_CAMERA)", who, l);
     }
     if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
-    P.pixels = pixels; P.Cg = Cg; P.oc = off_colors; P.on = off_normals; P.op = off_positions; P.om = off_mask; P.nl = lights;
+    P.pixels = pixels; P.Cg = Cg; P.oc = ALBEDO ? -1 : off_colors; P.on = off_normals; P.op = off_positions; P.om = off_mask; P.nl = lights;
     P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
     P.kinds = light_kinds; P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0; P.lo = lo; P.hi = hi;
     return DIRT_OK;
 }
+
+static void shade_set_colors(dirt::ShadeParams&, const float*, int, float*) {}   // the channel path has nothing to set
+static void shade_set_colors(dirt::ShadeAlbedoParams& P, const float* colors, int color_stride, float* grad_colors)
+{
+    P.col = colors; P.cstride = color_stride; P.gcol = grad_colors;
+}
+
+// `colors`, `color_stride`: ALBEDO only (the channel path passes nullptr, 0); `off_colors`: the channel path only (ALBEDO passes -1)
+static int shade_forward(const char* who, const float* gbuffer, const float* colors, const float* params, float* out, long long scenes,
+                         long long pixels, int Cg, int off_colors, int color_stride, int off_normals, int off_positions, int off_mask,
+                         int param_scenes, int lights, unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi,
+                         unsigned flags, void* stream)
+{
+    dirt::ShadeArgs<ALBEDO> P{};
+    int rc = shade_check(who, scenes, pixels, Cg, off_colors, color_stride, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds,
+                         flags, clamp_lo, clamp_hi, P);
+    if (rc) return rc;
+    if (scenes * pixels == 0) return dirt::stage_ok(report);
+    if (!gbuffer || !params || !out) STAGE_FAIL("%s: gbuffer / params / out is NULL", who);
+    if (ALBEDO && !colors) STAGE_FAIL("%s: colors is NULL", who);
+    if (pixels > 0x7fffffffll * dirt::SHADE_BLOCK) STAGE_FAIL("%s: too many pixels per scene", who);
+    P.g = gbuffer; P.prm = params; P.out = out; P.dsided = double_sided;
+    shade_set_colors(P, colors, color_stride, nullptr);
+    const dim3 grid((unsigned)((pixels + dirt::SHADE_BLOCK - 1) / dirt::SHADE_BLOCK), (unsigned)scenes);
+    hipLaunchKernelGGL(dirt::shade_forward_kernel<ALBEDO>, grid, dim3(dirt::SHADE_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
+    return dirt::stage_hip(report, who, hipGetLastError());
+}
+
+// `grad_colors`: ALBEDO only (the channel path passes nullptr: its colours' gradient is part of grad_gbuffer)
+static int shade_backward(const char* who, const float* gbuffer, const float* colors, const float* params, const float* grad_out,
+                          float* grad_gbuffer, float* grad_colors, float* grad_params, void* scratch, size_t scratch_bytes, long long scenes,
+                          long long pixels, int Cg, int off_colors, int color_stride, int off_normals, int off_positions, int off_mask,
+                          int param_scenes, int lights, unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi,
+                          unsigned flags, void* stream)
+{
+    dirt::ShadeArgs<ALBEDO> P{};
+    int rc = shade_check(who, scenes, pixels, Cg, off_colors, color_stride, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds,
+                         flags, clamp_lo, clamp_hi, P);
+    if (rc) return rc;
+    if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params && !grad_colors)) return dirt::stage_ok(report);
+    if (!gbuffer || !params || !grad_out) STAGE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
+    if (ALBEDO && !colors) STAGE_FAIL("%s: colors is NULL", who);
+    if (grad_params) {
+        rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_shade_scratch_bytes(scenes, pixels, lights), "dirt_shade_scratch_bytes");
+        if (rc) return rc;
+    }
+    const long long blocks = shade_blocks(pixels);
+    if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
+    P.g = gbuffer; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.partial = static_cast<float*>(scratch); P.dsided = double_sided;
+    shade_set_colors(P, colors, color_stride, grad_colors);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)blocks, (unsigned)scenes);
+    const bool params_wanted = grad_params != nullptr, gbuf = grad_gbuffer != nullptr;
+    switch (lights) {
+    case 0: dirt::shade_launch_backward<0, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 1: dirt::shade_launch_backward<1, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 2: dirt::shade_launch_backward<2, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 3: dirt::shade_launch_backward<3, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 4: dirt::shade_launch_backward<4, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 5: dirt::shade_launch_backward<5, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 6: dirt::shade_launch_backward<6, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    case 7: dirt::shade_launch_backward<7, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    default: dirt::shade_launch_backward<8, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
+    if (params_wanted) {
+        const int NP = DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
+        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
+        dirt::shade_launch_reduce(static_cast<const float*>(scratch), grad_params, rows, NP, param_scenes, s);
+        e = hipGetLastError();
+    }
+    return dirt::stage_hip(report, who, e);
+}
+
+#ifndef DIRT_SHADE_ALBEDO_UNIT
 
 size_t dirt_shade_scratch_bytes(long long scenes, long long pixels, int lights)
 {
@@ -374,18 +502,8 @@ int dirt_shade_forward(const float* gbuffer, const float* params, float* out, lo
                        int off_normals, int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds,
                        unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
 {
-    const char* who = "dirt_shade_forward";
-    dirt::ShadeParams P{};
-    int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
-                         clamp_lo, clamp_hi, P);
-    if (rc) return rc;
-    if (scenes * pixels == 0) return dirt::stage_ok(report);
-    if (!gbuffer || !params || !out) STAGE_FAIL("%s: gbuffer / params / out is NULL", who);
-    if (pixels > 0x7fffffffll * dirt::SHADE_BLOCK) STAGE_FAIL("%s: too many pixels per scene", who);
-    P.g = gbuffer; P.prm = params; P.out = out; P.dsided = double_sided;
-    const dim3 grid((unsigned)((pixels + dirt::SHADE_BLOCK - 1) / dirt::SHADE_BLOCK), (unsigned)scenes);
-    hipLaunchKernelGGL(dirt::shade_forward_kernel, grid, dim3(dirt::SHADE_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
-    return dirt::stage_hip(report, who, hipGetLastError());
+    return shade_forward("dirt_shade_forward", gbuffer, nullptr, params, out, scenes, pixels, Cg, off_colors, 0, off_normals, off_positions, off_mask,
+                         param_scenes, lights, light_kinds, double_sided, clamp_lo, clamp_hi, flags, stream);
 }
 
 int dirt_shade_backward(const float* gbuffer, const float* params, const float* grad_out, float* grad_gbuffer, float* grad_params,
@@ -393,44 +511,31 @@ int dirt_shade_backward(const float* gbuffer, const float* params, const float* 
                         int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned double_sided,
                         float clamp_lo, float clamp_hi, unsigned flags, void* stream)
 {
-    const char* who = "dirt_shade_backward";
-    dirt::ShadeParams P{};
-    int rc = shade_check(who, scenes, pixels, Cg, off_colors, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, flags,
-                         clamp_lo, clamp_hi, P);
-    if (rc) return rc;
-    if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params)) return dirt::stage_ok(report);
-    if (!gbuffer || !params || !grad_out) STAGE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
-    if (grad_params) {
-        rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_shade_scratch_bytes(scenes, pixels, lights), "dirt_shade_scratch_bytes");
-        if (rc) return rc;
-    }
-    const long long blocks = shade_blocks(pixels);
-    if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
-    P.g = gbuffer; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.partial = static_cast<float*>(scratch); P.dsided = double_sided;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks, (unsigned)scenes);
-    const bool params_wanted = grad_params != nullptr, gbuf = grad_gbuffer != nullptr;
-    switch (lights) {
-    case 0: dirt::shade_launch_backward<0>(P, params_wanted, gbuf, grid, s); break;
-    case 1: dirt::shade_launch_backward<1>(P, params_wanted, gbuf, grid, s); break;
-    case 2: dirt::shade_launch_backward<2>(P, params_wanted, gbuf, grid, s); break;
-    case 3: dirt::shade_launch_backward<3>(P, params_wanted, gbuf, grid, s); break;
-    case 4: dirt::shade_launch_backward<4>(P, params_wanted, gbuf, grid, s); break;
-    case 5: dirt::shade_launch_backward<5>(P, params_wanted, gbuf, grid, s); break;
-    case 6: dirt::shade_launch_backward<6>(P, params_wanted, gbuf, grid, s); break;
-    case 7: dirt::shade_launch_backward<7>(P, params_wanted, gbuf, grid, s); break;
-    default: dirt::shade_launch_backward<8>(P, params_wanted, gbuf, grid, s); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
-    if (params_wanted) {
-        const int NP = DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
-        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
-        hipLaunchKernelGGL(dirt::shade_reduce_kernel, dim3((unsigned)NP, (unsigned)param_scenes), dim3(dirt::SHADE_BLOCK), 0, s,
-                           static_cast<const float*>(scratch), grad_params, rows, NP);
-        e = hipGetLastError();
-    }
-    return dirt::stage_hip(report, who, e);
+    return shade_backward("dirt_shade_backward", gbuffer, nullptr, params, grad_out, grad_gbuffer, nullptr, grad_params, scratch, scratch_bytes,
+                          scenes, pixels, Cg, off_colors, 0, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, double_sided,
+                          clamp_lo, clamp_hi, flags, stream);
 }
+
+#else
+
+int dirt_shade_albedo_forward(const float* gbuffer, const float* colors, const float* params, float* out, long long scenes, long long pixels,
+                              int Cg, int color_stride, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                              unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
+{
+    return shade_forward("dirt_shade_albedo_forward", gbuffer, colors, params, out, scenes, pixels, Cg, -1, color_stride, off_normals, off_positions,
+                         off_mask, param_scenes, lights, light_kinds, double_sided, clamp_lo, clamp_hi, flags, stream);
+}
+
+int dirt_shade_albedo_backward(const float* gbuffer, const float* colors, const float* params, const float* grad_out, float* grad_gbuffer,
+                               float* grad_colors, float* grad_params, void* scratch, size_t scratch_bytes, long long scenes, long long pixels,
+                               int Cg, int color_stride, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                               unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
+{
+    return shade_backward("dirt_shade_albedo_backward", gbuffer, colors, params, grad_out, grad_gbuffer, grad_colors, grad_params, scratch,
+                          scratch_bytes, scenes, pixels, Cg, -1, color_stride, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds,
+                          double_sided, clamp_lo, clamp_hi, flags, stream);
+}
+
+#endif
 
 }  // extern "C"

@@ -7,6 +7,9 @@ as one HIP kernel forward and one backward (dirt_shade.hip; specification in DES
     def shader_fn(gbuffer, view_matrix, light_direction):
         return shade_gbuffer(gbuffer, [diffuse_directional_light(light_direction, (1., 0., 0.), double_sided=False)],
                              colors=4, normals=7, positions=1, mask=0, ambient=(.2, .2, .2), background=(0., 0., .3))
+
+`colors` may also be a tensor [..., 3] beside the G-buffer -- the output of `texture.sample_texture_uv`, of a network -- which
+the same kernels read in place of the three channels and whose gradient they write (examples/textured_fused.py).
 """
 import numbers
 
@@ -76,35 +79,49 @@ def _value(x, width, name, device, batch):
 
 class _ShadeGBuffer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, gbuffer, block, meta):
+    def forward(ctx, gbuffer, block, colors, meta):
+        """colors: None (three channels of the G-buffer, offsets[0]) or float32 [..., 3] beside it, read in place where its
+        pixels lie a constant stride apart (`_stage.rows_in_place`)"""
         lib = _lib.load()
         scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = meta
         out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
         block = block.contiguous()
-        if scenes * pixels:
+        tail = (int(block.shape[0]), nl, kinds, sided, lo, hi, flags)
+        src, stride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+        if scenes * pixels and src is None:
             _stage.call(lib.dirt_shade_forward, gbuffer.device, gbuffer.data_ptr(), block.data_ptr(), out.data_ptr(), scenes, pixels, cg,
-                        *offsets, int(block.shape[0]), nl, kinds, sided, lo, hi, flags)
-        ctx.save_for_backward(gbuffer, block)
-        ctx.meta = meta
+                        *offsets, *tail)
+        elif scenes * pixels:
+            _stage.call(lib.dirt_shade_albedo_forward, gbuffer.device, gbuffer.data_ptr(), src.data_ptr(), block.data_ptr(), out.data_ptr(),
+                        scenes, pixels, cg, stride, *offsets[1:], *tail)
+        ctx.save_for_backward(gbuffer, block, src)
+        ctx.meta, ctx.color_stride = meta, stride
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         lib = _lib.load()
-        gbuffer, block = ctx.saved_tensors
+        gbuffer, block, src = ctx.saved_tensors
         scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = ctx.meta
         dev = gbuffer.device
         want_p = ctx.needs_input_grad[1]
+        want_c = src is not None and ctx.needs_input_grad[2]
         grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
+        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None   # dense [..., 3], whatever the colours' strides
         if not scenes * pixels:
-            return grad_g, grad_p, None
+            return grad_g, grad_p, grad_c.zero_() if want_c else None, None
         grad_out = grad_out.to(torch.float32).contiguous()
         nbytes = lib.dirt_shade_scratch_bytes(scenes, pixels, nl) if want_p else 0
-        _stage.call(lib.dirt_shade_backward, dev, gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_p),
-                    _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg, *offsets, int(block.shape[0]), nl, kinds, sided, lo, hi,
-                    flags)
-        return grad_g, grad_p, None
+        tail = (_ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg)
+        if src is None:
+            _stage.call(lib.dirt_shade_backward, dev, gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_p),
+                        *tail, *offsets, int(block.shape[0]), nl, kinds, sided, lo, hi, flags)
+        else:
+            _stage.call(lib.dirt_shade_albedo_backward, dev, gbuffer.data_ptr(), src.data_ptr(), block.data_ptr(), grad_out.data_ptr(),
+                        _ptr(grad_g), _ptr(grad_c), _ptr(grad_p), *tail, ctx.color_stride, *offsets[1:], int(block.shape[0]), nl, kinds, sided,
+                        lo, hi, flags)
+        return grad_g, grad_p, grad_c, None
 
 
 def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None, ambient=(0., 0., 0.), camera_position=None,
@@ -114,6 +131,10 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
     gbuffer: float32 [H, W, Cg], [B, H, W, Cg] or a flat [N, Cg] on the GPU; a contiguous one is read in place.
     colors, normals, positions, mask: the first channel of each attribute inside a pixel (3, 3, 3 and 1 channels; any
         order, no overlap).  `positions` is needed only if a light needs it; mask=None: every pixel is covered.
+    colors may instead be a floating-point tensor shaped like the G-buffer with 3 channels ([H, W, 3], [B, H, W, 3], [N, 3])
+        on its device: the colours come from it, it is differentiable, and the G-buffer needs no colour channels (normals,
+        positions and mask may sit anywhere).  One whose pixels lie a constant stride >= 3 floats apart -- a contiguous
+        tensor, the first or last three channels of an RGBA image, `gbuffer[..., 4:7]` -- is read in place.
     lights: up to 8 records ('diffuse_directional', direction, color, double_sided),
         ('specular_directional', direction, color, shininess, double_sided) (needs `camera_position`) or
         ('diffuse_point', position, color, double_sided) -- the three models of `dirt_amd.lighting`, with their conventions
@@ -151,12 +172,13 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
     scenes = batch if batch is not None else 1
     pixels = g.numel() // (cg * scenes) if scenes else 0
     meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
-    return _ShadeGBuffer.apply(g, block, meta)
+    return _ShadeGBuffer.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
 
 
 def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient, camera_position, background, clamp):
     """Everything `shade_gbuffer` refuses with a ValueError, on the tensor's shape and device alone (no device work): ->
-    (channel offsets, light kinds, sidedness, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])])."""
+    (channel offsets, light kinds, sidedness, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])]).
+    `colors` as a tensor: the offsets' first entry is -1."""
     if not gbuffer.dtype.is_floating_point:
         raise ValueError('shade_gbuffer expects a float32 gbuffer, got %s' % gbuffer.dtype)
     dev = gbuffer.device
@@ -166,6 +188,17 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
     for name, off, width, required in (('colors', colors, 3, True), ('normals', normals, 3, True), ('positions', positions, 3, False),
                                        ('mask', mask, 1, False)):
         if off is None and not required:
+            offsets.append(-1)
+            continue
+        if name == 'colors' and isinstance(off, torch.Tensor):
+            want = tuple(gbuffer.shape[:-1]) + (3,)
+            if not off.dtype.is_floating_point:
+                raise ValueError('colors as a tensor must be floating-point, got %s' % off.dtype)
+            if tuple(off.shape) != want:
+                raise ValueError('colors as a tensor must have shape %s (the G-buffer\'s %s with 3 channels), got %s'
+                                 % (list(want), list(gbuffer.shape), list(off.shape)))
+            if off.device != dev:
+                raise ValueError('colors is on %s, the G-buffer on %s' % (off.device, dev))
             offsets.append(-1)
             continue
         if isinstance(off, bool) or not isinstance(off, int):

@@ -105,18 +105,7 @@ def _pixel_grid(uv_shape, footprint=False):
 def _pairs_in_place(uvs):
     """(tensor to pass, element stride between pairs) such that pair i starts at data_ptr + 4 * i * stride: a slice
     `gbuffer[..., a:a+2]` of a contiguous G-buffer is read in place, anything else is made contiguous."""
-    if uvs.stride(-1) == 1 and uvs.dim() >= 2:
-        step = uvs.stride(-2)
-        ok = step >= 2
-        expect = step
-        for d in range(uvs.dim() - 2, -1, -1):
-            if uvs.stride(d) != expect:
-                ok = False
-                break
-            expect *= uvs.shape[d]
-        if ok:
-            return uvs, step
-    return uvs.contiguous(), 2
+    return _stage.rows_in_place(uvs, 2)
 
 
 _BATCHED = {'sample_forward': 'sample_batch_forward', 'sample_backward_image': 'sample_batch_backward_image', 'mip_build': 'mip_build_batch',

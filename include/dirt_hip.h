@@ -351,6 +351,26 @@ int dirt_shade_backward(const float *gbuffer, const float *params, const float *
                         int off_colors, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
                         unsigned light_kinds, unsigned double_sided, float clamp_lo, float clamp_hi, unsigned flags,
                         void *stream);
+/*
+ * The same lighting with the colours in an image of their own, so that any colour source composes with it (a texture
+ * look-up's output, a network's): colors [scenes, pixels, color_stride], the first three floats of a pixel its colour,
+ * color_stride >= 3 (3: dense; 4: the first or the last three channels of an RGBA image; Cg: three channels of the
+ * G-buffer itself), read in place, 4-byte alignment suffices.  The G-buffer then has no colour channels: there is no
+ * off_colors, Cg may be as small as 3, and normals / positions / mask may sit anywhere, channel 0 included.  Everything
+ * else is as above -- the same kernels with the colour's load and the store of its gradient redirected.
+ * Backward: grad_colors [scenes, pixels, 3], dense; grad_gbuffer (fully written: no channel is a colour's), grad_colors
+ * and grad_params may each be NULL and are then not computed -- all three NULL: success, nothing is launched.  Only
+ * grad_params needs `scratch` (dirt_shade_scratch_bytes, as above).  NULL colors and color_stride < 3 are refused.
+ */
+int dirt_shade_albedo_forward(const float *gbuffer, const float *colors, const float *params, float *out, long long scenes,
+                              long long pixels, int Cg, int color_stride, int off_normals, int off_positions, int off_mask,
+                              int param_scenes, int lights, unsigned light_kinds, unsigned double_sided, float clamp_lo,
+                              float clamp_hi, unsigned flags, void *stream);
+int dirt_shade_albedo_backward(const float *gbuffer, const float *colors, const float *params, const float *grad_out,
+                               float *grad_gbuffer, float *grad_colors, float *grad_params, void *scratch, size_t scratch_bytes,
+                               long long scenes, long long pixels, int Cg, int color_stride, int off_normals, int off_positions,
+                               int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned double_sided,
+                               float clamp_lo, float clamp_hi, unsigned flags, void *stream);
 
 /*
  * The vertex stage in front of the rasteriser, fused.  Replaces the torch composition of the reference's samples
