@@ -108,3 +108,47 @@ def diffuse_point(vertex_positions, vertex_normals, vertex_colors, light_positio
     incident = relative / (torch.linalg.vector_norm(relative, dim=-1, keepdim=True) + 1.e-12)
     cosines = _clamp_cosines(torch.sum(vertex_normals * incident, dim=-1), double_sided)
     return light_color[..., None, :] * vertex_colors * cosines[..., None]
+
+
+# ---- second-order spherical-harmonic irradiance.  Not in the reference: the light model of differentiable face and body
+# fitting, 9 coefficients per colour channel.  This is the specification `shading.shade_gbuffer_sh` implements per pixel
+# (DESIGN.md §7b).
+
+SH_C0, SH_C1, SH_C2 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792
+SH_C3, SH_C4 = 0.31539156525252005, 0.5462742152960396
+SH_BAND = (0, 1, 1, 1, 2, 2, 2, 2, 2)   # the band l of basis function k
+SH_LAMBERT = (3.141592653589793, 2.0943951023931953, 0.7853981633974483)   # band_scale: radiance coefficients -> Lambertian irradiance
+
+
+def sh_basis(normals):
+    """The nine real spherical harmonics of bands 0-2 at `normals` [..., 3] (taken as given, not normalised) -> [..., 9],
+    in the order (l, m) = (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2); orthonormal over the unit sphere."""
+    normals = _as(normals, torch.zeros((), dtype=torch.float32))
+    x, y, z = normals[..., 0], normals[..., 1], normals[..., 2]
+    return torch.stack([SH_C0 * torch.ones_like(x), SH_C1 * y, SH_C1 * z, SH_C1 * x,
+                        SH_C2 * (x * y), SH_C2 * (y * z), SH_C3 * (3. * (z * z) - 1.), SH_C2 * (x * z), SH_C4 * (x * x - y * y)], dim=-1)
+
+
+def spherical_harmonics(vertex_normals, vertex_colors, coefficients, band_scale=(1., 1., 1.), normalize=False):
+    """Reflectance under spherical-harmonic lighting: colour_j * sum_k band_scale[band(k)] * coefficients[k, j] * Y_k(normal).
+    [*, V, 3], [*, V, 3], coefficients [K, 3] -- or [B, K, 3] against normals whose first axis is B -- with K in (1, 4, 9)
+    (whole bands; the missing ones are zero) -> [*, V, 3].  band_scale: three numbers, one per band (SH_LAMBERT turns
+    radiance coefficients into irradiance).  normalize: the normals go through torch.nn.functional.normalize
+    (n / max(|n|, 1e-12)) first; otherwise they are taken as given, as everywhere in this module."""
+    vertex_normals = _as(vertex_normals, torch.zeros((), dtype=torch.float32))
+    vertex_colors = _as(vertex_colors, vertex_normals)
+    coefficients = _as(coefficients, vertex_normals)
+    if coefficients.dim() not in (2, 3) or coefficients.shape[-1] != 3 or coefficients.shape[-2] not in (1, 4, 9):
+        raise ValueError('coefficients must have shape [K, 3] or [B, K, 3] with K in (1, 4, 9), got %s' % list(coefficients.shape))
+    scale = [float(s) for s in band_scale]
+    if len(scale) != 3:
+        raise ValueError('band_scale must be 3 numbers, got %d' % len(scale))
+    if normalize:
+        vertex_normals = torch.nn.functional.normalize(vertex_normals, dim=-1, eps=1.e-12)
+    K = coefficients.shape[-2]
+    weights = torch.tensor([scale[b] for b in SH_BAND[:K]], dtype=vertex_normals.dtype, device=vertex_normals.device)
+    basis = sh_basis(vertex_normals)[..., :K] * weights   # [*, V, K]
+    if coefficients.dim() == 3:   # one table per leading batch entry: [B, 1.., K, 3]
+        coefficients = coefficients.reshape((coefficients.shape[0],) + (1,) * (basis.dim() - 2) + (K, 3))
+    irradiance = (basis[..., None] * coefficients).sum(-2)
+    return vertex_colors * irradiance

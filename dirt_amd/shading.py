@@ -154,8 +154,20 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
     lights = list(lights)
     offsets, kinds, sided, lo, hi, flags, const, tensors = _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
                                                                             camera_position, background, clamp)
-    dev, cg, batch, width = gbuffer.device, int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None, len(const)
-    block = _const_block(dev, tuple(const))
+    dev, cg, batch = gbuffer.device, int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    block = _splice_block(dev, const, tensors)
+
+    g = gbuffer.to(torch.float32).contiguous()
+    scenes = batch if batch is not None else 1
+    pixels = g.numel() // (cg * scenes) if scenes else 0
+    meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
+    return _ShadeGBuffer.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
+
+
+def _splice_block(dev, const, tensors):
+    """The parameter block [1 or B, len(const)]: the cached constant row with the tensors spliced in by one torch.cat, whose
+    autograd hands the block's gradient back to them (and drops the constant part's)."""
+    block, width = _const_block(dev, tuple(const)), len(const)
     if tensors:
         rows = max(int(t.shape[0]) for _, t in tensors)
         pieces, cursor = [], 0
@@ -167,12 +179,7 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
         if cursor < width:
             pieces.append(block[:, cursor:].expand(rows, -1))
         block = torch.cat(pieces, dim=1)
-
-    g = gbuffer.to(torch.float32).contiguous()
-    scenes = batch if batch is not None else 1
-    pixels = g.numel() // (cg * scenes) if scenes else 0
-    meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
-    return _ShadeGBuffer.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
+    return block
 
 
 def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient, camera_position, background, clamp):
@@ -182,11 +189,24 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
     if not gbuffer.dtype.is_floating_point:
         raise ValueError('shade_gbuffer expects a float32 gbuffer, got %s' % gbuffer.dtype)
     dev = gbuffer.device
-    cg = int(gbuffer.shape[-1])
     batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('normals', normals, 3, True), ('positions', positions, 3, False),
+                                         ('mask', mask, 1, False)))
+    if len(lights) > _lib.SHADE_MAX_LIGHTS:
+        raise ValueError('shade_gbuffer takes at most %d lights, got %d' % (_lib.SHADE_MAX_LIGHTS, len(lights)))
+    lo, hi = _clamp_bounds(clamp)
+    flags = (_lib.SHADE_CLAMP if clamp is not None else 0) | (_lib.SHADE_HAS_CAMERA if camera_position is not None else 0)
+    kinds, sided, const, tensors = _light_block(lights, positions, ambient, camera_position, background, dev, batch)
+    return offsets, kinds, sided, lo, hi, flags, const, tensors
+
+
+def _channel_offsets(gbuffer, attributes):
+    """The first channel of each of `attributes` (name, channel index or None or -- colors only -- a tensor, width, required)
+    inside a pixel of `gbuffer`, -1 for an absent one and for colours that are a tensor; refuses what does not fit or overlaps."""
+    dev = gbuffer.device
+    cg = int(gbuffer.shape[-1])
     offsets, offsets_named = [], []
-    for name, off, width, required in (('colors', colors, 3, True), ('normals', normals, 3, True), ('positions', positions, 3, False),
-                                       ('mask', mask, 1, False)):
+    for name, off, width, required in attributes:
         if off is None and not required:
             offsets.append(-1)
             continue
@@ -210,19 +230,24 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
                 raise ValueError('%s (channel %d) overlaps %s (channel %d)' % (name, off, other, o))
         offsets_named.append((name, off, width))
         offsets.append(off)
-    if len(lights) > _lib.SHADE_MAX_LIGHTS:
-        raise ValueError('shade_gbuffer takes at most %d lights, got %d' % (_lib.SHADE_MAX_LIGHTS, len(lights)))
-    if clamp is not None:
-        try:
-            lo, hi = (float(v) for v in clamp)
-        except (TypeError, ValueError):
-            raise ValueError('clamp must be (lo, hi) or None, got %r' % (clamp,))
-        if not lo <= hi:
-            raise ValueError('clamp needs lo <= hi, got %r' % (clamp,))
-    else:
-        lo, hi = 0., 0.
-    flags = (_lib.SHADE_CLAMP if clamp is not None else 0) | (_lib.SHADE_HAS_CAMERA if camera_position is not None else 0)
+    return offsets
 
+
+def _clamp_bounds(clamp):
+    """(lo, hi) of `clamp`, (0, 0) for None"""
+    if clamp is None:
+        return 0., 0.
+    try:
+        lo, hi = (float(v) for v in clamp)
+    except (TypeError, ValueError):
+        raise ValueError('clamp must be (lo, hi) or None, got %r' % (clamp,))
+    if not lo <= hi:
+        raise ValueError('clamp needs lo <= hi, got %r' % (clamp,))
+    return lo, hi
+
+
+def _light_block(lights, positions, ambient, camera_position, background, dev, batch):
+    """The parameter block of `shade_gbuffer` -> (light kinds, sidedness, its constant row, [(first slot, tensor [1 or B, width])])."""
     # the parameter block: [1 or B, 9 + 8 lights]; python numbers go into a cached constant row, tensors are spliced in with
     # one torch.cat whose autograd hands the block's gradient back to them
     slots = [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
@@ -253,4 +278,111 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
             const[start:start + len(v)] = v
         else:
             tensors.append((start, v))
-    return offsets, kinds, sided, lo, hi, flags, const, tensors
+    return kinds, sided, const, tensors
+
+
+# ---- spherical-harmonic lighting (dirt_shade_sh.hip)
+
+_SH_TERMS = 9
+
+
+class _ShadeGBufferSH(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, block, colors, meta):
+        """colors: None (three channels of the G-buffer) or float32 [..., 3] beside it, read in place under `_stage.rows_in_place`"""
+        lib = _lib.load()
+        scenes, pixels, cg, offsets, scale, lo, hi, flags = meta
+        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
+        block = block.contiguous()
+        src, stride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+        if scenes * pixels:
+            _stage.call(lib.dirt_shade_sh_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(src), block.data_ptr(), out.data_ptr(), scenes, pixels,
+                        cg, stride, *offsets, int(block.shape[0]), *scale, lo, hi, flags)
+        ctx.save_for_backward(gbuffer, block, src)
+        ctx.meta, ctx.color_stride = meta, stride
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, block, src = ctx.saved_tensors
+        scenes, pixels, cg, offsets, scale, lo, hi, flags = ctx.meta
+        dev = gbuffer.device
+        want_p = ctx.needs_input_grad[1]
+        want_c = src is not None and ctx.needs_input_grad[2]
+        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
+        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None   # dense [..., 3], whatever the colours' strides
+        if not scenes * pixels:
+            return grad_g, grad_p, grad_c.zero_() if want_c else None, None
+        grad_out = grad_out.to(torch.float32).contiguous()
+        nbytes = lib.dirt_shade_sh_scratch_bytes(scenes, pixels) if want_p else 0
+        _stage.call(lib.dirt_shade_sh_backward, dev, gbuffer.data_ptr(), _ptr(src), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g),
+                    _ptr(grad_c), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg, ctx.color_stride, *offsets,
+                    int(block.shape[0]), *scale, lo, hi, flags)
+        return grad_g, grad_p, grad_c, None
+
+
+def shade_gbuffer_sh(gbuffer, coefficients, *, colors, normals, mask=None, background=(0., 0., 0.), clamp=(0., 1.), normalize=False,
+                     band_scale=(1., 1., 1.)):
+    """Lights a G-buffer per pixel with second-order spherical harmonics in one kernel, differentiably: what
+    `lighting.spherical_harmonics` computes per vertex, composited and clamped as `shade_gbuffer` does.
+
+    gbuffer, colors (channel index or tensor [..., 3]), normals, mask, background, clamp: as in `shade_gbuffer`.
+    coefficients: a floating-point tensor [K, 3], or [B, K, 3] with a [B, H, W, Cg] G-buffer (one table per scene), K in
+        (1, 4, 9): bands 0, 0-1 or 0-2 in the order of `lighting.sh_basis`, one column per colour channel.  On the G-buffer's
+        device, differentiable.
+    normalize: the normals go through torch.nn.functional.normalize (n / max(|n|, 1e-12)) first, with its gradient;
+        otherwise they are taken as given.
+    band_scale: three python numbers multiplying bands 0, 1, 2 (`lighting.SH_LAMBERT`: radiance -> irradiance); not differentiable.
+
+    Returns [..., 3]:  clamp(c * E * m + background * (1 - m), lo, hi)  with  E_j = sum_k band_scale[band(k)] L[k, j] Y_k(n).
+    Gradients are those of torch's autograd for that composition (the clamp passes the gradient at its edges)."""
+    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
+        raise ValueError('shade_gbuffer_sh expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_sh')
+    offsets, scale, lo, hi, flags, const, tensors = _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background, clamp,
+                                                                        normalize, band_scale)
+    block = _splice_block(gbuffer.device, const, tensors)
+    g = gbuffer.to(torch.float32).contiguous()
+    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
+    pixels = g.numel() // (cg * scenes) if scenes else 0
+    meta = (scenes, pixels, cg, tuple(offsets), scale, lo, hi, flags)
+    return _ShadeGBufferSH.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
+
+
+def _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background, clamp, normalize, band_scale):
+    """Everything `shade_gbuffer_sh` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel
+    offsets (colors, normals, mask), band scales, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])])."""
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('shade_gbuffer_sh expects a float32 gbuffer, got %s' % gbuffer.dtype)
+    dev = gbuffer.device
+    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('normals', normals, 3, True), ('mask', mask, 1, False)))
+    if not isinstance(coefficients, torch.Tensor) or not coefficients.dtype.is_floating_point:
+        raise ValueError('coefficients must be a floating-point tensor, got %s' % (getattr(coefficients, 'dtype', type(coefficients).__name__),))
+    shape = tuple(coefficients.shape)
+    if len(shape) not in (2, 3) or shape[-1] != 3 or shape[-2] not in (1, 4, 9):
+        raise ValueError('coefficients must have shape [K, 3] or [B, K, 3] with K in (1, 4, 9), got %s' % list(shape))
+    if len(shape) == 3 and shape[0] != batch:
+        raise ValueError('coefficients [B, K, 3] need a [B, H, W, Cg] G-buffer with the same B, got %s against a G-buffer %s'
+                         % (list(shape), list(gbuffer.shape)))
+    if coefficients.device != dev:
+        raise ValueError('coefficients is on %s, the G-buffer on %s' % (coefficients.device, dev))
+    try:
+        scale = tuple(float(v) for v in band_scale)
+    except (TypeError, ValueError):
+        raise ValueError('band_scale must be 3 numbers, got %r' % (band_scale,))
+    if len(scale) != 3:
+        raise ValueError('band_scale must be 3 numbers, got %d' % len(scale))
+    lo, hi = _clamp_bounds(clamp)
+    flags = (_lib.SHADE_CLAMP if clamp is not None else 0) | (_lib.SHADE_SH_NORMALIZE if normalize else 0)
+    # the parameter block: [1 or B, 30]; bands the table does not have stay zeros of the constant row
+    const = [0.] * _lib.SHADE_SH_PARAMS
+    tensors = [(0, coefficients.to(torch.float32).reshape(-1, 3 * shape[-2]))]
+    bg = _value(background, 3, 'background', dev, batch)
+    if isinstance(bg, list):
+        const[3 * _SH_TERMS:] = bg
+    else:
+        tensors.append((3 * _SH_TERMS, bg))
+    return offsets, scale, lo, hi, flags, const, tensors

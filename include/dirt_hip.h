@@ -371,6 +371,36 @@ int dirt_shade_albedo_backward(const float *gbuffer, const float *colors, const 
                                long long scenes, long long pixels, int Cg, int color_stride, int off_normals, int off_positions,
                                int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned double_sided,
                                float clamp_lo, float clamp_hi, unsigned flags, void *stream);
+/*
+ * Second-order spherical-harmonic lighting of a G-buffer, fused (the reference has no such model; the specification is
+ * DESIGN.md §7b and dirt_amd/lighting.py::spherical_harmonics).  Per pixel, with colour c, normal n, mask m:
+ *     nh = n, or n / max(|n|, 1e-12) with DIRT_SHADE_SH_NORMALIZE;   E_j = sum_k scale_band(k) L[k, j] Y_k(nh)
+ *     out_j = clamp(c_j E_j m + background_j (1 - m), clamp_lo, clamp_hi)
+ * with the nine real basis functions in the order (l, m) = (0,0), (1,-1), (1,0), (1,1), (2,-2) .. (2,2); scale0 / scale1 /
+ * scale2 multiply bands 0 / 1 / 2 ((pi, 2 pi / 3, pi / 4): radiance coefficients to Lambertian irradiance).
+ *   gbuffer [scenes, pixels, Cg], read in place.  colors NULL: the colour is the three channels at off_colors; otherwise
+ *   colors [scenes, pixels, color_stride >= 3] as dirt_shade_albedo_forward takes it, and off_colors is not read.
+ *   off_normals: three channels; off_mask: one, or -1 (every pixel covered).  Attributes may not overlap.
+ *   params [param_scenes, DIRT_SHADE_SH_PARAMS], param_scenes = 1 or scenes: L[k, j] at 3 k + j, then background[3].
+ *   flags: DIRT_SHADE_CLAMP, DIRT_SHADE_SH_NORMALIZE; any other bit is refused.   out [scenes, pixels, 3].
+ * Backward: grad_gbuffer [scenes, pixels, Cg], fully written; grad_colors [scenes, pixels, 3], dense, only with colors;
+ * grad_params like params.  Each may be NULL and is then not computed -- all three NULL: success, nothing is launched.
+ * grad_params needs `scratch` of dirt_shade_sh_scratch_bytes(scenes, pixels) bytes (0: invalid sizes): one row of partial
+ * sums per workgroup, added by a second launch in a fixed order -- no atomics, the same bits on every run.  Zero scenes
+ * or pixels: success, nothing is launched or written.  Failures: dirt_last_error().
+ */
+#define DIRT_SHADE_SH_PARAMS 30
+#define DIRT_SHADE_SH_NORMALIZE 4u
+size_t dirt_shade_sh_scratch_bytes(long long scenes, long long pixels);
+int dirt_shade_sh_forward(const float *gbuffer, const float *colors, const float *params, float *out, long long scenes,
+                          long long pixels, int Cg, int color_stride, int off_colors, int off_normals, int off_mask,
+                          int param_scenes, float scale0, float scale1, float scale2, float clamp_lo, float clamp_hi,
+                          unsigned flags, void *stream);
+int dirt_shade_sh_backward(const float *gbuffer, const float *colors, const float *params, const float *grad_out,
+                           float *grad_gbuffer, float *grad_colors, float *grad_params, void *scratch, size_t scratch_bytes,
+                           long long scenes, long long pixels, int Cg, int color_stride, int off_colors, int off_normals,
+                           int off_mask, int param_scenes, float scale0, float scale1, float scale2, float clamp_lo,
+                           float clamp_hi, unsigned flags, void *stream);
 
 /*
  * The vertex stage in front of the rasteriser, fused.  Replaces the torch composition of the reference's samples
