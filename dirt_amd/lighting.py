@@ -152,3 +152,81 @@ def spherical_harmonics(vertex_normals, vertex_colors, coefficients, band_scale=
         coefficients = coefficients.reshape((coefficients.shape[0],) + (1,) * (basis.dim() - 2) + (K, 3))
     irradiance = (basis[..., None] * coefficients).sum(-2)
     return vertex_colors * irradiance
+
+
+# ---- Cook-Torrance metallic-roughness reflectance (GGX distribution, Smith-Schlick visibility, Schlick Fresnel).  Not in the
+# reference: the material model of inverse rendering.  This is the specification `shading.shade_gbuffer_pbr` implements per
+# pixel.
+
+PBR_KINDS = ('directional', 'point')
+
+
+def cook_torrance_lobes(vertex_positions, vertex_normals, vertex_colors, roughness, metalness, camera_position, lights,
+                        min_roughness=0.04, dielectric_f0=0.04):
+    """The two lobes of `cook_torrance` apart: a list, per light, of (diffuse, specular, weight, products) with diffuse =
+    kd c / pi and specular = D Vis F ([*, V, 3] each), weight = light colour * max(n^ . l, 0) and products = n^ * l, the three
+    products n^ . l adds up; the light's term is (diffuse + specular) * weight."""
+    min_roughness, dielectric_f0 = float(min_roughness), float(dielectric_f0)
+    if not 0. < min_roughness <= 1.:
+        raise ValueError('min_roughness must be > 0 and <= 1, got %r' % min_roughness)
+    if not 0. <= dielectric_f0 <= 1.:
+        raise ValueError('dielectric_f0 must lie in [0, 1], got %r' % dielectric_f0)
+    p = _as(vertex_positions, torch.zeros((), dtype=torch.float32))
+    n, c, r, mu, cam = (_as(x, p) for x in (vertex_normals, vertex_colors, roughness, metalness, camera_position))
+    normalize = lambda x: torch.nn.functional.normalize(x, dim=-1, eps=1.e-12)   # noqa: E731
+    dot = lambda a, b: torch.sum(a * b, dim=-1, keepdim=True)   # noqa: E731
+    nh_ = normalize(n)
+    v = normalize(cam[..., None, :] - p)
+    r, mu = r[..., None], mu[..., None]
+    rho = torch.clamp(r, min_roughness, 1.)
+    a2 = (rho * rho) * (rho * rho)
+    k = (rho + 1.) * (rho + 1.) / 8.
+    f0 = dielectric_f0 * (1. - mu) + c * mu
+    nv = torch.clamp(dot(nh_, v), min=0.)
+    lobes = []
+    for i, rec in enumerate(lights):
+        if not isinstance(rec, (tuple, list)) or len(rec) != 3 or rec[0] not in PBR_KINDS:
+            raise ValueError('light %d: expected (%s, vector, color), got %r' % (i, ' or '.join(repr(s) for s in PBR_KINDS), rec))
+        d, kc = _as(rec[1], p), _as(rec[2], p)
+        l = normalize(-d[..., None, :]).expand_as(p) if rec[0] == 'directional' else normalize(d[..., None, :] - p)
+        h = normalize(l + v)
+        nl, nh, vh = (torch.clamp(dot(a, b), min=0.) for a, b in ((nh_, l), (nh_, h), (v, h)))
+        x = torch.linalg.cross(nh_, h, dim=-1)
+        den = dot(x, x) + torch.mul(a2, nh * nh)   # a call, not an operator: tests/shade_pbr_reference.py cuts the autograd path here
+        D = a2 / (torch.pi * (den * den))
+        vis = 0.25 / ((nl * (1. - k) + k) * (nv * (1. - k) + k))
+        w = 1. - vh
+        F = f0 + (1. - f0) * (((w * w) * (w * w)) * w)
+        kd = (1. - F) * (1. - mu)
+        lobes.append((kd * c / torch.pi, (D * vis) * F, kc[..., None, :] * nl, nh_ * l))
+    return lobes
+
+
+def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, metalness, camera_position, lights,
+                  min_roughness=0.04, dielectric_f0=0.04):
+    """Metallic-roughness reflectance under directional and point lights, summed.
+    positions, normals, colours (albedo) [*, V, 3]; roughness, metalness [*, V]; camera_position [*, 3];
+    lights: records ('directional', direction [*, 3], color [*, 3]) or ('point', position [*, 3], color [*, 3]) -> [*, V, 3]
+    (zeros without lights).  Per point (every normalisation is torch.nn.functional.normalize, x / max(|x|, 1e-12)):
+
+        n^ = normalize(n)                     v = normalize(cam - p)
+        rho = clamp(r, min_roughness, 1)      a2 = (rho^2)^2                  k = (rho + 1)^2 / 8
+        F0_j = dielectric_f0 (1 - mu) + c_j mu                                nv = max(n^ . v, 0)
+        per light:  l = normalize(-d) (directional)  |  normalize(d - p) (point: towards the light; no distance fall-off)
+                    h = normalize(l + v)      nl = max(n^ . l, 0)   nh = max(n^ . h, 0)   vh = max(v . h, 0)
+                    D   = a2 / (pi den^2),  den = |n^ x h|^2 + a2 nh^2
+                    Vis = 0.25 / ((nl (1 - k) + k) (nv (1 - k) + k))
+                    w = 1 - vh,  F_j = F0_j + (1 - F0_j) ((w w)(w w) w)       kd_j = (1 - F_j)(1 - mu)
+                    L_j = (kd_j c_j / pi + D Vis F_j) color_j nl
+
+    `den` is written with the cross product (|n^ x h|^2 = 1 - nh^2 for unit vectors): the subtractive form nh^2 (a2 - 1) + 1
+    loses four decimal digits in float32 at low roughness.  `Vis` is the Smith-Schlick term with the 4 nl nv of the
+    microfacet denominator cancelled: nothing divides by a cosine.  min_roughness in (0, 1] and dielectric_f0 in [0, 1] are
+    python numbers."""
+    lobes = cook_torrance_lobes(vertex_positions, vertex_normals, vertex_colors, roughness, metalness, camera_position, lights,
+                                min_roughness, dielectric_f0)
+    p = _as(vertex_positions, torch.zeros((), dtype=torch.float32))
+    total = torch.zeros_like(_as(vertex_colors, p) + p)
+    for diffuse, specular, weight, _ in lobes:
+        total = total + (diffuse + specular) * weight
+    return total

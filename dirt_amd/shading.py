@@ -201,8 +201,8 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
 
 
 def _channel_offsets(gbuffer, attributes):
-    """The first channel of each of `attributes` (name, channel index or None or -- colors only -- a tensor, width, required)
-    inside a pixel of `gbuffer`, -1 for an absent one and for colours that are a tensor; refuses what does not fit or overlaps."""
+    """The first channel of each of `attributes` (name, channel index or None or -- colors and material only -- a tensor, width,
+    required) inside a pixel of `gbuffer`, -1 for an absent one and for one that is a tensor; refuses what does not fit or overlaps."""
     dev = gbuffer.device
     cg = int(gbuffer.shape[-1])
     offsets, offsets_named = [], []
@@ -210,15 +210,15 @@ def _channel_offsets(gbuffer, attributes):
         if off is None and not required:
             offsets.append(-1)
             continue
-        if name == 'colors' and isinstance(off, torch.Tensor):
-            want = tuple(gbuffer.shape[:-1]) + (3,)
+        if name in ('colors', 'material') and isinstance(off, torch.Tensor):
+            want = tuple(gbuffer.shape[:-1]) + (width,)
             if not off.dtype.is_floating_point:
-                raise ValueError('colors as a tensor must be floating-point, got %s' % off.dtype)
+                raise ValueError('%s as a tensor must be floating-point, got %s' % (name, off.dtype))
             if tuple(off.shape) != want:
-                raise ValueError('colors as a tensor must have shape %s (the G-buffer\'s %s with 3 channels), got %s'
-                                 % (list(want), list(gbuffer.shape), list(off.shape)))
+                raise ValueError('%s as a tensor must have shape %s (the G-buffer\'s %s with %d channels), got %s'
+                                 % (name, list(want), list(gbuffer.shape), width, list(off.shape)))
             if off.device != dev:
-                raise ValueError('colors is on %s, the G-buffer on %s' % (off.device, dev))
+                raise ValueError('%s is on %s, the G-buffer on %s' % (name, off.device, dev))
             offsets.append(-1)
             continue
         if isinstance(off, bool) or not isinstance(off, int):
@@ -386,3 +386,144 @@ def _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background
     else:
         tensors.append((3 * _SH_TERMS, bg))
     return offsets, scale, lo, hi, flags, const, tensors
+
+
+# ---- Cook-Torrance metallic-roughness lighting (dirt_shade_pbr.hip)
+
+_PBR_KINDS = _lib.SHADE_PBR_KINDS
+
+
+def pbr_directional_light(direction, color):
+    """A light record for `shade_gbuffer_pbr`: light travelling along `direction` (normalised by the shader)."""
+    return ('directional', direction, color)
+
+
+def pbr_point_light(position, color):
+    """A light record for `shade_gbuffer_pbr`: a light at `position`, without distance fall-off."""
+    return ('point', position, color)
+
+
+class _ShadeGBufferPBR(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, block, colors, material, meta):
+        """colors / material: None (channels of the G-buffer) or float32 [..., 3] / [..., 2] beside it, read in place under
+        `_stage.rows_in_place`"""
+        lib = _lib.load()
+        scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = meta
+        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
+        block = block.contiguous()
+        csrc, cstride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+        msrc, mstride = _stage.rows_in_place(material, 2) if material is not None else (None, 0)
+        if scenes * pixels:
+            _stage.call(lib.dirt_shade_pbr_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), out.data_ptr(),
+                        scenes, pixels, cg, cstride, mstride, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
+        ctx.save_for_backward(gbuffer, block, csrc, msrc)
+        ctx.meta, ctx.strides = meta, (cstride, mstride)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, block, csrc, msrc = ctx.saved_tensors
+        scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = ctx.meta
+        dev = gbuffer.device
+        want_p = ctx.needs_input_grad[1]
+        want_c = csrc is not None and ctx.needs_input_grad[2]
+        want_m = msrc is not None and ctx.needs_input_grad[3]
+        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
+        # dense [..., 3] and [..., 2], whatever the tensors' strides
+        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None
+        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (2,), dtype=torch.float32) if want_m else None
+        if not scenes * pixels:
+            return grad_g, grad_p, grad_c.zero_() if want_c else None, grad_m.zero_() if want_m else None, None
+        grad_out = grad_out.to(torch.float32).contiguous()
+        nbytes = lib.dirt_shade_pbr_scratch_bytes(scenes, pixels, nl) if want_p else 0
+        _stage.call(lib.dirt_shade_pbr_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), grad_out.data_ptr(),
+                    _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg,
+                    *ctx.strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
+        return grad_g, grad_p, grad_c, grad_m, None
+
+
+def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, camera_position, mask=None, ambient=(0., 0., 0.),
+                      background=(0., 0., 0.), clamp=(0., 1.), min_roughness=0.04, dielectric_f0=0.04):
+    """Lights a G-buffer per pixel with the Cook-Torrance metallic-roughness model in one kernel, differentiably: what
+    `lighting.cook_torrance` computes per vertex (GGX distribution, Smith-Schlick visibility, Schlick Fresnel; its docstring
+    is the specification), composited and clamped as `shade_gbuffer` does.
+
+    gbuffer, colors (the albedo: channel index or tensor [..., 3]), normals, positions, mask, ambient, background,
+        camera_position, clamp: as in `shade_gbuffer`; `positions` and `camera_position` are required.
+    material: the first of two consecutive G-buffer channels (roughness, metalness), or a floating-point tensor shaped like the
+        G-buffer with 2 channels on its device, differentiable and read in place where its pixels lie a constant stride >= 2
+        floats apart: `tex[..., :3]` and `tex[..., 3:5]` of a 5-channel texture look-up serve as colours and material.
+    lights: up to 4 records ('directional', direction, color) or ('point', position, color); `pbr_directional_light` and
+        `pbr_point_light` build them.  Vectors and colours: 3 numbers or a tensor [3], or [B, 3] with a [B, H, W, Cg] G-buffer;
+        tensors are differentiable.  Directions are normalised by the shader; point lights have no distance fall-off.
+    min_roughness (in (0, 1]: the roughness is clamped to [min_roughness, 1]) and dielectric_f0 (in [0, 1]: the Fresnel
+        reflectance of a non-metal at normal incidence): python numbers, not differentiable.
+
+    Returns [..., 3]:  clamp((ambient * c + sum of the lights' terms) * m + background * (1 - m), lo, hi).
+    Gradients are those of torch's autograd for that composition, including at the kinks (max(x, 0) and the clamps pass the
+    gradient at their edges, the norm of a zero vector has gradient 0).  A zero normal makes the distribution term a2 / 0 and
+    the pixel inf * 0 = NaN whatever its mask, as in `lighting.cook_torrance`: give the uncovered pixels of a deferred renderer
+    a unit normal (examples/fit_material_fused.py::background_attributes)."""
+    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
+        raise ValueError('shade_gbuffer_pbr expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_pbr')
+    lights = list(lights)
+    offsets, kinds, scalars, lo, hi, flags, const, tensors = _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask,
+                                                                                   ambient, camera_position, background, clamp, min_roughness,
+                                                                                   dielectric_f0)
+    block = _splice_block(gbuffer.device, const, tensors)
+    g = gbuffer.to(torch.float32).contiguous()
+    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
+    pixels = g.numel() // (cg * scenes) if scenes else 0
+    meta = (scenes, pixels, cg, tuple(offsets), len(lights), kinds, scalars, lo, hi, flags)
+    as_input = lambda x: x.to(torch.float32) if isinstance(x, torch.Tensor) else None   # noqa: E731
+    return _ShadeGBufferPBR.apply(g, block, as_input(colors), as_input(material), meta)
+
+
+def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask, ambient, camera_position, background, clamp,
+                         min_roughness, dielectric_f0):
+    """Everything `shade_gbuffer_pbr` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel
+    offsets (colors, material, normals, positions, mask), light kinds, (min_roughness, dielectric_f0), lo, hi, flags, the
+    block's constant row, [(first slot, tensor [1 or B, width])])."""
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('shade_gbuffer_pbr expects a float32 gbuffer, got %s' % gbuffer.dtype)
+    dev = gbuffer.device
+    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('material', material, 2, True), ('normals', normals, 3, True),
+                                         ('positions', positions, 3, True), ('mask', mask, 1, False)))
+    if len(lights) > _lib.SHADE_PBR_MAX_LIGHTS:
+        raise ValueError('shade_gbuffer_pbr takes at most %d lights, got %d' % (_lib.SHADE_PBR_MAX_LIGHTS, len(lights)))
+    scalars = []
+    for name, x, text, ok in (('min_roughness', min_roughness, '> 0 and <= 1', lambda v: 0. < v <= 1.),
+                              ('dielectric_f0', dielectric_f0, 'in [0, 1]', lambda v: 0. <= v <= 1.)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not ok(float(x)):
+            raise ValueError('%s must be a number %s, got %r' % (name, text, x))
+        scalars.append(float(x))
+    if camera_position is None:
+        raise ValueError('shade_gbuffer_pbr needs camera_position')
+    lo, hi = _clamp_bounds(clamp)
+    flags = _lib.SHADE_CLAMP if clamp is not None else 0
+    # the parameter block: [1 or B, 9 + 8 lights] in the layout of `_light_block`
+    slots = [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
+             (6, _value(camera_position, 3, 'camera_position', dev, batch))]
+    kinds = 0
+    for l, rec in enumerate(lights):
+        if not isinstance(rec, (tuple, list)) or not rec or rec[0] not in _PBR_KINDS:
+            raise ValueError('light %d: expected a record starting with one of %s, got %r' % (l, sorted(_PBR_KINDS), rec))
+        if len(rec) != 3:
+            raise ValueError('light %d: a %s record has 3 fields, got %d' % (l, rec[0], len(rec)))
+        base = _lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * l
+        slots.append((base, _value(rec[1], 3, 'light %d %s' % (l, 'position' if rec[0] == 'point' else 'direction'), dev, batch)))
+        slots.append((base + 3, _value(rec[2], 3, 'light %d color' % l, dev, batch)))
+        kinds |= _PBR_KINDS[rec[0]] << l
+    const = [0.] * (_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights))
+    tensors = []
+    for start, v in slots:
+        if isinstance(v, list):
+            const[start:start + len(v)] = v
+        else:
+            tensors.append((start, v))
+    return offsets, kinds, tuple(scalars), lo, hi, flags, const, tensors

@@ -401,6 +401,45 @@ int dirt_shade_sh_backward(const float *gbuffer, const float *colors, const floa
                            long long scenes, long long pixels, int Cg, int color_stride, int off_colors, int off_normals,
                            int off_mask, int param_scenes, float scale0, float scale1, float scale2, float clamp_lo,
                            float clamp_hi, unsigned flags, void *stream);
+/*
+ * Cook-Torrance (metallic-roughness) lighting of a G-buffer, fused (the reference has no such model; the specification is
+ * DESIGN.md §7b and dirt_amd/lighting.py::cook_torrance).  Per pixel, with albedo c, normal n, position p, roughness r,
+ * metalness mu, mask m, and every normalisation x / max(|x|, 1e-12):
+ *     N = normalize(n)   v = normalize(camera - p)   rho = clamp(r, min_roughness, 1)   a2 = (rho^2)^2   k = (rho + 1)^2 / 8
+ *     F0_j = dielectric_f0 (1 - mu) + c_j mu         nv = max(N . v, 0)
+ *     per light:  l = normalize(-vector) (directional) | normalize(vector - p) (point);  h = normalize(l + v)
+ *                 nl = max(N . l, 0)  nh = max(N . h, 0)  vh = max(v . h, 0)
+ *                 D = a2 / (pi den^2), den = |N x h|^2 + a2 nh^2;   Vis = 0.25 / ((nl (1 - k) + k) (nv (1 - k) + k))
+ *                 F_j = F0_j + (1 - F0_j) (1 - vh)^5;   kd_j = (1 - F_j)(1 - mu);   L_j = (kd_j c_j / pi + D Vis F_j) colour_j nl
+ *     out_j = clamp((ambient_j c_j + sum L_j) m + background_j (1 - m), clamp_lo, clamp_hi)
+ *   gbuffer [scenes, pixels, Cg], read in place.  colors NULL: the colour is the three channels at off_colors; otherwise
+ *   colors [scenes, pixels, color_stride >= 3] and off_colors is not read.  material NULL: roughness and metalness are the two
+ *   channels at off_material; otherwise material [scenes, pixels, material_stride >= 2] and off_material is not read.
+ *   off_normals, off_positions: three channels each; off_mask: one, or -1 (every pixel covered).  Attributes may not overlap.
+ *   params [param_scenes, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights], param_scenes = 1 or scenes: ambient[3],
+ *   background[3], camera[3], then per light {vector[3], colour[3], 0, 0}.  lights: 0..DIRT_SHADE_PBR_MAX_LIGHTS; light_kinds:
+ *   bit i set = light i is a point light (bits beyond `lights` are refused).  min_roughness in (0, 1], dielectric_f0 in [0, 1].
+ *   flags: DIRT_SHADE_CLAMP; any other bit is refused.   out [scenes, pixels, 3].
+ * Backward: grad_gbuffer [scenes, pixels, Cg], fully written; grad_colors [scenes, pixels, 3] and grad_material
+ * [scenes, pixels, 2], dense, only with colors / material; grad_params like params.  Each may be NULL and is then not
+ * computed -- all four NULL: success, nothing is launched.  grad_params needs `scratch` of
+ * dirt_shade_pbr_scratch_bytes(scenes, pixels, lights) bytes (0: invalid sizes): one row of partial sums per workgroup, added
+ * by a second launch in a fixed order -- no atomics, the same bits on every run.  Zero scenes or pixels: success, nothing is
+ * launched or written.  Failures: dirt_last_error().
+ */
+#define DIRT_SHADE_PBR_MAX_LIGHTS 4
+size_t dirt_shade_pbr_scratch_bytes(long long scenes, long long pixels, int lights);
+int dirt_shade_pbr_forward(const float *gbuffer, const float *colors, const float *material, const float *params, float *out,
+                           long long scenes, long long pixels, int Cg, int color_stride, int material_stride, int off_colors,
+                           int off_material, int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                           unsigned light_kinds, float min_roughness, float dielectric_f0, float clamp_lo, float clamp_hi,
+                           unsigned flags, void *stream);
+int dirt_shade_pbr_backward(const float *gbuffer, const float *colors, const float *material, const float *params,
+                            const float *grad_out, float *grad_gbuffer, float *grad_colors, float *grad_material,
+                            float *grad_params, void *scratch, size_t scratch_bytes, long long scenes, long long pixels, int Cg,
+                            int color_stride, int material_stride, int off_colors, int off_material, int off_normals,
+                            int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds,
+                            float min_roughness, float dielectric_f0, float clamp_lo, float clamp_hi, unsigned flags, void *stream);
 
 /*
  * The vertex stage in front of the rasteriser, fused.  Replaces the torch composition of the reference's samples
