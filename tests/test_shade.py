@@ -873,3 +873,118 @@ def test_graphed_step_captures_the_fused_shader(gpu):
     for a, b in ((gv, leaves[1].grad), (gvc, leaves[2].grad)):   # float atomics in the rasteriser's gradient: summation order
         agree = (a - b).abs() <= 1e-4 * torch.maximum(a.abs(), b.abs()) + 1e-9
         assert float(agree.float().mean()) >= 0.99
+
+
+# ---- many scenes, many rows of partial sums: shade_launch_reduce (dirt_shade.hip) and the grid's y dimension, which this file,
+# tests/test_shade_sh.py and tests/test_shade_pbr_edges.py share.  The bound is derived from dirt_stage.h::block_column_sum:
+# lane t adds rows t, t + 256, ... one after the other (ceil(rows / 256) additions, the first to a zero), then the 256 lanes
+# fold in 8 halvings; the longest chain of additions an element passes through is L = ceil(rows / 256) + 8, and
+# |sum32 - sum64| <= L 2^-24 sum |row| to first order.
+
+REDUCE_BLOCK, FOLD_LEVELS = 256, 8     # SHADE_BLOCK lanes reduce a column; 256 -> 1 in eight halvings
+MAX_SCENES = 65535                     # the grid's y dimension; 65536 is refused (test_c_entry_points_refuse_bad_arguments_without_a_device)
+SPAN = 1024                            # pixels of a backward workgroup of the three shaders (BLOCK x ITER of each)
+
+
+def reduce_chain(rows):
+    """L: the additions of the longest chain block_column_sum makes over `rows` rows"""
+    return -(-rows // REDUCE_BLOCK) + FOLD_LEVELS
+
+
+def within_the_reduce_bound(got, rows, what):
+    """got [P]: the float32 column sums of rows [R, P] by block_column_sum"""
+    rows = rows.double().cpu()
+    L = reduce_chain(rows.shape[0])
+    err, bound = (got.double().cpu().reshape(-1) - rows.sum(0)).abs(), L * 2. ** -24 * rows.abs().sum(0)
+    print('%s: %d rows, L = %d, worst |sum32 - sum64| / bound = %.3f' % (what, rows.shape[0], L, float((err / bound.clamp_min(1e-300)).max())))
+    assert bool((bound > 0).any()) and bool((err <= bound).all()), (what, err, bound)
+
+
+def many_scenes(run, dev, pixels, values, seed, what):
+    """[65535, 1, 1, Cg]: the grid's y dimension at its limit.  run(g, values, go) -> (out, d gbuffer, {name: gradient}) is the
+    fused call with gradients; pixels: numpy [n, Cg], dealt out to the scenes in turn; values: {name: GPU tensor}, the
+    parameters one block has.
+    With a block per scene (the values times U(0.9, 1.1) per scene), a scene's output, d gbuffer and parameter gradients have
+    the bits of a one-scene call on its pixel with its parameters.  With one block shared, output and d gbuffer have the bits
+    of the pixels run as one flat frame, and the parameter sums -- 65535 rows, 256 turns of the reduce loop per lane -- lie
+    within the bound of the float64 sum of the rows, which are what the per-scene call on the same values returns row by row
+    (one row per scene there: its reduce adds the row to a zero)."""
+    B, (n, cg) = MAX_SCENES, pixels.shape
+    rng = np.random.default_rng(seed)
+    g = torch.from_numpy(pixels)[torch.from_numpy(np.arange(B) % n)].to(dev).reshape(B, 1, 1, cg)
+    go = torch.from_numpy(rng.standard_normal((B, 1, 1, 3)).astype(np.float32)).to(dev)
+    rows_of = lambda v: v[None].expand((B,) + tuple(v.shape))   # noqa: E731
+    per_scene = {k: (rows_of(v) * torch.from_numpy(rng.uniform(0.9, 1.1, (B,) + tuple(v.shape)).astype(np.float32)).to(dev)).contiguous()
+                 for k, v in values.items()}
+    out, dg, dp = run(g, per_scene, go)
+    assert all(dp[k].shape == per_scene[k].shape for k in values)
+    for s in (0, 1, 255, 256, 257, 32768, B - 256, B - 1):
+        o1, g1, p1 = run(g[s:s + 1], {k: v[s] for k, v in per_scene.items()}, go[s:s + 1])
+        assert torch.equal(out[s], o1[0]) and torch.equal(dg[s], g1[0]), (what, s)
+        for k in values:
+            assert torch.equal(dp[k][s], p1[k]), (what, s, k)
+    _, _, rows = run(g, {k: rows_of(v).contiguous() for k, v in values.items()}, go)
+    out, dg, dp = run(g, values, go)
+    flat_out, flat_dg, _ = run(g.reshape(B, cg), values, go.reshape(B, 3))
+    assert torch.equal(out.reshape(B, 3), flat_out) and torch.equal(dg.reshape(B, cg), flat_dg), what
+    assert reduce_chain(B) == 264
+    for k in values:
+        within_the_reduce_bound(dp[k], rows[k].reshape(B, -1), '%s, 65535 scenes, d %s' % (what, k))
+
+
+def frame_of_512_rows(run, dev, pixels, grad_out, values, seed, what):
+    """[2, 512, 512, Cg] with one parameter block: 256 workgroups per scene, 512 rows, the reduce loop's second turn in every
+    lane.  The frame is one workgroup's span of pixels (numpy [1024, Cg]) 512 times over, its grad_out that span's times a
+    signed power of two per workgroup: output and d gbuffer have the bits of the span run alone (scaled: exact), and every
+    row of partial sums is the span's parameter gradients scaled likewise, so the sums are known in float64."""
+    copies, (n, cg) = 512, pixels.shape
+    assert n == SPAN and grad_out.shape == (SPAN, 3)
+    span_g, span_go = torch.from_numpy(pixels).to(dev), torch.from_numpy(grad_out).to(dev)
+    o1, g1, p1 = run(span_g, values, span_go)
+    # 1 or 2 in a lane's first turn, 0.5 or 4 in its second: the two rows a lane adds never cancel, so neither can go missing unseen
+    rng = np.random.default_rng(seed)
+    scale = rng.choice([-1., 1.], copies) * np.where(np.arange(copies) < REDUCE_BLOCK, rng.choice([1., 2.], copies), rng.choice([0.5, 4.], copies))
+    scale = torch.from_numpy(scale.astype(np.float32)).to(dev)
+    g = span_g.repeat(copies, 1).reshape(2, 512, 512, cg)
+    go = (span_go[None] * scale[:, None, None]).reshape(2, 512, 512, 3)
+    out, dg, dp = run(g, values, go)
+    assert torch.equal(out.reshape(copies, SPAN, 3), o1[None].expand(copies, -1, -1)), what
+    assert torch.equal(dg.reshape(copies, SPAN, cg), g1[None] * scale[:, None, None]) and bool(g1.any()), what
+    assert reduce_chain(copies) == 10
+    for k in values:
+        within_the_reduce_bound(dp[k], p1[k].reshape(1, -1) * scale[:, None], '%s, 2 x 512 x 512, d %s' % (what, k))
+
+
+def _many(dev):
+    """-> (run, pixels, grad_out, values) of the two-light extra case for `many_scenes` and `frame_of_512_rows`"""
+    from dirt_amd import shading
+    case, _ = extra_case('lights2')
+    values = {k: case.kw[k] for k in ('ambient', 'background', 'camera_position')}
+    for i, rec in enumerate(case.lights):
+        values['light%d.vector' % i], values['light%d.color' % i] = rec[1], rec[2]
+        if rec[0] == 'specular_directional':
+            values['light%d.shininess' % i] = rec[3]
+    values = {k: torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev) for k, v in values.items()}
+
+    def run(g, values, go):
+        g = g.detach().requires_grad_(True)
+        named = {k: v.detach().requires_grad_(True) for k, v in values.items()}
+        lights = [(rec[0], named['light%d.vector' % i], named['light%d.color' % i]) +
+                  ((named['light%d.shininess' % i],) if rec[0] == 'specular_directional' else ()) + (rec[-1],) for i, rec in enumerate(case.lights)]
+        out = shading.shade_gbuffer(g, lights, clamp=case.kw['clamp'], **case.layout, **{k: named[k] for k in ('ambient', 'background', 'camera_position')})
+        out.backward(go)
+        return out.detach(), g.grad, {k: t.grad for k, t in named.items()}
+
+    return run, case.g, case.go, values
+
+
+@pytest.mark.gpu
+def test_65535_scenes_of_one_pixel(gpu):
+    run, pixels, _, values = _many(gpu)
+    many_scenes(run, gpu, pixels, values, 5400, 'shade_gbuffer')
+
+
+@pytest.mark.gpu
+def test_a_2x512x512_frame_adds_512_rows(gpu):
+    run, pixels, grad_out, values = _many(gpu)
+    frame_of_512_rows(run, gpu, pixels[:SPAN], grad_out[:SPAN], values, 5401, 'shade_gbuffer')

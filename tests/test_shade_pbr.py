@@ -138,7 +138,8 @@ def _layout_n(name):
 
 CASES = dict(
     {'lights_' + name: dict(seed=6000 + i, kinds=kinds) for i, (name, kinds) in enumerate(LIGHT_SETS.items())},
-    **{'pattern_channels': dict(seed=6050, layout='c12'), 'pattern_tensors': dict(seed=6051, layout='t7', kinds=(P, D, D))},
+    **{'pattern_channels': dict(seed=6050, layout='c12'), 'pattern_tensors': dict(seed=6051, layout='t7', kinds=(P, D, D)),
+       'pattern_tensors_0': dict(seed=6053, layout='t7', kinds=())},     # tests/test_shade_pbr_edges.py: no light, both tensors
     **_options(),
     **{name: dict(seed=6200 + i, layout=name, n=_layout_n(name), kinds=(D, P, P, D)[:1 + i % 4], clamp=(0., 1.) if i % 3 else None)
        for i, name in enumerate(list(CHANNEL_LAYOUTS) + list(TENSOR_LAYOUTS))},
@@ -391,6 +392,8 @@ def test_the_cases_hold_what_their_names_say():
     mixed = case_of('scenes_%d_mixed' % (SPAN + 1))[0]
     assert mixed.n == 3 * (SPAN + 1) and mixed.params['ambient'].shape == (3, 3) and mixed.params['light1.color'].shape == (3,)
     assert case_of('scenes_%d_shared' % SPAN)[0].idx is None
+    dark, ref = case_of('pattern_tensors_0')
+    assert dark.kinds == () and dark.colors is not None and dark.material is not None and dark.n == FLAT and ref['cosines'].shape == (FLAT, 1)
 
 
 def _movement(alt, ref, kinds):

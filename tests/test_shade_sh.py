@@ -835,3 +835,38 @@ def test_the_example_recovers_the_light(gpu):
     ex = _load_example('fit_sh_lighting_fused')
     losses, before, after = ex.fit(width=64, height=48, steps=30, device=gpu)
     assert losses[-1] < losses[0] and after < before
+
+
+def _many(dev):
+    """-> (run, pixels, grad_out, values) of `pattern_channel` for the many-scenes checks of tests/test_shade.py"""
+    from dirt_amd import shading
+    case, _ = case_of('pattern_channel')
+    values = {'coefficients': torch.from_numpy(case.coefficients).to(dev), 'background': torch.from_numpy(case.kw['background']).to(dev)}
+
+    def run(g, values, go):
+        g = g.detach().requires_grad_(True)
+        named = {k: v.detach().requires_grad_(True) for k, v in values.items()}
+        out = shading.shade_gbuffer_sh(g, named['coefficients'], colors=case.layout['colors'], normals=case.layout['normals'],
+                                       mask=case.layout['mask'], background=named['background'], clamp=case.kw['clamp'],
+                                       normalize=case.kw['normalize'], band_scale=case.kw['band_scale'])
+        out.backward(go)
+        return out.detach(), g.grad, {k: t.grad for k, t in named.items()}
+
+    return run, case.g, case.go, values
+
+
+@pytest.mark.gpu
+def test_65535_scenes_of_one_pixel(gpu):
+    """the grid's y dimension at its limit and 65535 rows in shade_launch_reduce: tests/test_shade.py::many_scenes"""
+    from tests import test_shade
+    run, pixels, _, values = _many(gpu)
+    assert SPAN == test_shade.SPAN
+    test_shade.many_scenes(run, gpu, pixels, values, 5400, 'shade_gbuffer_sh')
+
+
+@pytest.mark.gpu
+def test_a_2x512x512_frame_adds_512_rows(gpu):
+    """512 rows of partial sums shared by two scenes: tests/test_shade.py::frame_of_512_rows"""
+    from tests import test_shade
+    run, pixels, grad_out, values = _many(gpu)
+    test_shade.frame_of_512_rows(run, gpu, pixels[:SPAN], grad_out[:SPAN], values, 5401, 'shade_gbuffer_sh')
