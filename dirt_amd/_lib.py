@@ -62,6 +62,7 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
            'dirt_texture_sample_batch_forward', 'dirt_texture_sample_batch_backward_image', 'dirt_texture_mip_build_batch',
            'dirt_texture_mip_collapse_batch', 'dirt_texture_sample_mip_batch_forward', 'dirt_texture_sample_mip_batch_backward',
+           'dirt_texture_cube_forward', 'dirt_texture_cube_backward',
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward', 'dirt_shade_albedo_forward', 'dirt_shade_albedo_backward',
            'dirt_shade_sh_scratch_bytes', 'dirt_shade_sh_forward', 'dirt_shade_sh_backward',
            'dirt_shade_pbr_scratch_bytes', 'dirt_shade_pbr_forward', 'dirt_shade_pbr_backward',
@@ -147,6 +148,12 @@ def load():
         lib.dirt_texture_sample_mip_batch_forward.restype = i
         lib.dirt_texture_sample_mip_batch_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, ll, ll, ll, i, i, i, i, i, i, i, i, f32, u, vp]
         lib.dirt_texture_sample_mip_batch_backward.restype = i
+    if hasattr(lib, 'dirt_texture_cube_forward') or not override:   # cube-map look-up (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_texture_cube_forward.argtypes = [fp, fp, fp, fp, ll, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_cube_forward.restype = i
+        lib.dirt_texture_cube_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, f32, u, vp]
+        lib.dirt_texture_cube_backward.restype = i
     if hasattr(lib, 'dirt_shade_forward') or not override:   # fused G-buffer lighting (ABI 4, additive)
         f32 = ctypes.c_float
         lib.dirt_shade_scratch_bytes.argtypes = [ll, ll, i]

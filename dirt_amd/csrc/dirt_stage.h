@@ -1,5 +1,5 @@
 // dirt_stage.h -- what the fused stages around the rasteriser share, each piece written and explained once here:
-//   texture look-up   (dirt_texture.hip, dirt_texture_mip.hip; what only those two share -- the per-look-up arithmetic, the backward tile scheme, the pixel grid -- is dirt_texture_common.h);
+//   texture look-up   (dirt_texture.hip, dirt_texture_mip.hip, dirt_texture_cube.hip; what only those three share -- the per-look-up arithmetic, the backward tile scheme, the pixel grid -- is dirt_texture_common.h);
 //   G-buffer lighting (dirt_shade.hip);
 //   vertex stage      (dirt_geometry.hip);
 //   skinning          (dirt_skin.hip: Float3 / Float4 / load3 / store3, dot3, the wave sum, the four-wave fold, the error channel, the scratch check);

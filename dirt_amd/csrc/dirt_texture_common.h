@@ -1,5 +1,5 @@
 // dirt_texture_common.h -- what the texture kernels share (dirt_texture.hip: nearest / bilinear; dirt_texture_mip.hip: trilinear over a
-// mip pyramid).  Per look-up: (u, v) -> fractional (row, column) index of the reference's samples/textured.py:16-26, the four bilinear taps of
+// mip pyramid; dirt_texture_cube.hip: the three by direction into a cube map).  Per look-up: (u, v) -> fractional (row, column) index of the reference's samples/textured.py:16-26, the four bilinear taps of
 // :36-60, the channel-vector loads / stores, the blend.  The pieces of the backward tile scheme.  The rule of a batched launch (a texture per scene).
 // Host: the pixel grid, a launch for one texture or a batch (Scenes), the scene count of a batch, the clear of a buffer.
 #pragma once
@@ -72,6 +72,31 @@ __device__ __forceinline__ float bilinear_blend(float tl, float tr, float bl, fl
 {
     const float ta = (tl * k.wc0) * k.wr0, tb = (tr * k.fc) * k.wr0, tc = (bl * k.wc0) * k.fr, td = (br * k.fc) * k.fr;
     return ((ta + tb) + tc) + td;
+}
+
+// ---- what the trilinear look-ups share (dirt_texture_mip.hip; dirt_texture_cube.hip: a pyramid per cube face) ----
+// the size of a dimension n0 at level k of a mip pyramid
+__host__ __device__ __forceinline__ int mip_dim(int n0, int k) { const int d = n0 >> k; return d > 1 ? d : 1; }
+
+// clamp to [0, L - 1] (NaN -> 0), split into level and fraction (spec 4 of dirt_texture_mip.hip)
+__device__ __forceinline__ void mip_split(float lam, int L, int& l, float& f)
+{
+    const float top = (float)(L - 1);
+    const float c = lam > 0.f ? (lam < top ? lam : top) : 0.f;
+    const float fl = floorf(c);
+    l = (int)fl; f = c - fl;
+}
+
+// the bilinear sample of one level [*, Wk, Ct]
+template <int CT>
+__device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk, const Taps& k, int Ct, int ch, float (&o)[CT ? CT : 1])
+{
+    constexpr int NV = CT ? CT : 1;
+    float a[NV], b[NV], c[NV], d[NV];
+    load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c0) * Ct, Ct, a, ch); load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c1) * Ct, Ct, b, ch);
+    load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c0) * Ct, Ct, c, ch); load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c1) * Ct, Ct, d, ch);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) o[j] = bilinear_blend(a[j], b[j], c[j], d[j], k);
 }
 
 // ---- backward: a workgroup takes a tw x th tile of the pixel grid (16 x 16 of an image `cols` wide; 256 x 1 of a flat list).  The

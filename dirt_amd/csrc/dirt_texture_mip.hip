@@ -61,8 +61,6 @@ struct MipParams : MipArgs {
     long long off[MIP_MAX];  // float offset of each level in the packed buffers
 };
 
-__host__ __device__ __forceinline__ int mip_dim(int n0, int k) { const int d = n0 >> k; return d > 1 ? d : 1; }
-
 // the floats of the packed pyramid
 template <class P> __host__ __device__ __forceinline__ long long mip_floats(const P& p)
 {
@@ -125,15 +123,6 @@ template <class P> __device__ __forceinline__ float mip_lambda(const P& p, long 
     const float ax = dux * (float)p.Wt, bx = dvx * (float)p.Ht, ay = duy * (float)p.Wt, by = dvy * (float)p.Ht;
     const float rx = sqrtf(ax * ax + bx * bx), ry = sqrtf(ay * ay + by * by);
     return log2f(fmaxf(rx, ry)) + p.lod_bias;
-}
-
-// clamp to [0, L - 1] (NaN -> 0), split into level and fraction (spec 4)
-__device__ __forceinline__ void mip_split(float lam, int L, int& l, float& f)
-{
-    const float top = (float)(L - 1);
-    const float c = lam > 0.f ? (lam < top ? lam : top) : 0.f;
-    const float fl = floorf(c);
-    l = (int)fl; f = c - fl;
 }
 
 // ---- pyramid build: a workgroup takes a block of th x tw base texels (32 x 32 where the pyramid goes that far) and reduces it
@@ -244,18 +233,6 @@ __global__ __launch_bounds__(256) void mip_collapse_kernel(const float* __restri
         }
         gt[e] = acc;
     }
-}
-
-// the bilinear sample of one level [*, Wk, Ct]
-template <int CT>
-__device__ __forceinline__ void mip_sample(const float* __restrict__ lvl, int Wk, const Taps& k, int Ct, int ch, float (&o)[CT ? CT : 1])
-{
-    constexpr int NV = CT ? CT : 1;
-    float a[NV], b[NV], c[NV], d[NV];
-    load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c0) * Ct, Ct, a, ch); load_ch<CT>(lvl + ((size_t)k.r0 * Wk + k.c1) * Ct, Ct, b, ch);
-    load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c0) * Ct, Ct, c, ch); load_ch<CT>(lvl + ((size_t)k.r1 * Wk + k.c1) * Ct, Ct, d, ch);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) o[j] = bilinear_blend(a[j], b[j], c[j], d[j], k);
 }
 
 // the taps of level l for a level-0 index (and the derivatives of the level's index)

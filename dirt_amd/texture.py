@@ -10,7 +10,11 @@ the same values bit for bit.
 screen-space footprint of the (u, v) image (dirt_texture_mip.hip; specification in DESIGN.md §7).
 
 `sample_texture_uv_batch` and `mip_pyramid_batch` are the same two for a texture per scene, [B, Ht, Wt, C]: every pass is one
-launch for all scenes (the dirt_texture_*_batch entry points), not a Python loop of B calls."""
+launch for all scenes (the dirt_texture_*_batch entry points), not a Python loop of B calls.
+
+`sample_texture_cube` looks a cube map [6, N, N, C] up by direction (an environment map; dirt_texture_cube.hip), with the
+same three filters; `directions_to_cube_indices` and `sample_cube` are its pure-torch form, as `uvs_to_pixel_indices` and
+`sample_texture` are the flat look-up's."""
 import ctypes
 import functools
 import math
@@ -347,3 +351,135 @@ def mip_pyramid_batch(textures, max_level=None):
     levels, floats, geo = _mip_geometry(ht, wt, ct, max_level)
     packed = _MipPyramid.apply(textures.to(torch.float32), levels, floats, scenes)
     return [packed[:, o:o + h * w * ct].view(scenes, h, w, ct) for (o, h, w) in geo]
+
+
+# ---- cube map: a texture indexed by a direction (dirt_texture_cube.hip; specification in DESIGN.md §7) ---------------------------
+
+def directions_to_cube_indices(directions, size):
+    """[..., 3] directions (not normalised) -> (face int64 [...], fractional (row, column) indices float32 [..., 2] into a
+    `size` x `size` face, valid bool [...]): the major axis picks the face (+X, -X, +Y, -Y, +Z, -Z = 0..5, ties to X before Y
+    before Z), the other two components over its magnitude give the GL texel-centre index, clamped to the face.  A direction
+    that is not finite or is all zero is not valid: face 0, index 0, and no gradient.  Pure torch, on any device, differentiable;
+    `sample_cube(cube, *directions_to_cube_indices(directions, size))` is what `sample_texture_cube` fuses."""
+    with torch.no_grad():
+        valid = torch.isfinite(directions).all(-1) & (directions.abs().amax(-1) > 0)
+    d = torch.where(valid.unsqueeze(-1), directions, torch.zeros_like(directions))
+    x, y, z = d.unbind(-1)
+    ax, ay, az = x.abs(), y.abs(), z.abs()
+    is_x = (ax >= ay) & (ax >= az)
+    is_y = ~is_x & (ay >= az)
+    a = torch.where(is_x, ax, torch.where(is_y, ay, az))
+    pos = torch.where(is_x, x, torch.where(is_y, y, z)) > 0
+    face = torch.where(is_x, 0, torch.where(is_y, 2, 4)) + (~pos).to(torch.int64)
+    sc = torch.where(is_x, torch.where(pos, -z, z), torch.where(is_y, x, torch.where(pos, x, -x)))
+    tc = torch.where(is_y, torch.where(pos, z, -z), -y)
+    a = torch.where(valid, a, torch.ones_like(a))
+    indices = torch.stack([tc, sc], -1) / a.unsqueeze(-1)
+    indices = (((indices + 1.) * 0.5) * float(size) - 0.5).clamp(0., float(size - 1))
+    zero = torch.zeros_like(face)
+    return torch.where(valid, face, zero), torch.where(valid.unsqueeze(-1), indices, torch.zeros_like(indices)), valid
+
+
+def sample_cube(cube, face, indices, valid, mode='bilinear'):
+    """cube [6, N, N, C], and per look-up the face, the fractional (row, column) `indices` [..., 2] and `valid` of
+    `directions_to_cube_indices` -> [..., C]: the bilinear blend of the face's four texels around the index (taps never leave
+    the face), or with 'nearest' the texel whose centre is closest; 0 where not valid.  Pure torch, differentiable."""
+    n = cube.shape[1]
+
+    def fetch(rows, cols):
+        return cube[face, rows.clamp(0, n - 1), cols.clamp(0, n - 1)]
+
+    if mode == 'nearest':
+        idx = (indices + 0.5).to(torch.int64)
+        out = fetch(idx[..., 0], idx[..., 1])
+    elif mode == 'bilinear':
+        floor = torch.floor(indices)
+        frac = indices - floor
+        r, c = floor[..., 0].to(torch.int64), floor[..., 1].to(torch.int64)
+        fr, fc = frac[..., :1], frac[..., 1:]
+        out = (fetch(r, c) * (1. - fc) * (1. - fr) + fetch(r, c + 1) * fc * (1. - fr)
+               + fetch(r + 1, c) * (1. - fc) * fr + fetch(r + 1, c + 1) * fc * fr)
+    else:
+        raise NotImplementedError(mode)
+    return torch.where(valid.unsqueeze(-1), out, torch.zeros_like(out))
+
+
+class _SampleTextureCube(torch.autograd.Function):
+    """cube [6, N, N, C], directions [..., 3]; `lod` given: trilinear over a pyramid per face (pyramid and scratch [6, floats])."""
+
+    @staticmethod
+    def forward(ctx, cube, directions, lod, flags, lod_bias, max_level):
+        cube = cube.contiguous()
+        n, ct = int(cube.shape[1]), int(cube.shape[3])
+        lib = _lib.load()
+        src, stride = _stage.rows_in_place(directions, 3)
+        rows, cols, _ = _pixel_grid(directions.shape)
+        lod_t = lod.to(torch.float32).contiguous() if lod is not None else None
+        levels, pyr = 1, cube      # (one level: the packed pyramids are the cube itself)
+        if lod is not None:
+            levels, floats, _ = _mip_geometry(n, n, ct, max_level)
+            pyr = torch.empty((6, floats), dtype=torch.float32, device=cube.device)
+            _call_entry('mip_build', 6, cube.device, (cube.data_ptr(), pyr.data_ptr()), n, n, ct, levels)
+        out = torch.empty(tuple(directions.shape[:-1]) + (ct,), dtype=torch.float32, device=cube.device)
+        _call(lib.dirt_texture_cube_forward, cube.device, pyr.data_ptr(), _stage.ptr(src), _stage.ptr(lod_t), _stage.ptr(out), rows * cols, n, ct, levels,
+              stride, float(lod_bias), flags)
+        ctx.save_for_backward(pyr, src, lod_t)
+        ctx.meta = (stride, flags, float(lod_bias), tuple(directions.shape), rows, cols, n, ct, levels)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pyr, src, lod_t = ctx.saved_tensors
+        stride, flags, lod_bias, dir_shape, rows, cols, n, ct, levels = ctx.meta
+        dev = pyr.device
+        grad_out = grad_out.contiguous().to(torch.float32)
+        scratch = torch.empty((6, pyr.numel() // 6), dtype=torch.float32, device=dev)   # every level's gradient, cleared by the call
+        grad_dirs = torch.empty(dir_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        grad_lod = torch.empty(dir_shape[:-1], dtype=torch.float32, device=dev) if lod_t is not None and ctx.needs_input_grad[2] else None
+        _call(_lib.load().dirt_texture_cube_backward, dev, pyr.data_ptr(), _stage.ptr(src), _stage.ptr(lod_t), _stage.ptr(grad_out), scratch.data_ptr(),
+              _stage.ptr(grad_dirs), _stage.ptr(grad_lod), rows, cols, n, ct, levels, stride, 3, lod_bias, flags)
+        grad_cube = None
+        if ctx.needs_input_grad[0] and levels == 1:
+            grad_cube = scratch.view(6, n, n, ct)
+        elif ctx.needs_input_grad[0]:
+            grad_cube = torch.empty((6, n, n, ct), dtype=torch.float32, device=dev)
+            _call_entry('mip_collapse', 6, dev, (scratch.data_ptr(), grad_cube.data_ptr()), n, n, ct, levels)
+        return grad_cube, grad_dirs, grad_lod, None, None, None
+
+
+def sample_texture_cube(cube, directions, filter='bilinear', *, lod=None, lod_bias=0.0, max_level=None):
+    """Fused `sample_cube(cube, *directions_to_cube_indices(directions, N), filter)`: cube [6, N, N, C] float32 with its
+    faces in OpenGL order (+X, -X, +Y, -Y, +Z, -Z), directions [..., 3] (not normalised; a slice gbuffer[..., a:a+3] of a
+    contiguous G-buffer is read in place) -> [..., C].  A direction that is not finite or is all zero -- a background pixel's
+    normal -- gives 0 and takes no part in any gradient, so no mask is needed.  Each face clamps to its own edges (no
+    seamless filtering).  Differentiable with respect to the cube and the directions.
+
+    filter='trilinear' blends two adjacent levels of a mip pyramid per face (`mip_pyramid_batch(cube)`, capped by
+    `max_level`) at the level of detail `lod` + `lod_bias`; `lod`, shaped like directions[..., 0], is required (e.g. a
+    roughness times the top level) and is differentiable too.  The three keyword arguments apply to 'trilinear' only."""
+    who = 'sample_texture_cube'
+    if filter not in ('bilinear', 'nearest', 'trilinear'):
+        raise ValueError("%s: filter must be 'bilinear', 'nearest' or 'trilinear', got %r" % (who, filter))
+    if filter != 'trilinear' and (lod is not None or lod_bias != 0.0 or max_level is not None):
+        raise ValueError("lod, lod_bias and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
+    if not isinstance(cube, torch.Tensor) or cube.dim() != 4 or cube.shape[0] != 6 or cube.shape[1] != cube.shape[2] or 0 in cube.shape:
+        raise ValueError('%s expects cube to be 4D [6, size, size, channels], got shape %s' % (who, tuple(getattr(cube, 'shape', ()))))
+    if not isinstance(directions, torch.Tensor) or directions.dim() < 1 or directions.shape[-1] != 3:
+        raise ValueError('%s expects directions of shape [..., 3], got %s' % (who, tuple(getattr(directions, 'shape', ()))))
+    for name, t in (('cube', cube), ('directions', directions)):
+        if not t.is_floating_point():
+            raise ValueError('%s: %s must be a floating-point tensor, got %s' % (who, name, t.dtype))
+    if cube.device != directions.device:
+        raise ValueError('cube and directions must be on the same device (%s vs %s)' % (cube.device, directions.device))
+    if filter == 'trilinear':
+        _check_max_level(max_level)
+        if lod is None:
+            raise ValueError("%s: filter='trilinear' needs lod (a level of detail from the footprint of the directions is not supported)" % who)
+        if not isinstance(lod, torch.Tensor) or tuple(lod.shape) != tuple(directions.shape[:-1]):
+            raise ValueError('lod must be a tensor shaped like directions[..., 0] %s, got %s' % (tuple(directions.shape[:-1]), tuple(getattr(lod, 'shape', ()))))
+        if lod.device != directions.device:
+            raise ValueError('lod and directions must be on the same device (%s vs %s)' % (lod.device, directions.device))
+    _stage.require_gpu(cube, 'dirt_amd.texture.sample_texture_cube')
+    return _SampleTextureCube.apply(cube.to(torch.float32), directions.to(torch.float32), lod, _lib.TEX_NEAREST if filter == 'nearest' else 0,
+                                    float(lod_bias), max_level)

@@ -312,6 +312,28 @@ int dirt_texture_sample_mip_batch_backward(const float *pyramids, const float *u
                                            float *grad_lod, long long scenes, long long rows, long long cols, int image_rows, int Ht,
                                            int Wt, int Ct, int levels, int uv_stride, int grad_uv_stride, int mask_stride,
                                            float lod_bias, unsigned flags, void *stream);
+/* CUBE-MAP look-up: a texture indexed by a direction (an environment map).  These two replace no reference interface -- the
+ * reference's samples/textured.py:16-61 has flat textures only; specification in dirt_amd/csrc/dirt_texture_cube.hip and
+ * DESIGN.md §7.  `pyramid` [6, floats]: the packed pyramid of each `size` x `size` x `channels` face, faces in the order +X, -X,
+ * +Y, -Y, +Z, -Z, as dirt_texture_mip_build_batch makes it of the cube [6, size, size, channels] with scenes = 6 and `floats` as
+ * dirt_texture_mip_levels(size, size, channels, ...) says; with levels = 1 it is the cube itself.  directions: n triples
+ * (x, y, z) `dir_stride` >= 3 floats apart, read in place (4-byte alignment suffices), not normalised; one that is not finite
+ * or all zero gives 0 in every channel and adds to no gradient.  lod [n]: the look-up is trilinear, lambda = lod + lod_bias;
+ * NULL: level 0 only, bilinear, or its nearest texel with DIRT_TEX_NEAREST -- the only flag these calls take (a face clamps
+ * to its edges: DIRT_TEX_CLAMP is refused, as is DIRT_TEX_NEAREST with lod).  out [n, channels].
+ * Backward: the n = rows x cols look-ups as a pixel grid (a flat list: rows = 1), tiled as dirt_texture_sample_backward_image
+ * tiles it.  grad_out [n, channels] -> grad_pyramid [6, floats] (cleared by the call, by a kernel on `stream`, also when
+ * n == 0; the gradient of every level -- dirt_texture_mip_collapse_batch with scenes = 6 turns it into the cube's),
+ * grad_directions (triples `grad_dir_stride` >= 3 apart, only the three floats of a row are written; may be NULL) and grad_lod
+ * (n; may be NULL, needs `lod`).  Both return 0 or DIRT_E_*, described by dirt_texture_last_error(); refused before any device
+ * work: the flags above, sizes < 1, strides < 3, levels outside 1..dirt_texture_mip_levels(size, size, ...), NULL required
+ * pointers, a pixel grid that overflows or has more than 2^31 - 1 tiles, grad_lod without lod. */
+int dirt_texture_cube_forward(const float *pyramid, const float *directions, const float *lod, float *out, long long n, int size,
+                              int channels, int levels, int dir_stride, float lod_bias, unsigned flags, void *stream);
+int dirt_texture_cube_backward(const float *pyramid, const float *directions, const float *lod, const float *grad_out,
+                               float *grad_pyramid, float *grad_directions, float *grad_lod, long long rows, long long cols,
+                               int size, int channels, int levels, int dir_stride, int grad_dir_stride, float lod_bias,
+                               unsigned flags, void *stream);
 
 /*
  * G-buffer lighting of a deferred shader, fused.  Replaces the torch composition of the reference's shader
