@@ -38,6 +38,7 @@ SHADE_SH_NORMALIZE = 4
 SHADE_SH_PARAMS = 30   # floats of the spherical-harmonic parameter block: 9 coefficients x 3 channels, then the background
 SHADE_PBR_MAX_LIGHTS = 4
 SHADE_PBR_KINDS = {'directional': 0, 'point': 1}   # the bit of a light in light_kinds
+NORMAL_MAP_ENCODED = 1
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
 GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
@@ -69,7 +70,9 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
            'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward',
-           'dirt_blend_scratch_bytes', 'dirt_blend_forward', 'dirt_blend_backward')
+           'dirt_blend_scratch_bytes', 'dirt_blend_forward', 'dirt_blend_backward',
+           'dirt_tangent_scratch_bytes', 'dirt_tangent_forward', 'dirt_tangent_backward',
+           'dirt_normal_map_forward', 'dirt_normal_map_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -212,6 +215,18 @@ def load():
         lib.dirt_blend_forward.restype = i
         lib.dirt_blend_backward.argtypes = [i, i, fp, ll, ip, ip, fp, fp, fp, fp, fp, fp, vp, sz, ll, ll, i, i, i, u, vp]
         lib.dirt_blend_backward.restype = i
+    if hasattr(lib, 'dirt_tangent_forward') or not override:   # tangent-space normal mapping (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_tangent_scratch_bytes.argtypes = [ll, ll, ll]
+        lib.dirt_tangent_scratch_bytes.restype = sz
+        lib.dirt_tangent_forward.argtypes = [fp, i, fp, fp, ip, ip, ip, fp, ll, ll, ll, vp]
+        lib.dirt_tangent_forward.restype = i
+        lib.dirt_tangent_backward.argtypes = [fp, i, fp, fp, ip, ip, ip, fp, fp, fp, vp, sz, ll, ll, ll, vp]
+        lib.dirt_tangent_backward.restype = i
+        lib.dirt_normal_map_forward.argtypes = [fp, fp, fp, ll, ll, i, i, i, i, f32, u, vp]
+        lib.dirt_normal_map_forward.restype = i
+        lib.dirt_normal_map_backward.argtypes = [fp, fp, fp, fp, fp, ll, ll, i, i, i, i, f32, u, vp]
+        lib.dirt_normal_map_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

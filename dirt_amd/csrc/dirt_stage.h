@@ -4,7 +4,8 @@
 //   vertex stage      (dirt_geometry.hip);
 //   skinning          (dirt_skin.hip: Float3 / Float4 / load3 / store3, dot3, the wave sum, the four-wave fold, the error channel, the scratch check);
 //   kinematics        (dirt_kinematics.hip: Float4 / load3 / store3, dot3, the error channel, the scratch check);
-//   blend shapes      (dirt_blend.hip: Float4 / load3 / store3, load_quad / store_quad, the wave sum, the four-wave fold, the error channel, the scratch check).
+//   blend shapes      (dirt_blend.hip: Float4 / load3 / store3, load_quad / store_quad, the wave sum, the four-wave fold, the error channel, the scratch check);
+//   normal mapping    (dirt_tangent.hip, dirt_normal_map.hip: Float4 / load3 / store3, dot3 / cross3, the error channel, the scratch check).
 // Device side: the 12- and 16-byte accesses to rows that are only 4-byte aligned (Float3 of dirt_device.h, Float4, load3 /
 // store3: all four; load_quad / store_quad, a quad of a row with its zero-padded tail: blend shapes), dot3 / cross3 (shade, geometry), the all-lanes wave sum, the fold of a workgroup's four waves into its
 // row of partial sums and the fixed-order sum of a column of such rows (shade, geometry: their parameter and matrix gradients).

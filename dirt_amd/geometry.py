@@ -158,3 +158,81 @@ def vertex_normals(vertices, topology, pre_split=False):
     """`lighting.vertex_normals(vertices, faces)` (or `vertex_normals_pre_split` with pre_split=True) alone, in one kernel:
     [.., V, 3|4] -> [.., V, 3] (dirt/lighting.py:31-89,97-129)."""
     return vertex_stage(vertices, topology, pre_split=pre_split, want=('normals',))[2]
+
+
+# ---- per-vertex tangent frames (dirt_tangent.hip)
+
+class _VertexTangents(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertices, normals, uvs, topology, meta):
+        lib = _lib.load()
+        B, V, C, batched = meta
+        dev = vertices.device
+        tangents = torch.empty(((B, V) if batched else (V,)) + (4,), dtype=torch.float32, device=dev)
+        if B * V:
+            _stage.call(lib.dirt_tangent_forward, dev, vertices.data_ptr(), C, normals.data_ptr(), uvs.data_ptr(), *_index_pointers(topology),
+                        tangents.data_ptr(), B, V, topology.num_faces)
+        ctx.save_for_backward(vertices, normals, uvs)
+        ctx.topology, ctx.meta = topology, meta
+        return tangents
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_tangents):
+        lib = _lib.load()
+        vertices, normals, uvs = ctx.saved_tensors
+        topology = ctx.topology
+        B, V, C, batched = ctx.meta
+        dev = vertices.device
+        grads = _stage.grad_outputs((vertices, normals), ctx.needs_input_grad[:2], not B * V)
+        if not B * V:
+            return tuple(grads) + (None, None, None)
+        incoming, = _stage.float32_contiguous(grad_tangents)
+        nbytes = lib.dirt_tangent_scratch_bytes(B, V, topology.num_faces) if grads[0] is not None else 0
+        _stage.call(lib.dirt_tangent_backward, dev, vertices.data_ptr(), C, normals.data_ptr(), uvs.data_ptr(), *_index_pointers(topology),
+                    incoming.data_ptr(), *(_stage.ptr(g) for g in grads), _stage.ptr(_stage.scratch(dev, nbytes)), nbytes,
+                    B, V, topology.num_faces)
+        return tuple(grads) + (None, None, None)
+
+
+def _check_tangent_arguments(vertices, normals, uvs, topology):
+    """Everything `vertex_tangents` refuses with a ValueError, from shapes, dtypes and devices alone (no device work): ->
+    (B, V, C, batched)"""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() not in (2, 3) or vertices.shape[-1] not in (3, 4):
+        raise ValueError('vertex_tangents expects vertices [V, 3|4] or [B, V, 3|4], got %s' % (tuple(getattr(vertices, 'shape', ())),))
+    if vertices.dtype != torch.float32:
+        raise ValueError('vertex_tangents expects float32 vertices, got %s' % vertices.dtype)
+    if not isinstance(topology, MeshTopology):
+        raise ValueError('vertex_tangents expects a MeshTopology (build it once per mesh), got %r' % type(topology).__name__)
+    V, C = int(vertices.shape[-2]), int(vertices.shape[-1])
+    if V != topology.num_vertices:
+        raise ValueError('vertex_tangents: %d vertices, the topology was built for %d' % (V, topology.num_vertices))
+    want = tuple(vertices.shape[:-1]) + (3,)
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != want:
+        raise ValueError('normals must have shape %s (the vertices\' %s with 3 components), got %s'
+                         % (list(want), list(vertices.shape), list(getattr(normals, 'shape', ()))))
+    _stage.check_float32('normals', normals, vertices, 'vertices')
+    if not isinstance(uvs, torch.Tensor) or tuple(uvs.shape) != (V, 2):
+        raise ValueError('uvs must have shape [%d, 2] (one pair per vertex, shared by the scenes), got %s' % (V, list(getattr(uvs, 'shape', ()))))
+    _stage.check_float32('uvs', uvs, vertices, 'vertices')
+    B, batched = _stage.scene_count('vertex_tangents', ('vertices', vertices, 3))
+    _stage.check_index_device('vertex_tangents', 'topology', 'topology', topology, 'vertices', vertices)
+    return B, V, C, batched
+
+
+def vertex_tangents(vertices, normals, uvs, topology):
+    """`lighting.vertex_tangents(vertices, normals, uvs, faces)` in one kernel, differentiably: the per-vertex tangent frames
+    of tangent-space normal mapping, -> [.., V, 4] (the unit tangent, orthogonal to the normal, along increasing u; the
+    handedness -1 / +1 of the bitangent).  Interpolated over the mesh next to the normals, they are what
+    `shading.perturb_normals` takes.
+
+    vertices: float32 [V, 3|4] or [B, V, 3|4] on the GPU (only x, y, z are used); normals: [.., V, 3] with the same lead,
+        taken as given (unit, as `vertex_stage` returns them); uvs: float32 [V, 2] on the same device, shared by the scenes,
+        constant; topology: the mesh's `MeshTopology`.
+    A vertex no face names, or whose faces are all degenerate in uv, gets (0, 0, 0, 1).  Gradients go to the vertices (a
+    fourth component gets zeros) and to the normals; the handedness is a sign and carries none.  The scatter of the torch
+    form (six `index_add`s) is a gather over the topology's inverted index, forward and backward: no atomics, the same bits
+    on every run, and nothing in a call synchronises with the host."""
+    meta = _check_tangent_arguments(vertices, normals, uvs, topology)
+    _stage.require_gpu(vertices, 'dirt_amd.geometry.vertex_tangents')
+    return _VertexTangents.apply(vertices.contiguous(), normals.contiguous(), uvs.detach().contiguous(), topology, meta)

@@ -230,3 +230,75 @@ def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, me
     for diffuse, specular, weight, _ in lobes:
         total = total + (diffuse + specular) * weight
     return total
+
+
+# ---- tangent-space normal mapping.  Not in the reference: per-vertex tangent frames from the uvs and the per-pixel frame
+# that turns a normal-map texel into a shading normal.  These are the specifications `geometry.vertex_tangents` and
+# `shading.perturb_normals` implement.
+
+def _dot(a, b):
+    return torch.sum(a * b, dim=-1, keepdim=True)
+
+
+def _guarded_unit(x):
+    """(x / |x| with a denominator of 1 where x is zero, so that no NaN reaches a gradient; [..., 1] bool: x . x > 0)"""
+    xx = _dot(x, x)
+    ok = xx > 0
+    return x / torch.sqrt(torch.where(ok, xx, torch.ones_like(xx))), ok
+
+
+def vertex_tangents(vertices, normals, uvs, faces):
+    """Per-vertex tangent frames from the uv parametrisation: [*, V, 3|4], [*, V, 3], [V, 2], [F, 3] -> [*, V, 4], the unit
+    tangent (the direction of increasing u, orthogonal to the normal) and the handedness w = -1 or +1 of the bitangent
+    w * cross(n, t) against the direction of increasing v.  The normals are taken as given (unit, as `vertex_normals` returns
+    them); the uvs are shared by the scenes and constant (no gradient).  Per face, with s = sign(det) (0 for a degenerate uv
+    triangle, which contributes nothing):
+
+        e1 = p1 - p0, e2 = p2 - p0      (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0      det = du1 dv2 - du2 dv1
+        t_f = s (dv2 e1 - dv1 e2)       b_f = s (du1 e2 - du2 e1)
+
+    Per vertex, T and Bt the sums of t_f and b_f over the faces that name it (once per naming corner):
+
+        x = T - n (n . T)       t = x / |x| where x . x > 0, else 0       w = -1 where cross(n, t) . Bt < 0, else +1
+
+    w carries no gradient, and so neither does Bt."""
+    vertices, faces = _prepare_vertices_and_faces(vertices, faces)
+    p = vertices[..., :3]
+    n = _as(normals, p)
+    uv = _as(uvs, p).detach()
+    p0, p1, p2 = (p[..., faces[:, k], :] for k in range(3))
+    e1, e2 = p1 - p0, p2 - p0
+    d1, d2 = uv[faces[:, 1]] - uv[faces[:, 0]], uv[faces[:, 2]] - uv[faces[:, 0]]
+    du1, dv1, du2, dv2 = d1[:, 0:1], d1[:, 1:2], d2[:, 0:1], d2[:, 1:2]
+    s = torch.sign(du1 * dv2 - du2 * dv1)
+    t_f = (s * dv2) * e1 - (s * dv1) * e2
+    b_f = (s * du1) * e2 - (s * du2) * e1
+    T, Bt = torch.zeros_like(p), torch.zeros_like(p)
+    for k in range(3):
+        T = T.index_add(-2, faces[:, k], t_f)
+        Bt = Bt.index_add(-2, faces[:, k], b_f.detach())
+    t, _ = _guarded_unit(T - n * _dot(n, T))
+    w = torch.where(_dot(torch.linalg.cross(n, t, dim=-1), Bt) < 0, -1., 1.).to(t.dtype).detach()
+    return torch.cat([t, w], dim=-1)
+
+
+def perturb_normals(normals, tangents, normal_map, strength=1.0, encoded=True):
+    """The shading normal of a tangent-space normal map: [*, 3], [*, 4] (`vertex_tangents`, interpolated), [*, 3] -> [*, 3].
+
+        d = 2 normal_map - 1 if encoded, else normal_map;  d.xy *= strength  (a python number, no gradient)
+        N = n / |n|       x = t - N (N . t),  T = x / |x|       Bv = w cross(N, T)
+        y = d.x T + d.y Bv + d.z N        out = y / |y|
+
+    where n . n > 0, x . x > 0 and y . y > 0; any other element -- a background's zero normal, a zero tangent, a tangent
+    parallel to the normal, a zero decoded vector -- returns its normal unchanged and passes the incoming gradient to it
+    alone.  w multiplies as given (an interpolated handedness is a weight) and receives its gradient."""
+    n = _as(normals, torch.zeros((), dtype=torch.float32))
+    tangents, m = _as(tangents, n), _as(normal_map, n)
+    t, w = tangents[..., :3], tangents[..., 3:4]
+    d = 2. * m - 1. if encoded else m
+    dx, dy, dz = d[..., 0:1] * float(strength), d[..., 1:2] * float(strength), d[..., 2:3]
+    N, ok_n = _guarded_unit(n)
+    T, ok_x = _guarded_unit(t - N * _dot(N, t))
+    Bv = w * torch.linalg.cross(N, T, dim=-1)
+    out, ok_y = _guarded_unit((dx * T + dy * Bv) + dz * N)
+    return torch.where(ok_n & ok_x & ok_y, out, n)

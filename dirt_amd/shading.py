@@ -527,3 +527,84 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
         else:
             tensors.append((start, v))
     return offsets, kinds, tuple(scalars), lo, hi, flags, const, tensors
+
+
+# ---- tangent-space normal mapping (dirt_normal_map.hip)
+
+class _PerturbNormals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, normal_map, meta):
+        """normal_map: float32 [..., 3] beside the G-buffer, read in place under `_stage.rows_in_place`"""
+        lib = _lib.load()
+        scenes, pixels, cg, offsets, strength, flags = meta
+        out = torch.empty_like(gbuffer)
+        src, stride = _stage.rows_in_place(normal_map, 3)
+        if scenes * pixels:
+            _stage.call(lib.dirt_normal_map_forward, gbuffer.device, gbuffer.data_ptr(), src.data_ptr(), out.data_ptr(), scenes, pixels, cg, stride,
+                        *offsets, strength, flags)
+        ctx.save_for_backward(gbuffer, src)
+        ctx.meta, ctx.map_stride = meta, stride
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, src = ctx.saved_tensors
+        scenes, pixels, cg, offsets, strength, flags = ctx.meta
+        grad_g, = _stage.grad_outputs((gbuffer,), ctx.needs_input_grad[:1], not scenes * pixels)
+        # dense [..., 3], whatever the normal map's strides
+        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (3,), dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        if not scenes * pixels:
+            return grad_g, grad_m.zero_() if grad_m is not None else None, None
+        grad_out = grad_out.to(torch.float32).contiguous()
+        _stage.call(lib.dirt_normal_map_backward, gbuffer.device, gbuffer.data_ptr(), src.data_ptr(), grad_out.data_ptr(), _ptr(grad_g),
+                    _ptr(grad_m), scenes, pixels, cg, ctx.map_stride, *offsets, strength, flags)
+        return grad_g, grad_m, None
+
+
+def perturb_normals(gbuffer, normal_map, *, normals, tangents, strength=1.0, encoded=True):
+    """Tangent-space normal mapping of a G-buffer in one kernel, differentiably: what `lighting.perturb_normals` computes
+    per element, written back into the G-buffer, so that no `torch.cat` stands between a texture look-up and a shader.
+
+    gbuffer: float32 [H, W, Cg], [B, H, W, Cg] or a flat [N, Cg] on the GPU, as the shaders take it.
+    normals, tangents: the first channel of the interpolated normal (3 channels) and of the interpolated tangent frame of
+        `geometry.vertex_tangents` (4 channels: tangent and handedness) inside a pixel; no overlap.
+    normal_map: a floating-point tensor shaped like the G-buffer with 3 channels on its device, differentiable.  One whose
+        pixels lie a constant stride >= 3 floats apart -- `tex[..., 5:8]` of an 8-channel texture look-up -- is read in place.
+    strength: a python number multiplying the decoded x and y (0: the normals are only renormalised); not differentiable.
+    encoded: the map holds (d + 1) / 2, as an image file does, and is decoded as 2 m - 1; otherwise it holds d itself.
+
+    Returns a new G-buffer of the same shape: the normal channels hold the shading normal (unit), every other channel the
+    input's bits; `shade_gbuffer`, `shade_gbuffer_sh` and `shade_gbuffer_pbr` take it with the same channel indices.
+    A pixel with a zero normal (a background), with no tangent orthogonal to its normal or with a zero decoded vector keeps
+    its normal and passes the incoming gradient to it alone.  Gradients are those of torch's autograd for
+    `lighting.perturb_normals`: to the normal, tangent and handedness channels of the G-buffer (the other channels pass
+    theirs through) and to the normal map (dense [..., 3])."""
+    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
+        raise ValueError('perturb_normals expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    offsets, strength, flags = _check_normal_map_arguments(gbuffer, normal_map, normals, tangents, strength, encoded)
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.perturb_normals')
+    g = gbuffer.to(torch.float32).contiguous()
+    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
+    pixels = g.numel() // (cg * scenes) if scenes else 0
+    return _PerturbNormals.apply(g, normal_map.to(torch.float32), (scenes, pixels, cg, tuple(offsets), strength, flags))
+
+
+def _check_normal_map_arguments(gbuffer, normal_map, normals, tangents, strength, encoded):
+    """Everything `perturb_normals` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel offsets
+    (normals, tangents), strength, flags)"""
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('perturb_normals expects a float32 gbuffer, got %s' % gbuffer.dtype)
+    offsets = _channel_offsets(gbuffer, (('normals', normals, 3, True), ('tangents', tangents, 4, True)))
+    want = tuple(gbuffer.shape[:-1]) + (3,)
+    if not isinstance(normal_map, torch.Tensor) or not normal_map.dtype.is_floating_point:
+        raise ValueError('normal_map must be a floating-point tensor, got %s' % (getattr(normal_map, 'dtype', type(normal_map).__name__),))
+    if tuple(normal_map.shape) != want:
+        raise ValueError('normal_map must have shape %s (the G-buffer\'s %s with 3 channels), got %s'
+                         % (list(want), list(gbuffer.shape), list(normal_map.shape)))
+    if normal_map.device != gbuffer.device:
+        raise ValueError('normal_map is on %s, the G-buffer on %s' % (normal_map.device, gbuffer.device))
+    if isinstance(strength, bool) or not isinstance(strength, numbers.Real):
+        raise ValueError('strength must be a number, got %r' % (strength,))
+    return offsets, float(strength), _lib.NORMAL_MAP_ENCODED if encoded else 0

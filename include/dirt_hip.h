@@ -634,6 +634,49 @@ int dirt_blend_backward(int template_scenes, int coefficient_scenes, const float
                         long long V, int K, int Ks, int J, unsigned flags, void *stream);
 
 /*
+ * Tangent-space normal mapping, fused; specification in dirt_amd/csrc/dirt_tangent.hip, dirt_amd/csrc/dirt_normal_map.hip
+ * and DESIGN.md §7g (dirt_amd/lighting.py: `vertex_tangents`, `perturb_normals`).
+ *
+ * dirt_tangent_*: per-vertex tangent frames from the uv parametrisation, over the inverted index of the vertex stage.
+ *   vertices [B, V, components] (components = 3 or 4; only x, y, z are read), normals [B, V, 3] (taken as given),
+ *   uvs [V, 2] shared by the scenes, faces / offsets / entries as for dirt_geometry_forward (trusted likewise)
+ *   -> tangents [B, V, 4]: the unit tangent and the handedness -1 / +1; a vertex whose tangent sum has no part orthogonal
+ *   to its normal (no face, degenerate uv triangles only) gets (0, 0, 0, 1).  One launch.
+ * Backward: grad_tangents [B, V, 4] (the handedness' component is not read) -> grad_vertices [B, V, components] (a fourth
+ *   component gets zeros) and grad_normals [B, V, 3]; each may be NULL and is then not computed; those given are fully
+ *   written.  grad_vertices needs `scratch` of dirt_tangent_scratch_bytes(B, V, F) bytes (0: invalid sizes): d loss /
+ *   d (tangent sum) per vertex, which a second launch gathers over each vertex's faces.  No atomics, the same bits on
+ *   every run.  B or V equal to 0: success, nothing is launched.
+ *
+ * dirt_normal_map_*: a G-buffer [scenes, pixels, Cg] (7 <= Cg <= DIRT_SHADE_MAX_CHANNELS) with three channels of normals at
+ *   off_normals and four of tangent and handedness at off_tangents (no overlap), and a texel of three floats per pixel,
+ *   map_stride >= 3 floats apart -> out [scenes, pixels, Cg]: the G-buffer with its normal channels replaced by the
+ *   shading normal (a pixel with a zero normal, no tangent orthogonal to it or a zero decoded texel keeps its normal),
+ *   every other channel copied.  flags: DIRT_NORMAL_MAP_ENCODED (the texel is decoded as 2 m - 1); the decoded x and y
+ *   are multiplied by `strength`.  One launch.
+ * Backward: grad_out [scenes, pixels, Cg] -> grad_gbuffer [scenes, pixels, Cg] (grad_out with the normal channels
+ *   replaced by the normal's gradient and the tangent's and handedness' added to theirs) and grad_normal_map
+ *   [scenes, pixels, 3] dense; each may be NULL and is then not computed.  One launch, no scratch, no atomics.
+ *   scenes * pixels equal to 0: success, nothing is launched.
+ * Failures: dirt_last_error().
+ */
+#define DIRT_NORMAL_MAP_ENCODED 1u
+size_t dirt_tangent_scratch_bytes(long long B, long long V, long long F);
+int dirt_tangent_forward(const float *vertices, int components, const float *normals, const float *uvs, const int32_t *faces,
+                         const int32_t *offsets, const int32_t *entries, float *tangents, long long B, long long V,
+                         long long F, void *stream);
+int dirt_tangent_backward(const float *vertices, int components, const float *normals, const float *uvs, const int32_t *faces,
+                          const int32_t *offsets, const int32_t *entries, const float *grad_tangents, float *grad_vertices,
+                          float *grad_normals, void *scratch, size_t scratch_bytes, long long B, long long V, long long F,
+                          void *stream);
+int dirt_normal_map_forward(const float *gbuffer, const float *normal_map, float *out, long long scenes, long long pixels,
+                            int Cg, int map_stride, int off_normals, int off_tangents, float strength, unsigned flags,
+                            void *stream);
+int dirt_normal_map_backward(const float *gbuffer, const float *normal_map, const float *grad_out, float *grad_gbuffer,
+                             float *grad_normal_map, long long scenes, long long pixels, int Cg, int map_stride,
+                             int off_normals, int off_tangents, float strength, unsigned flags, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
