@@ -19,15 +19,16 @@
 //     gN = d.z gy + T x gC - ((N . t) gx + t (N . gx))                          d n = (gN - N (N . gN)) / |n|
 //     d m = (strength, strength, 1) d d, doubled when encoded
 //
-// Kernels: normal_map_forward_kernel, normal_map_backward_kernel; NM_ITER passes of NM_BLOCK pixels per workgroup.  A lane
-// computes one pixel from its seven channels and its texel and leaves the result in LDS; then the workgroup walks the pass's
+// Kernels: normal_map_forward_kernel, normal_map_backward_kernel; NM_ITER passes of NM_BLOCK pixels per workgroup
+// (dirt_shade_common.h holds the tile walk and the attribute check this file shares with the shaders).  A lane computes one
+// pixel from its seven channels and its texel and leaves the result in LDS; then the workgroup walks the pass's
 // NM_BLOCK * Cg floats in order, lane after lane, taking each from the source row (the G-buffer forward, grad_out backward)
 // or from LDS: every row is read and written whole, whatever Cg.  d normal_map is dense, one 12-byte store per lane.  There
 // are no parameter sums: no reduction, no scratch, no atomics.  `encoded` and the two outputs of the backward are
 // wave-uniform branches, not template arguments: the kernels are bound by their memory traffic, not by registers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "dirt_stage.h"
+#include "dirt_shade_common.h"
 
 namespace dirt {
 
@@ -92,11 +93,6 @@ __device__ __forceinline__ void nm_pixel(const NormalMapParams& P, long long pix
     px.valid = ok_n && ok_x && ok_y;
 }
 
-// the walk of the copy-out loops: element e = tid + NM_BLOCK * step of a pass is channel e % Cg of pixel e / Cg
-struct NmWalk { int step_px, step_ch, px0, ch0; };
-
-__device__ __forceinline__ NmWalk nm_walk(int Cg, int tid) { return NmWalk{NM_BLOCK / Cg, NM_BLOCK % Cg, tid / Cg, tid % Cg}; }
-
 // ---- forward: the G-buffer copied, its normal channels replaced
 __global__ __launch_bounds__(NM_BLOCK) void normal_map_forward_kernel(NormalMapParams P)
 {
@@ -104,7 +100,7 @@ __global__ __launch_bounds__(NM_BLOCK) void normal_map_forward_kernel(NormalMapP
     __shared__ unsigned char s_src[DIRT_SHADE_MAX_CHANNELS];
     const int tid = threadIdx.x, Cg = P.Cg;
     for (int ch = tid; ch < Cg; ch += NM_BLOCK) s_src[ch] = (unsigned char)((unsigned)(ch - P.on) < 3u ? ch - P.on : NM_PASS);
-    const NmWalk wk = nm_walk(Cg, tid);
+    const TileWalk wk = tile_walk<NM_BLOCK>(Cg, tid);
     for (int it = 0; it < NM_ITER; ++it) {
         const long long first = ((long long)blockIdx.x * NM_ITER + it) * NM_BLOCK;   // (uniform)
         if (first >= P.n) break;
@@ -118,15 +114,11 @@ __global__ __launch_bounds__(NM_BLOCK) void normal_map_forward_kernel(NormalMapP
         __syncthreads();
         const float* __restrict__ src = P.g + first * Cg;
         float* __restrict__ dst = P.out + first * Cg;
-        const int total = npx * Cg;
-        int pxi = wk.px0, ch = wk.ch0;
-        for (int e = tid; e < total; e += NM_BLOCK) {
+        tile_for_each<NM_BLOCK>(npx, Cg, tid, wk, [&](int e, int pxi, int ch) {
             const int k = s_src[ch];
             const float through = src[e];
             dst[e] = k == NM_PASS ? through : s_v[pxi * 3 + k];
-            pxi += wk.step_px; ch += wk.step_ch;
-            if (ch >= Cg) { ch -= Cg; ++pxi; }
-        }
+        });
         __syncthreads();
     }
 }
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(NM_BLOCK) void normal_map_backward_kernel(NormalMap
     const int tid = threadIdx.x, Cg = P.Cg;
     for (int ch = tid; ch < Cg; ch += NM_BLOCK)
         s_src[ch] = (unsigned char)((unsigned)(ch - P.on) < 3u ? ch - P.on : ((unsigned)(ch - P.ot) < 4u ? 3 + ch - P.ot : NM_PASS));
-    const NmWalk wk = nm_walk(Cg, tid);
+    const TileWalk wk = tile_walk<NM_BLOCK>(Cg, tid);
     for (int it = 0; it < NM_ITER; ++it) {
         const long long first = ((long long)blockIdx.x * NM_ITER + it) * NM_BLOCK;   // (uniform)
         if (first >= P.n) break;
@@ -192,16 +184,12 @@ __global__ __launch_bounds__(NM_BLOCK) void normal_map_backward_kernel(NormalMap
         __syncthreads();
         const float* __restrict__ src = P.gout + first * Cg;
         float* __restrict__ dst = P.gg + first * Cg;
-        const int total = npx * Cg;
-        int pxi = wk.px0, ch = wk.ch0;
-        for (int e = tid; e < total; e += NM_BLOCK) {
+        tile_for_each<NM_BLOCK>(npx, Cg, tid, wk, [&](int e, int pxi, int ch) {
             const int k = s_src[ch];
             const float through = src[e];
             const float mine = k == NM_PASS ? 0.f : s_v[pxi * NM_ROW + k];
             dst[e] = k == NM_PASS ? through : (k < 3 ? mine : through + mine);
-            pxi += wk.step_px; ch += wk.step_ch;
-            if (ch >= Cg) { ch -= Cg; ++pxi; }
-        }
+        });
         __syncthreads();
     }
 }
@@ -221,16 +209,14 @@ static int normal_map_check(const char* who, long long scenes, long long pixels,
     if (Cg < 7 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 7..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
     if (map_stride < 3) STAGE_FAIL("%s: map_stride=%d, a pixel's texel is 3 floats", who, map_stride);
     if (flags & ~DIRT_NORMAL_MAP_ENCODED) STAGE_FAIL("%s: unknown flags 0x%x", who, flags);
-    if (off_normals < 0 || off_normals + 3 > Cg) STAGE_FAIL("%s: normals at channel %d does not fit in %d channels", who, off_normals, Cg);
-    if (off_tangents < 0 || off_tangents + 4 > Cg) STAGE_FAIL("%s: tangents at channel %d does not fit in %d channels", who, off_tangents, Cg);
-    if (off_tangents < off_normals + 3 && off_normals < off_tangents + 4)
-        STAGE_FAIL("%s: tangents (channel %d) overlaps normals (channel %d)", who, off_tangents, off_normals);
+    const int off[2] = {off_normals, off_tangents}, width[2] = {3, 4};
+    const bool absent[2] = {false, false};
+    const char* const names[2] = {"normals", "tangents"};
+    if (int rc = dirt::shade_check_attributes(who, Cg, 2, off, width, absent, names)) return rc;
     P.n = scenes * pixels; P.Cg = Cg; P.mstride = map_stride; P.on = off_normals; P.ot = off_tangents;
     P.encoded = (flags & DIRT_NORMAL_MAP_ENCODED) ? 1 : 0;
     return DIRT_OK;
 }
-
-static long long normal_map_blocks(long long n) { return (n + dirt::NM_BLOCK * dirt::NM_ITER - 1) / (dirt::NM_BLOCK * dirt::NM_ITER); }
 
 int dirt_normal_map_forward(const float* gbuffer, const float* normal_map, float* out, long long scenes, long long pixels, int Cg, int map_stride,
                             int off_normals, int off_tangents, float strength, unsigned flags, void* stream)
@@ -242,7 +228,7 @@ int dirt_normal_map_forward(const float* gbuffer, const float* normal_map, float
     if (P.n == 0) return dirt::stage_ok(report);
     if (!gbuffer || !normal_map || !out) STAGE_FAIL("%s: gbuffer / normal_map / out is NULL", who);
     P.g = gbuffer; P.map = normal_map; P.out = out; P.strength = strength;
-    hipLaunchKernelGGL(dirt::normal_map_forward_kernel, dim3((unsigned)normal_map_blocks(P.n)), dim3(dirt::NM_BLOCK), 0,
+    hipLaunchKernelGGL(dirt::normal_map_forward_kernel, dim3((unsigned)dirt::shade_blocks(P.n, dirt::NM_BLOCK * dirt::NM_ITER)), dim3(dirt::NM_BLOCK), 0,
                        reinterpret_cast<hipStream_t>(stream), P);
     return dirt::stage_hip(report, who, hipGetLastError());
 }
@@ -258,7 +244,7 @@ int dirt_normal_map_backward(const float* gbuffer, const float* normal_map, cons
     if (P.n == 0 || (!grad_gbuffer && !grad_normal_map)) return dirt::stage_ok(report);
     if (!gbuffer || !normal_map || !grad_out) STAGE_FAIL("%s: gbuffer / normal_map / grad_out is NULL", who);
     P.g = gbuffer; P.map = normal_map; P.gout = grad_out; P.gg = grad_gbuffer; P.gmap = grad_normal_map; P.strength = strength;
-    hipLaunchKernelGGL(dirt::normal_map_backward_kernel, dim3((unsigned)normal_map_blocks(P.n)), dim3(dirt::NM_BLOCK), 0,
+    hipLaunchKernelGGL(dirt::normal_map_backward_kernel, dim3((unsigned)dirt::shade_blocks(P.n, dirt::NM_BLOCK * dirt::NM_ITER)), dim3(dirt::NM_BLOCK), 0,
                        reinterpret_cast<hipStream_t>(stream), P);
     return dirt::stage_hip(report, who, hipGetLastError());
 }

@@ -24,7 +24,8 @@
 // is written whole (zeros in the channels no attribute uses) with consecutive lanes on consecutive floats, and keeps the
 // parameter gradients in registers; these are summed over the wave with DPP adds, over the four waves in LDS, and leave the
 // workgroup as ONE row of partial sums in caller-owned scratch.  shade_reduce_kernel adds the rows in a fixed order: no
-// atomics, and the same bits on every run.
+// atomics, and the same bits on every run.  The tile walk, the clamp, the host checks and the backward's epilogue are those of
+// dirt_shade_common.h, shared with dirt_shade_sh.hip, dirt_shade_pbr.hip and dirt_normal_map.hip.
 //
 // ALBEDO: the colour comes from a second image, [scenes, pixels, >= 3 floats apart], instead of three channels of the G-buffer,
 // and its gradient leaves as a second, dense image (dirt_shade_albedo_forward / _backward): the flag changes where px.c is
@@ -33,7 +34,7 @@
 // DIRT_SHADE_ALBEDO_UNIT and includes it) the ALBEDO = true instantiations and their two entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "dirt_stage.h"
+#include "dirt_shade_common.h"
 
 #ifdef DIRT_SHADE_ALBEDO_UNIT
 #define SHADE_UNIT_ALBEDO true
@@ -46,7 +47,9 @@ namespace dirt {
 constexpr int SHADE_HEAD = DIRT_SHADE_PARAM_HEAD, SHADE_LIGHT = DIRT_SHADE_PARAM_LIGHT;
 constexpr int SHADE_BLOCK = 256;      // lanes of a workgroup, pixels of one of its passes
 constexpr int SHADE_ITER = 4;         // passes of a backward workgroup
+constexpr int SHADE_SPAN = SHADE_BLOCK * SHADE_ITER;   // pixels of a backward workgroup
 constexpr int SHADE_ROW = 11;         // floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], dm, 0
+constexpr int SHADE_ZERO = 10;        // the row's zero
 
 struct ShadeParams {
     const float* g;        // [scenes, pixels, Cg]
@@ -114,12 +117,6 @@ __device__ __forceinline__ void light_geometry(int kind, const float* __restrict
 // x or pow(x, s): the scalar factor of a light's term
 __device__ __forceinline__ float light_factor(int kind, float x, float s) { return kind == DIRT_SHADE_SPECULAR_DIRECTIONAL ? powf(x, s) : x; }
 
-__device__ __forceinline__ float clamp_out(const ShadeParams& P, float pre)
-{
-    if (!P.clamp) return pre;
-    return pre < P.lo ? P.lo : (pre > P.hi ? P.hi : pre);   // a NaN stays NaN, as torch.clamp leaves it
-}
-
 struct Pixel { float c[3], n[3], p[3], m; };
 
 template <bool ALBEDO>
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_forward_kernel(ShadeArgs<AL
     store3(P.out + pix * 3, o);
 }
 
-// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (10: the row's zero); with ALBEDO no channel is a colour
+// which value of a pixel's LDS row goes to channel `ch` of d gbuffer; with ALBEDO no channel is a colour
 // (oc is -1 there, which the range test below would take for channels 0 and 1)
 template <bool ALBEDO>
 __device__ __forceinline__ int shade_source(const ShadeParams& P, int ch)
@@ -172,7 +169,7 @@ __device__ __forceinline__ int shade_source(const ShadeParams& P, int ch)
     if ((unsigned)(ch - P.on) < 3u) return 3 + ch - P.on;
     if (P.op >= 0 && (unsigned)(ch - P.op) < 3u) return 6 + ch - P.op;
     if (ch == P.om) return 9;
-    return 10;
+    return SHADE_ZERO;
 }
 
 // ---- backward.  NL: the number of lights (the per-lane parameter sums are registers, indexed at compile time);
@@ -192,12 +189,11 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeArgs<A
     float acc[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = 0.f;
-    // the walk of the copy-out loop: element e = tid + 256 step of the tile is channel e % Cg of pixel e / Cg
-    const int Cg = P.Cg, step_px = SHADE_BLOCK / Cg, step_ch = SHADE_BLOCK % Cg;
-    const int px0 = tid / Cg, ch0 = tid % Cg;
+    const int Cg = P.Cg;
+    const TileWalk walk = tile_walk<SHADE_BLOCK>(Cg, tid);
     if constexpr (GBUF) {
         for (int ch = tid; ch < Cg; ch += SHADE_BLOCK) s_src[ch] = (unsigned char)shade_source<ALBEDO>(P, ch);
-        s_g[tid * SHADE_ROW + 10] = 0.f;
+        s_g[tid * SHADE_ROW + SHADE_ZERO] = 0.f;
     }
     for (int it = 0; it < SHADE_ITER; ++it) {
         const long long first = ((long long)blockIdx.x * SHADE_ITER + it) * SHADE_BLOCK;   // (uniform)
@@ -229,7 +225,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeArgs<A
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const float pre = lit[j] * px.m + prm[3 + j] * om;
-                const float gpre = (!P.clamp || (pre >= P.lo && pre <= P.hi)) ? go[j] : 0.f;   // closed at both edges; 0 at a NaN
+                const float gpre = clamp_gate(P, pre, go[j]);
                 glit[j] = gpre * px.m;
                 gm += gpre * lit[j];
                 gmb += gpre * prm[3 + j];
@@ -312,18 +308,8 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeArgs<A
                 r[9] = gm;
             }
         }
-        if constexpr (GBUF) {
-            __syncthreads();
-            float* __restrict__ dst = P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg;
-            const int total = npx * Cg;
-            int pxi = px0, ch = ch0;
-            for (int e = tid; e < total; e += SHADE_BLOCK) {
-                dst[e] = s_g[pxi * SHADE_ROW + s_src[ch]];
-                pxi += step_px; ch += step_ch;
-                if (ch >= Cg) { ch -= Cg; ++pxi; }
-            }
-            __syncthreads();
-        }
+        if constexpr (GBUF)
+            tile_rows_out<SHADE_BLOCK, SHADE_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
     }
     if constexpr (PARAMS) {
         const int wave = tid >> 6, lane = tid & 63;
@@ -339,9 +325,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void shade_backward_kernel(ShadeArgs<A
 }
 
 // ---- the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a fixed order:
-// workgroup (k, b) sums value k (block_column_sum).  One copy for both translation units: the ALBEDO one calls the launcher.
-void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
-
+// workgroup (k, b) sums value k (block_column_sum).  One copy for every unit (dirt_shade_common.h declares the launcher).
 #ifndef DIRT_SHADE_ALBEDO_UNIT
 __global__ __launch_bounds__(SHADE_BLOCK) void shade_reduce_kernel(const float* __restrict__ partial, float* __restrict__ grad_params,
                                                                    long long rows, int NP)
@@ -374,8 +358,6 @@ extern "C" {
 
 static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
-static long long shade_blocks(long long pixels) { return (pixels + dirt::SHADE_BLOCK * dirt::SHADE_ITER - 1) / (dirt::SHADE_BLOCK * dirt::SHADE_ITER); }
-
 // What the entry points of this translation unit take their colours from: channels off_colors.. of the G-buffer, or (ALBEDO) the
 // image `colors`, whose pixels are color_stride floats apart.  The checks and the launches below are written once for both;
 // what differs is written out where it does.
@@ -385,23 +367,15 @@ static int shade_check(const char* who, long long scenes, long long pixels, int 
                        int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds, unsigned flags, float lo, float hi,
                        dirt::ShadeParams& P)
 {
-    if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
-    if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
-    if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
-    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (int rc = dirt::shade_check_sizes(who, scenes, pixels, Cg)) return rc;
     if (ALBEDO && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
     if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) STAGE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_MAX_LIGHTS);
     if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
     // ALBEDO: the G-buffer has no colour channels (off_colors is -1), so three channels of normals are the smallest one
     const int off[4] = {off_colors, off_normals, off_positions, off_mask}, width[4] = {3, 3, 3, 1};
+    const bool absent[4] = {ALBEDO, false, off_positions == -1, off_mask == -1};
     const char* const names[4] = {"colors", "normals", "positions", "mask"};
-    for (int a = ALBEDO ? 1 : 0; a < 4; ++a) {
-        if (off[a] == -1 && a >= 2) continue;
-        if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
-        for (int b = ALBEDO ? 1 : 0; b < a; ++b)
-            if (off[b] >= 0 && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
-                STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
-    }
+    if (int rc = dirt::shade_check_attributes(who, Cg, 4, off, width, absent, names)) return rc;
     for (int l = 0; l < lights; ++l) {
         const int kind = (light_kinds >> (2 * l)) & 3;
         if (kind > DIRT_SHADE_DIFFUSE_POINT) STAGE_FAIL("%s: light %d has unknown kind %d", who, l, kind);
@@ -409,9 +383,9 @@ static int shade_check(const char* who, long long scenes, long long pixels, int 
         if (kind == DIRT_SHADE_SPECULAR_DIRECTIONAL && !(flags & DIRT_SHADE_HAS_CAMERA))
             STAGE_FAIL("%s: light %d is specular and needs a camera position (DIRT_SHADE_HAS_CAMERA)", who, l);
     }
-    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    if (int rc = dirt::shade_check_clamp(who, flags, lo, hi)) return rc;
     P.pixels = pixels; P.Cg = Cg; P.oc = ALBEDO ? -1 : off_colors; P.on = off_normals; P.op = off_positions; P.om = off_mask; P.nl = lights;
-    P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
+    P.pstride = dirt::shade_pstride(param_scenes, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
     P.kinds = light_kinds; P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0; P.lo = lo; P.hi = hi;
     return DIRT_OK;
 }
@@ -461,7 +435,7 @@ static int shade_backward(const char* who, const float* gbuffer, const float* co
         rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_shade_scratch_bytes(scenes, pixels, lights), "dirt_shade_scratch_bytes");
         if (rc) return rc;
     }
-    const long long blocks = shade_blocks(pixels);
+    const long long blocks = dirt::shade_blocks(pixels, dirt::SHADE_SPAN);
     if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
     P.g = gbuffer; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.partial = static_cast<float*>(scratch); P.dsided = double_sided;
     shade_set_colors(P, colors, color_stride, grad_colors);
@@ -479,23 +453,15 @@ static int shade_backward(const char* who, const float* gbuffer, const float* co
     case 7: dirt::shade_launch_backward<7, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
     default: dirt::shade_launch_backward<8, ALBEDO>(P, params_wanted, gbuf, grid, s); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
-    if (params_wanted) {
-        const int NP = DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
-        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
-        dirt::shade_launch_reduce(static_cast<const float*>(scratch), grad_params, rows, NP, param_scenes, s);
-        e = hipGetLastError();
-    }
-    return dirt::stage_hip(report, who, e);
+    return dirt::shade_backward_finish(who, scratch, grad_params, scenes, blocks, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights, param_scenes, s);
 }
 
 #ifndef DIRT_SHADE_ALBEDO_UNIT
 
 size_t dirt_shade_scratch_bytes(long long scenes, long long pixels, int lights)
 {
-    if (scenes < 0 || scenes > 65535 || pixels < 0 || pixels > (1ll << 40) || lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) return 0;
-    return sizeof(float) * (size_t)scenes * (size_t)shade_blocks(pixels) * (size_t)(DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
+    if (lights < 0 || lights > DIRT_SHADE_MAX_LIGHTS) return 0;
+    return dirt::shade_scratch_bytes(scenes, pixels, dirt::SHADE_SPAN, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
 }
 
 int dirt_shade_forward(const float* gbuffer, const float* params, float* out, long long scenes, long long pixels, int Cg, int off_colors,

@@ -1,0 +1,137 @@
+// dirt_shade_common.h -- what the G-buffer kernels share (dirt_shade.hip and its second unit dirt_shade_albedo.hip: the three
+// reflectance models; dirt_shade_sh.hip: spherical harmonics; dirt_shade_pbr.hip: Cook-Torrance; dirt_normal_map.hip: normal
+// mapping), each piece written and explained once here.  Device: the tile walk that makes every row of a [pixels, Cg] image
+// leave whole, the channel map it reads, the clamp and its gradient gate.  Host: the refusals every
+// *_check repeats (each file calls them in its own order, with its own checks in between: the order decides which message a
+// caller with two faults sees), the scratch size, and what follows a backward launch.  NOT shared: the wave-sum / lane-0 /
+// barrier / fold tail of the backward kernels (dirt_stage.h says why at fold_waves_to_row), the three shade_*_source
+// functions and the pixel arithmetic: these are what the files differ in.
+#pragma once
+#include "dirt_stage.h"
+
+namespace dirt {
+
+// ---- device ---------------------------------------------------------------------------------------------------------------
+
+// (The workgroup's shape -- BLOCK lanes, ITER passes -- stays a pair of constants in each file, SHADE_ / SH_ / PBR_ / NM_BLOCK
+// and _ITER: each file's tests read them there by name.  Everything below takes them as arguments.)
+
+// A pass is npx <= BLOCK consecutive pixels, npx * Cg consecutive floats of the image.  The workgroup walks them in order, lane
+// after lane: lane tid takes elements e = tid, tid + BLOCK, ..., so that consecutive lanes touch consecutive floats whatever
+// Cg.  Element e is channel e % Cg of pixel e / Cg; the walk keeps both without dividing inside the loop: it starts at
+// (tid / Cg, tid % Cg) and a step adds (BLOCK / Cg, BLOCK % Cg), carrying once where the channel passes Cg (BLOCK % Cg < Cg:
+// one carry is enough).  With Cg > BLOCK a step is (0, BLOCK) and the carry does all the pixel's counting.
+struct TileWalk { int step_px, step_ch, px0, ch0; };
+
+template <int BLOCK>
+__device__ __forceinline__ TileWalk tile_walk(int Cg, int tid) { return TileWalk{BLOCK / Cg, BLOCK % Cg, tid / Cg, tid % Cg}; }
+
+// f(e, pxi, ch) for this lane's elements of a pass of npx pixels (a partial last pass: npx < BLOCK, and the loop ends early)
+template <int BLOCK, class F>
+__device__ __forceinline__ void tile_for_each(int npx, int Cg, int tid, const TileWalk& wk, F&& f)
+{
+    const int total = npx * Cg;
+    int pxi = wk.px0, ch = wk.ch0;
+    for (int e = tid; e < total; e += BLOCK) {
+        f(e, pxi, ch);
+        pxi += wk.step_px; ch += wk.step_ch;
+        if (ch >= Cg) { ch -= Cg; ++pxi; }
+    }
+}
+
+// A pass's rows (ROW floats a pixel) leave the LDS tile s_g for dst (the pass's first float of the image): every row whole.
+// s_src[ch] is the channel map: which value of a pixel's row goes to channel ch, the row's zero for a channel no attribute
+// uses.  The first barrier waits for the lanes' rows (and, in the first pass, for the map), the second keeps the next pass
+// from overwriting a row that is still being read.
+// (Each kernel fills its map, `for (ch = tid; ch < Cg; ch += BLOCK) s_src[ch] = its source function of ch` -- Cg may exceed
+// BLOCK: a second turn -- and writes its row's zero itself: with that loop in a helper here, whether it took a lambda or the
+// function as a template argument, the compiler laid every kernel of the five units out differently.)
+template <int BLOCK, int ROW>
+__device__ __forceinline__ void tile_rows_out(const float* s_g, const unsigned char* s_src, float* __restrict__ dst, int npx, int Cg,
+                                              int tid, const TileWalk& wk)
+{
+    __syncthreads();
+    tile_for_each<BLOCK>(npx, Cg, tid, wk, [&](int e, int pxi, int ch) { dst[e] = s_g[pxi * ROW + s_src[ch]]; });
+    __syncthreads();
+}
+
+// The clamp of the output (P: a parameter struct with clamp, lo, hi) and where it passes the gradient g
+template <class P>
+__device__ __forceinline__ float clamp_out(const P& p, float pre)
+{
+    if (!p.clamp) return pre;
+    return pre < p.lo ? p.lo : (pre > p.hi ? p.hi : pre);   // a NaN stays NaN, as torch.clamp leaves it
+}
+
+template <class P>
+__device__ __forceinline__ float clamp_gate(const P& p, float pre, float g)
+{
+    return (!p.clamp || (pre >= p.lo && pre <= p.hi)) ? g : 0.f;   // closed at both edges; 0 at a NaN
+}
+
+// dirt_shade.hip: the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a
+// fixed order, one workgroup per value.  One copy for every unit: the others call the launcher.
+void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
+
+// ---- host (every G-buffer stage reports into dirt_last_error) -----------------------------------------------------------------
+
+// workgroups of `span` = BLOCK * ITER pixels for `pixels` pixels
+inline long long shade_blocks(long long pixels, int span) { return (pixels + span - 1) / span; }
+
+// the sizes a shader takes: blockIdx.y is the scene, 2^40 pixels keep every index inside a long long
+inline int shade_check_sizes(const char* who, long long scenes, long long pixels, int Cg)
+{
+    if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
+    if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
+    if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
+    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    return DIRT_OK;
+}
+
+// `count` attributes of a pixel, attribute a in channels off[a] .. off[a] + width[a] - 1 unless absent[a] (no such channels, or
+// a tensor of its own: off[a] is not read): each fits in the Cg channels and overlaps none before it
+inline int shade_check_attributes(const char* who, int Cg, int count, const int* off, const int* width, const bool* absent,
+                                  const char* const* names)
+{
+    for (int a = 0; a < count; ++a) {
+        if (absent[a]) continue;
+        if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
+        for (int b = 0; b < a; ++b)
+            if (!absent[b] && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
+                STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
+    }
+    return DIRT_OK;
+}
+
+inline int shade_check_clamp(const char* who, unsigned flags, float lo, float hi)
+{
+    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    return DIRT_OK;
+}
+
+// floats between two scenes' parameter blocks of NP floats: 0 = one block for every scene
+inline int shade_pstride(int param_scenes, int NP) { return param_scenes == 1 ? 0 : NP; }
+
+// the scratch of a backward pass: one row of NP partial sums per workgroup; 0 for sizes the entry points refuse
+inline size_t shade_scratch_bytes(long long scenes, long long pixels, int span, int NP)
+{
+    if (scenes < 0 || scenes > 65535 || pixels < 0 || pixels > (1ll << 40)) return 0;
+    return sizeof(float) * (size_t)scenes * (size_t)shade_blocks(pixels, span) * (size_t)NP;
+}
+
+// after the launch of a backward kernel on (blocks, scenes) workgroups: its launch error, then (grad_params: the parameter
+// block wants its gradient) the sum of the rows it left in scratch, then the status the entry point returns
+inline int shade_backward_finish(const char* who, const void* scratch, float* grad_params, long long scenes, long long blocks, int NP,
+                                 int param_scenes, hipStream_t s)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return stage_hip(set_last_error, who, e);
+    if (grad_params) {
+        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
+        shade_launch_reduce(static_cast<const float*>(scratch), grad_params, rows, NP, param_scenes, s);
+        e = hipGetLastError();
+    }
+    return stage_hip(set_last_error, who, e);
+}
+
+}  // namespace dirt

@@ -23,20 +23,22 @@
 // then per light {vector[3], colour[3], 0, 0}.  The light kinds (one bit per light), the two scalars of the material model,
 // the clamp and the flag are launch arguments.
 //
-// Kernels: the tiling of dirt_shade_sh.hip.  Forward one pixel per lane; a pixel's colours are three floats and its material
-// two floats `cstride` / `mstride` apart, which is channels of the G-buffer (stride Cg) as well as a tensor of their own, so
+// Kernels: the tiling, the clamp and the host checks of dirt_shade_common.h.  Forward one pixel per lane; a pixel's colours
+// are three floats and its material two floats `cstride` / `mstride` apart, which is channels of the G-buffer (stride Cg)
+// as well as a tensor of their own, so
 // the forward is one kernel for the four source combinations.  Backward four passes of 256 pixels per workgroup inside one
 // scene: the forward again, d gbuffer through an LDS tile so that every row leaves whole, the tensors' gradients by one dense
 // store per lane, the parameter sums in registers under compile-time indices (hence the template on the light count), then
 // wave_sum -> fold_waves_to_row -> one row per workgroup in caller scratch -> shade_launch_reduce in a fixed order.  No atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "dirt_stage.h"
+#include "dirt_shade_common.h"
 
 namespace dirt {
 
 constexpr int PBR_BLOCK = 256;     // lanes of a workgroup, pixels of one of its passes
 constexpr int PBR_ITER = 4;        // passes of a backward workgroup
+constexpr int PBR_SPAN = PBR_BLOCK * PBR_ITER;   // pixels of a backward workgroup
 constexpr int PBR_HEAD = DIRT_SHADE_PARAM_HEAD, PBR_LIGHT = DIRT_SHADE_PARAM_LIGHT;
 constexpr int PBR_ROW = 13;        // floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], d roughness, d metalness, dm, 0 (odd: no bank conflicts)
 constexpr int PBR_ZERO = 12;       // the row's zero
@@ -155,12 +157,6 @@ __device__ __forceinline__ void pbr_light(const float* __restrict__ lp, bool poi
     }
 }
 
-__device__ __forceinline__ float pbr_clamp(const ShadePbrParams& P, float pre)
-{
-    if (!P.clamp) return pre;
-    return pre < P.lo ? P.lo : (pre > P.hi ? P.hi : pre);   // a NaN stays NaN, as torch.clamp leaves it
-}
-
 // ---- forward: one pixel per lane; the parameters are wave-uniform (scalar loads), the loop over the lights is uniform
 __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrParams P)
 {
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrPa
     const float om = 1.f - px.m;
     float o[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) o[j] = pbr_clamp(P, lit[j] * px.m + prm[3 + j] * om);
+    for (int j = 0; j < 3; ++j) o[j] = clamp_out(P, lit[j] * px.m + prm[3 + j] * om);
     store3(P.out + pix * 3, o);
 }
 
@@ -213,9 +209,8 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
     float acc[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = 0.f;
-    // the walk of the copy-out loop: element e = tid + 256 step of the tile is channel e % Cg of pixel e / Cg
-    const int Cg = P.Cg, step_px = PBR_BLOCK / Cg, step_ch = PBR_BLOCK % Cg;
-    const int px0 = tid / Cg, ch0 = tid % Cg;
+    const int Cg = P.Cg;
+    const TileWalk walk = tile_walk<PBR_BLOCK>(Cg, tid);
     if constexpr (GBUF) {
         for (int ch = tid; ch < Cg; ch += PBR_BLOCK) s_src[ch] = (unsigned char)shade_pbr_source(P, ch);
         s_g[tid * PBR_ROW + PBR_ZERO] = 0.f;
@@ -248,7 +243,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const float pre = lit[j] * px.m + prm[3 + j] * om;
-                const float gpre = (!P.clamp || (pre >= P.lo && pre <= P.hi)) ? go[j] : 0.f;   // closed at both edges; 0 at a NaN
+                const float gpre = clamp_gate(P, pre, go[j]);
                 glit[j] = gpre * px.m;
                 gm += gpre * lit[j];
                 gmb += gpre * prm[3 + j];
@@ -356,18 +351,8 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                 r[9] = gr; r[10] = gmu; r[11] = gm;
             }
         }
-        if constexpr (GBUF) {
-            __syncthreads();
-            float* __restrict__ dst = P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg;
-            const int total = npx * Cg;
-            int pxi = px0, ch = ch0;
-            for (int e = tid; e < total; e += PBR_BLOCK) {
-                dst[e] = s_g[pxi * PBR_ROW + s_src[ch]];
-                pxi += step_px; ch += step_ch;
-                if (ch >= Cg) { ch -= Cg; ++pxi; }
-            }
-            __syncthreads();
-        }
+        if constexpr (GBUF)
+            tile_rows_out<PBR_BLOCK, PBR_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
     }
     if constexpr (PARAMS) {
         const int wave = tid >> 6, lane = tid & 63;
@@ -380,9 +365,6 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
         if (tid < NP) fold_waves_to_row<NP>(s_part, P.partial, tid);
     }
 }
-
-// dirt_shade.hip: the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added in a fixed order
-void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
 
 template <int NL>
 static void shade_pbr_launch_backward(const ShadePbrParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
@@ -399,18 +381,13 @@ extern "C" {
 
 static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
-static long long shade_pbr_blocks(long long pixels) { return (pixels + dirt::PBR_BLOCK * dirt::PBR_ITER - 1) / (dirt::PBR_BLOCK * dirt::PBR_ITER); }
-
-// what shade_sh_check of dirt_shade_sh.hip refuses, for this file's arguments; `colors` / `material`: whether they are tensors of their own
+// what this file's entry points refuse (the shared refusals: dirt_shade_common.h); `colors` / `material`: whether they are tensors of their own
 static int shade_pbr_check(const char* who, bool colors, bool material, long long scenes, long long pixels, int Cg, int color_stride,
                            int material_stride, int off_colors, int off_material, int off_normals, int off_positions, int off_mask,
                            int param_scenes, int lights, unsigned light_kinds, float min_roughness, float f0, float lo, float hi,
                            unsigned flags, dirt::ShadePbrParams& P)
 {
-    if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
-    if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
-    if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
-    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (int rc = dirt::shade_check_sizes(who, scenes, pixels, Cg)) return rc;
     if (colors && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
     if (material && material_stride < 2) STAGE_FAIL("%s: material_stride=%d, a pixel's material is 2 floats", who, material_stride);
     if (lights < 0 || lights > DIRT_SHADE_PBR_MAX_LIGHTS) STAGE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_PBR_MAX_LIGHTS);
@@ -421,21 +398,15 @@ static int shade_pbr_check(const char* who, bool colors, bool material, long lon
     const int off[5] = {off_colors, off_material, off_normals, off_positions, off_mask}, width[5] = {3, 2, 3, 3, 1};
     const bool absent[5] = {colors, material, false, false, off_mask == -1};
     const char* const names[5] = {"colors", "material", "normals", "positions", "mask"};
-    for (int a = 0; a < 5; ++a) {
-        if (absent[a]) continue;
-        if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
-        for (int b = 0; b < a; ++b)
-            if (!absent[b] && off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
-                STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
-    }
+    if (int rc = dirt::shade_check_attributes(who, Cg, 5, off, width, absent, names)) return rc;
     if (!(min_roughness > 0.f && min_roughness <= 1.f)) STAGE_FAIL("%s: min_roughness=%g is not in (0, 1]", who, min_roughness);
     if (!(f0 >= 0.f && f0 <= 1.f)) STAGE_FAIL("%s: dielectric_f0=%g is not in [0, 1]", who, f0);
-    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    if (int rc = dirt::shade_check_clamp(who, flags, lo, hi)) return rc;
     P.pixels = pixels; P.Cg = Cg; P.oc = colors ? -1 : off_colors; P.omat = material ? -1 : off_material;
     P.on = off_normals; P.op = off_positions; P.om = off_mask;
     P.cstride = colors ? color_stride : Cg; P.mstride = material ? material_stride : Cg;
     P.nl = lights; P.kinds = light_kinds;
-    P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights;
+    P.pstride = dirt::shade_pstride(param_scenes, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
     P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0;
     P.lo = lo; P.hi = hi; P.min_roughness = min_roughness; P.f0 = f0;
     return DIRT_OK;
@@ -443,8 +414,8 @@ static int shade_pbr_check(const char* who, bool colors, bool material, long lon
 
 size_t dirt_shade_pbr_scratch_bytes(long long scenes, long long pixels, int lights)
 {
-    if (scenes < 0 || scenes > 65535 || pixels < 0 || pixels > (1ll << 40) || lights < 0 || lights > DIRT_SHADE_PBR_MAX_LIGHTS) return 0;
-    return sizeof(float) * (size_t)scenes * (size_t)shade_pbr_blocks(pixels) * (size_t)(DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
+    if (lights < 0 || lights > DIRT_SHADE_PBR_MAX_LIGHTS) return 0;
+    return dirt::shade_scratch_bytes(scenes, pixels, dirt::PBR_SPAN, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
 }
 
 int dirt_shade_pbr_forward(const float* gbuffer, const float* colors, const float* material, const float* params, float* out,
@@ -491,7 +462,7 @@ int dirt_shade_pbr_backward(const float* gbuffer, const float* colors, const flo
                                  "dirt_shade_pbr_scratch_bytes");
         if (rc) return rc;
     }
-    const long long blocks = shade_pbr_blocks(pixels);
+    const long long blocks = dirt::shade_blocks(pixels, dirt::PBR_SPAN);
     if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
     P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.mat = material ? material : gbuffer + off_material;
     P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.gcol = grad_colors; P.gmat = grad_material;
@@ -506,15 +477,7 @@ int dirt_shade_pbr_backward(const float* gbuffer, const float* colors, const flo
     case 3: dirt::shade_pbr_launch_backward<3>(P, params_wanted, gbuf, grid, s); break;
     default: dirt::shade_pbr_launch_backward<4>(P, params_wanted, gbuf, grid, s); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
-    if (params_wanted) {
-        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
-        dirt::shade_launch_reduce(static_cast<const float*>(scratch), grad_params, rows, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights,
-                                  param_scenes, s);
-        e = hipGetLastError();
-    }
-    return dirt::stage_hip(report, who, e);
+    return dirt::shade_backward_finish(who, scratch, grad_params, scenes, blocks, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights, param_scenes, s);
 }
 
 }  // extern "C"

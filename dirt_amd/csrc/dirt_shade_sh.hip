@@ -16,8 +16,9 @@
 // The parameter block is [scenes or 1, 30] floats: L[k, j] at 3 k + j, then the background.  The three band scales, the clamp
 // and the flag are launch arguments.
 //
-// Kernels: the tiling of dirt_shade.hip.  Forward one pixel per lane; the colours are three floats `cstride` apart, which is
-// three channels of the G-buffer (cstride = Cg) as well as an image of their own, so the forward is one kernel.  Backward four
+// Kernels: the tiling, the clamp and the host checks of dirt_shade_common.h.  Forward one pixel per lane; the colours are
+// three floats `cstride` apart, which is three channels of the G-buffer (cstride = Cg) as well as an image of their own, so
+// the forward is one kernel.  Backward four
 // passes of 256 pixels per workgroup inside one scene: the forward again, d gbuffer through an LDS tile so that every row
 // leaves whole, the colours' gradient of the tensor path by one 12-byte store per lane, the 30 parameter sums in registers,
 // then wave_sum -> fold_waves_to_row -> one row per workgroup in caller scratch -> shade_launch_reduce in a fixed order.
@@ -25,12 +26,13 @@
 // occupancy the 30 sums set (DESIGN.md §7b has the table).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "dirt_stage.h"
+#include "dirt_shade_common.h"
 
 namespace dirt {
 
 constexpr int SH_BLOCK = 256;      // lanes of a workgroup, pixels of one of its passes
 constexpr int SH_ITER = 4;         // passes of a backward workgroup
+constexpr int SH_SPAN = SH_BLOCK * SH_ITER;   // pixels of a backward workgroup
 constexpr int SH_TERMS = 9;        // basis functions
 constexpr int SH_PARAMS = DIRT_SHADE_SH_PARAMS;
 constexpr int SH_ROW = 9;          // floats of a pixel's row in the LDS tile: dc[3], dn[3], dm, 0, and one of padding (odd: no bank conflicts)
@@ -100,12 +102,6 @@ __device__ __forceinline__ void sh_pixel(const ShadeShParams& P, const float* __
     }
 }
 
-__device__ __forceinline__ float sh_clamp(const ShadeShParams& P, float pre)
-{
-    if (!P.clamp) return pre;
-    return pre < P.lo ? P.lo : (pre > P.hi ? P.hi : pre);   // a NaN stays NaN, as torch.clamp leaves it
-}
-
 // ---- forward: one pixel per lane; the 30 parameters are wave-uniform (scalar loads)
 __global__ __launch_bounds__(SH_BLOCK) void shade_sh_forward_kernel(ShadeShParams P)
 {
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(SH_BLOCK) void shade_sh_forward_kernel(ShadeShParam
     const float om = 1.f - px.m;
     float o[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) o[j] = sh_clamp(P, (px.c[j] * px.E[j]) * px.m + prm[27 + j] * om);
+    for (int j = 0; j < 3; ++j) o[j] = clamp_out(P, (px.c[j] * px.E[j]) * px.m + prm[27 + j] * om);
     store3(P.out + pix * 3, o);
 }
 
@@ -149,9 +145,8 @@ __global__ __launch_bounds__(SH_BLOCK) void shade_sh_backward_kernel(ShadeShPara
     float acc[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = 0.f;
-    // the walk of the copy-out loop: element e = tid + 256 step of the tile is channel e % Cg of pixel e / Cg
-    const int Cg = P.Cg, step_px = SH_BLOCK / Cg, step_ch = SH_BLOCK % Cg;
-    const int px0 = tid / Cg, ch0 = tid % Cg;
+    const int Cg = P.Cg;
+    const TileWalk walk = tile_walk<SH_BLOCK>(Cg, tid);
     if constexpr (GBUF) {
         for (int ch = tid; ch < Cg; ch += SH_BLOCK) s_src[ch] = (unsigned char)shade_sh_source<TENSOR>(P, ch);
         s_g[tid * SH_ROW + SH_ZERO] = 0.f;
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(SH_BLOCK) void shade_sh_backward_kernel(ShadeShPara
             for (int j = 0; j < 3; ++j) {
                 const float lit = px.c[j] * px.E[j];
                 const float pre = lit * px.m + prm[27 + j] * om;
-                const float gpre = (!P.clamp || (pre >= P.lo && pre <= P.hi)) ? go[j] : 0.f;   // closed at both edges; 0 at a NaN
+                const float gpre = clamp_gate(P, pre, go[j]);
                 const float glit = gpre * px.m;
                 gm += gpre * lit;
                 gmb += gpre * prm[27 + j];
@@ -215,18 +210,8 @@ __global__ __launch_bounds__(SH_BLOCK) void shade_sh_backward_kernel(ShadeShPara
                 r[6] = gm;
             }
         }
-        if constexpr (GBUF) {
-            __syncthreads();
-            float* __restrict__ dst = P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg;
-            const int total = npx * Cg;
-            int pxi = px0, ch = ch0;
-            for (int e = tid; e < total; e += SH_BLOCK) {
-                dst[e] = s_g[pxi * SH_ROW + s_src[ch]];
-                pxi += step_px; ch += step_ch;
-                if (ch >= Cg) { ch -= Cg; ++pxi; }
-            }
-            __syncthreads();
-        }
+        if constexpr (GBUF)
+            tile_rows_out<SH_BLOCK, SH_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
     }
     if constexpr (PARAMS) {
         const int wave = tid >> 6, lane = tid & 63;
@@ -239,9 +224,6 @@ __global__ __launch_bounds__(SH_BLOCK) void shade_sh_backward_kernel(ShadeShPara
         if (tid < NP) fold_waves_to_row<NP>(s_part, P.partial, tid);
     }
 }
-
-// dirt_shade.hip: the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added in a fixed order
-void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
 
 template <bool TENSOR>
 static void shade_sh_launch_backward(const ShadeShParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
@@ -258,34 +240,24 @@ extern "C" {
 
 static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
-static long long shade_sh_blocks(long long pixels) { return (pixels + dirt::SH_BLOCK * dirt::SH_ITER - 1) / (dirt::SH_BLOCK * dirt::SH_ITER); }
-
-// what shade_check of dirt_shade.hip refuses, for this file's arguments; `colors`: whether the colours are a tensor of their own
+// what this file's entry points refuse (the shared refusals: dirt_shade_common.h); `colors`: whether the colours are a tensor of their own
 static int shade_sh_check(const char* who, bool colors, long long scenes, long long pixels, int Cg, int color_stride, int off_colors,
                           int off_normals, int off_mask, int param_scenes, float s0, float s1, float s2, float lo, float hi, unsigned flags,
                           dirt::ShadeShParams& P)
 {
-    if (scenes < 0 || pixels < 0) STAGE_FAIL("%s: negative sizes (scenes=%lld pixels=%lld)", who, scenes, pixels);
-    if (scenes > 65535) STAGE_FAIL("%s: %lld scenes, at most 65535", who, scenes);
-    if (pixels > (1ll << 40)) STAGE_FAIL("%s: %lld pixels per scene, at most 2^40", who, pixels);
-    if (Cg < 1 || Cg > DIRT_SHADE_MAX_CHANNELS) STAGE_FAIL("%s: %d G-buffer channels, 1..%d", who, Cg, DIRT_SHADE_MAX_CHANNELS);
+    if (int rc = dirt::shade_check_sizes(who, scenes, pixels, Cg)) return rc;
     if (colors && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
     if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
     if (flags & ~(DIRT_SHADE_CLAMP | DIRT_SHADE_SH_NORMALIZE)) STAGE_FAIL("%s: unknown flags 0x%x", who, flags);
     // with a colour tensor the G-buffer has no colour channels (off_colors is not read): three channels of normals are the smallest one
     const int off[3] = {off_colors, off_normals, off_mask}, width[3] = {3, 3, 1};
+    const bool absent[3] = {colors, false, off_mask == -1};
     const char* const names[3] = {"colors", "normals", "mask"};
-    for (int a = colors ? 1 : 0; a < 3; ++a) {
-        if (off[a] == -1 && a == 2) continue;
-        if (off[a] < 0 || off[a] + width[a] > Cg) STAGE_FAIL("%s: %s at channel %d does not fit in %d channels", who, names[a], off[a], Cg);
-        for (int b = colors ? 1 : 0; b < a; ++b)
-            if (off[a] < off[b] + width[b] && off[b] < off[a] + width[a])
-                STAGE_FAIL("%s: %s (channel %d) overlaps %s (channel %d)", who, names[a], off[a], names[b], off[b]);
-    }
-    if ((flags & DIRT_SHADE_CLAMP) && !(lo <= hi)) STAGE_FAIL("%s: clamp bounds lo=%g > hi=%g", who, lo, hi);
+    if (int rc = dirt::shade_check_attributes(who, Cg, 3, off, width, absent, names)) return rc;
+    if (int rc = dirt::shade_check_clamp(who, flags, lo, hi)) return rc;
     P.pixels = pixels; P.Cg = Cg; P.oc = colors ? -1 : off_colors; P.on = off_normals; P.om = off_mask;
     P.cstride = colors ? color_stride : Cg;
-    P.pstride = param_scenes == 1 ? 0 : DIRT_SHADE_SH_PARAMS;
+    P.pstride = dirt::shade_pstride(param_scenes, DIRT_SHADE_SH_PARAMS);
     P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0; P.normalize = (flags & DIRT_SHADE_SH_NORMALIZE) ? 1 : 0;
     P.lo = lo; P.hi = hi; P.s0 = s0; P.s1 = s1; P.s2 = s2;
     return DIRT_OK;
@@ -293,8 +265,7 @@ static int shade_sh_check(const char* who, bool colors, long long scenes, long l
 
 size_t dirt_shade_sh_scratch_bytes(long long scenes, long long pixels)
 {
-    if (scenes < 0 || scenes > 65535 || pixels < 0 || pixels > (1ll << 40)) return 0;
-    return sizeof(float) * (size_t)scenes * (size_t)shade_sh_blocks(pixels) * (size_t)DIRT_SHADE_SH_PARAMS;
+    return dirt::shade_scratch_bytes(scenes, pixels, dirt::SH_SPAN, DIRT_SHADE_SH_PARAMS);
 }
 
 int dirt_shade_sh_forward(const float* gbuffer, const float* colors, const float* params, float* out, long long scenes, long long pixels,
@@ -332,7 +303,7 @@ int dirt_shade_sh_backward(const float* gbuffer, const float* colors, const floa
         rc = dirt::check_scratch(report, who, scratch, scratch_bytes, dirt_shade_sh_scratch_bytes(scenes, pixels), "dirt_shade_sh_scratch_bytes");
         if (rc) return rc;
     }
-    const long long blocks = shade_sh_blocks(pixels);
+    const long long blocks = dirt::shade_blocks(pixels, dirt::SH_SPAN);
     if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
     P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.gcol = grad_colors;
     P.partial = static_cast<float*>(scratch);
@@ -341,14 +312,7 @@ int dirt_shade_sh_backward(const float* gbuffer, const float* colors, const floa
     const bool params_wanted = grad_params != nullptr, gbuf = grad_gbuffer != nullptr;
     if (colors) dirt::shade_sh_launch_backward<true>(P, params_wanted, gbuf, grid, s);
     else dirt::shade_sh_launch_backward<false>(P, params_wanted, gbuf, grid, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dirt::stage_hip(report, who, e);
-    if (params_wanted) {
-        const long long rows = param_scenes == 1 ? scenes * blocks : blocks;
-        dirt::shade_launch_reduce(static_cast<const float*>(scratch), grad_params, rows, DIRT_SHADE_SH_PARAMS, param_scenes, s);
-        e = hipGetLastError();
-    }
-    return dirt::stage_hip(report, who, e);
+    return dirt::shade_backward_finish(who, scratch, grad_params, scenes, blocks, DIRT_SHADE_SH_PARAMS, param_scenes, s);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ as one HIP kernel forward and one backward (dirt_shade.hip; specification in DES
 `colors` may also be a tensor [..., 3] beside the G-buffer -- the output of `texture.sample_texture_uv`, of a network -- which
 the same kernels read in place of the three channels and whose gradient they write (examples/textured_fused.py).
 """
+import math
 import numbers
 
 import torch
@@ -75,6 +76,35 @@ def _value(x, width, name, device, batch):
     if len(vals) != width:
         raise ValueError('%s must be %d numbers, got %d' % (name, width, len(vals)))
     return vals
+
+
+def _gbuffer_sizes(gbuffer, who):
+    """The head of every entry point (`who`): refuses what is no G-buffer by its shape, -> (the G-buffer as a contiguous float32
+    tensor -- itself where it is one --, scenes, pixels of a scene, channels)."""
+    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
+        raise ValueError('%s expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (who, tuple(getattr(gbuffer, 'shape', ())),))
+    batched = gbuffer.dim() == 4
+    scenes = int(gbuffer.shape[0]) if batched else 1
+    pixels = math.prod(gbuffer.shape[1 if batched else 0:-1]) if scenes else 0
+    return gbuffer.to(torch.float32).contiguous(), scenes, pixels, int(gbuffer.shape[-1])
+
+
+def _param_head(ambient, background, camera_position, dev, batch):
+    """The head of a [1 or B, 9 + 8 lights] parameter block as slots (first slot, `_value`): ambient, background, camera."""
+    return [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
+            (6, _value(camera_position, 3, 'camera_position', dev, batch))]
+
+
+def _split_slots(width, slots):
+    """The slots of a parameter block of `width` floats -> (its constant row: the python numbers, zeros elsewhere,
+    [(first slot, tensor [1 or B, width])]: what `_splice_block` splices into it)."""
+    const, tensors = [0.] * width, []
+    for start, v in slots:
+        if isinstance(v, list):
+            const[start:start + len(v)] = v
+        else:
+            tensors.append((start, v))
+    return const, tensors
 
 
 class _ShadeGBuffer(torch.autograd.Function):
@@ -148,18 +178,12 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
     each what the function of the same name in `dirt_amd.lighting` returns with vertex_colors = vertex_reflectivities = c.
     Gradients are those of torch's autograd for that composition, including at the kinks (max(x, 0) and clamp pass the
     gradient at their edges, abs gives 0 at 0).  A shininess below 1 at a zero cosine (0 * inf in torch) is not defined."""
-    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
-        raise ValueError('shade_gbuffer expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shade_gbuffer')
     _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer')
     lights = list(lights)
     offsets, kinds, sided, lo, hi, flags, const, tensors = _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
                                                                             camera_position, background, clamp)
-    dev, cg, batch = gbuffer.device, int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
-    block = _splice_block(dev, const, tensors)
-
-    g = gbuffer.to(torch.float32).contiguous()
-    scenes = batch if batch is not None else 1
-    pixels = g.numel() // (cg * scenes) if scenes else 0
+    block = _splice_block(gbuffer.device, const, tensors)
     meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
     return _ShadeGBuffer.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
 
@@ -250,8 +274,7 @@ def _light_block(lights, positions, ambient, camera_position, background, dev, b
     """The parameter block of `shade_gbuffer` -> (light kinds, sidedness, its constant row, [(first slot, tensor [1 or B, width])])."""
     # the parameter block: [1 or B, 9 + 8 lights]; python numbers go into a cached constant row, tensors are spliced in with
     # one torch.cat whose autograd hands the block's gradient back to them
-    slots = [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
-             (6, _value(camera_position if camera_position is not None else (0., 0., 0.), 3, 'camera_position', dev, batch))]
+    slots = _param_head(ambient, background, camera_position if camera_position is not None else (0., 0., 0.), dev, batch)
     kinds = sided = 0
     for l, rec in enumerate(lights):
         if not isinstance(rec, (tuple, list)) or not rec or rec[0] not in _KINDS:
@@ -270,15 +293,7 @@ def _light_block(lights, positions, ambient, camera_position, background, dev, b
             slots.append((base + 6, _value(rec[3], 1, 'light %d shininess' % l, dev, batch)))
         kinds |= _KINDS[kind] << (2 * l)
         sided |= (1 if rec[-1] else 0) << l
-    width = _lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights)
-    const = [0.] * width
-    tensors = []
-    for start, v in slots:
-        if isinstance(v, list):
-            const[start:start + len(v)] = v
-        else:
-            tensors.append((start, v))
-    return kinds, sided, const, tensors
+    return (kinds, sided) + _split_slots(_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights), slots)
 
 
 # ---- spherical-harmonic lighting (dirt_shade_sh.hip)
@@ -338,15 +353,11 @@ def shade_gbuffer_sh(gbuffer, coefficients, *, colors, normals, mask=None, backg
 
     Returns [..., 3]:  clamp(c * E * m + background * (1 - m), lo, hi)  with  E_j = sum_k band_scale[band(k)] L[k, j] Y_k(n).
     Gradients are those of torch's autograd for that composition (the clamp passes the gradient at its edges)."""
-    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
-        raise ValueError('shade_gbuffer_sh expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shade_gbuffer_sh')
     _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_sh')
     offsets, scale, lo, hi, flags, const, tensors = _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background, clamp,
                                                                         normalize, band_scale)
     block = _splice_block(gbuffer.device, const, tensors)
-    g = gbuffer.to(torch.float32).contiguous()
-    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
-    pixels = g.numel() // (cg * scenes) if scenes else 0
     meta = (scenes, pixels, cg, tuple(offsets), scale, lo, hi, flags)
     return _ShadeGBufferSH.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
 
@@ -378,14 +389,8 @@ def _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background
     lo, hi = _clamp_bounds(clamp)
     flags = (_lib.SHADE_CLAMP if clamp is not None else 0) | (_lib.SHADE_SH_NORMALIZE if normalize else 0)
     # the parameter block: [1 or B, 30]; bands the table does not have stay zeros of the constant row
-    const = [0.] * _lib.SHADE_SH_PARAMS
-    tensors = [(0, coefficients.to(torch.float32).reshape(-1, 3 * shape[-2]))]
-    bg = _value(background, 3, 'background', dev, batch)
-    if isinstance(bg, list):
-        const[3 * _SH_TERMS:] = bg
-    else:
-        tensors.append((3 * _SH_TERMS, bg))
-    return offsets, scale, lo, hi, flags, const, tensors
+    slots = [(0, coefficients.to(torch.float32).reshape(-1, 3 * shape[-2])), (3 * _SH_TERMS, _value(background, 3, 'background', dev, batch))]
+    return (offsets, scale, lo, hi, flags) + _split_slots(_lib.SHADE_SH_PARAMS, slots)
 
 
 # ---- Cook-Torrance metallic-roughness lighting (dirt_shade_pbr.hip)
@@ -467,17 +472,13 @@ def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, 
     gradient at their edges, the norm of a zero vector has gradient 0).  A zero normal makes the distribution term a2 / 0 and
     the pixel inf * 0 = NaN whatever its mask, as in `lighting.cook_torrance`: give the uncovered pixels of a deferred renderer
     a unit normal (examples/fit_material_fused.py::background_attributes)."""
-    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
-        raise ValueError('shade_gbuffer_pbr expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shade_gbuffer_pbr')
     _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_pbr')
     lights = list(lights)
     offsets, kinds, scalars, lo, hi, flags, const, tensors = _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask,
                                                                                    ambient, camera_position, background, clamp, min_roughness,
                                                                                    dielectric_f0)
     block = _splice_block(gbuffer.device, const, tensors)
-    g = gbuffer.to(torch.float32).contiguous()
-    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
-    pixels = g.numel() // (cg * scenes) if scenes else 0
     meta = (scenes, pixels, cg, tuple(offsets), len(lights), kinds, scalars, lo, hi, flags)
     as_input = lambda x: x.to(torch.float32) if isinstance(x, torch.Tensor) else None   # noqa: E731
     return _ShadeGBufferPBR.apply(g, block, as_input(colors), as_input(material), meta)
@@ -507,8 +508,7 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
     lo, hi = _clamp_bounds(clamp)
     flags = _lib.SHADE_CLAMP if clamp is not None else 0
     # the parameter block: [1 or B, 9 + 8 lights] in the layout of `_light_block`
-    slots = [(0, _value(ambient, 3, 'ambient', dev, batch)), (3, _value(background, 3, 'background', dev, batch)),
-             (6, _value(camera_position, 3, 'camera_position', dev, batch))]
+    slots = _param_head(ambient, background, camera_position, dev, batch)
     kinds = 0
     for l, rec in enumerate(lights):
         if not isinstance(rec, (tuple, list)) or not rec or rec[0] not in _PBR_KINDS:
@@ -519,14 +519,7 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
         slots.append((base, _value(rec[1], 3, 'light %d %s' % (l, 'position' if rec[0] == 'point' else 'direction'), dev, batch)))
         slots.append((base + 3, _value(rec[2], 3, 'light %d color' % l, dev, batch)))
         kinds |= _PBR_KINDS[rec[0]] << l
-    const = [0.] * (_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights))
-    tensors = []
-    for start, v in slots:
-        if isinstance(v, list):
-            const[start:start + len(v)] = v
-        else:
-            tensors.append((start, v))
-    return offsets, kinds, tuple(scalars), lo, hi, flags, const, tensors
+    return (offsets, kinds, tuple(scalars), lo, hi, flags) + _split_slots(_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights), slots)
 
 
 # ---- tangent-space normal mapping (dirt_normal_map.hip)
@@ -581,13 +574,9 @@ def perturb_normals(gbuffer, normal_map, *, normals, tangents, strength=1.0, enc
     its normal and passes the incoming gradient to it alone.  Gradients are those of torch's autograd for
     `lighting.perturb_normals`: to the normal, tangent and handedness channels of the G-buffer (the other channels pass
     theirs through) and to the normal map (dense [..., 3])."""
-    if not isinstance(gbuffer, torch.Tensor) or gbuffer.dim() not in (2, 3, 4):
-        raise ValueError('perturb_normals expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got %s' % (tuple(getattr(gbuffer, 'shape', ())),))
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'perturb_normals')
     offsets, strength, flags = _check_normal_map_arguments(gbuffer, normal_map, normals, tangents, strength, encoded)
     _stage.require_gpu(gbuffer, 'dirt_amd.shading.perturb_normals')
-    g = gbuffer.to(torch.float32).contiguous()
-    cg, scenes = int(gbuffer.shape[-1]), int(gbuffer.shape[0]) if gbuffer.dim() == 4 else 1
-    pixels = g.numel() // (cg * scenes) if scenes else 0
     return _PerturbNormals.apply(g, normal_map.to(torch.float32), (scenes, pixels, cg, tuple(offsets), strength, flags))
 
 

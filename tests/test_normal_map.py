@@ -108,7 +108,9 @@ MESHES = {
 PIXELS = dict(
     {'flat': dict(seed=7100), 'decoded': dict(seed=7101, encoded=False), 'strength0': dict(seed=7102, strength=0.),
      'strength2': dict(seed=7103, strength=2.)},
-    **{name: dict(seed=7110 + i, layout=name, n=FLAT if LAYOUTS[name][0] < 255 else NM_BLOCK + 3) for i, name in enumerate(LAYOUTS)})
+    **{name: dict(seed=7110 + i, layout=name, n=FLAT if LAYOUTS[name][0] < 255 else NM_BLOCK + 3) for i, name in enumerate(LAYOUTS)},
+    # a pass of one pixel, a second pass of one pixel, a second workgroup of one pixel
+    **{'px%d' % n: dict(seed=7120 + i, layout='c11', n=n) for i, n in enumerate((1, NM_BLOCK + 1, SPAN + 1))})
 _CASES = {}
 
 

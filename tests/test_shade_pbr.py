@@ -731,20 +731,20 @@ def _abi(lib, dev, case, n, guard=7):
 @pytest.mark.parametrize('path', ['channels', 'tensors'])
 def test_the_c_abi_writes_inside_its_outputs(gpu, lib, path, n):
     """Guard values around out, grad_gbuffer, grad_colors, grad_material, grad_params (and the scratch) stay; every element
-    inside is written.  At the whole frame the results are the wrapper's, bit for bit."""
+    inside is written.  The results are the wrapper's on the whole frame (which test_every_backward_instantiation holds against
+    the restatement), bit for bit: all of them at the whole frame, the first n pixels' at a shorter one (a pass of one pixel, a
+    partial and a full pass, a second pass of one pixel), where a pixel's values do not depend on how many follow it."""
     case, ref = case_of('pattern_' + path)
     out, gg, gc, gm, gp = _abi(lib, gpu, case, n)
+    got = shade(case, gpu)
+    assert torch.equal(out, got['out'][:n]) and torch.equal(gg, got['d_gbuffer'][:n])
+    assert (gc is None or torch.equal(gc, got['d_colors'][:n])) and (gm is None or torch.equal(gm, got['d_material'][:n]))
     if n == case.n:
-        got = shade(case, gpu)
-        assert torch.equal(out, got['out']) and torch.equal(gg, got['d_gbuffer'])
-        assert (gc is None or torch.equal(gc, got['d_colors'])) and (gm is None or torch.equal(gm, got['d_material']))
         assert torch.equal(gp[0:3], got['d_params']['ambient']) and torch.equal(gp[3:6], got['d_params']['background'])
         assert torch.equal(gp[6:9], got['d_params']['camera_position'])
         for i in range(len(case.kinds)):
             assert torch.equal(gp[9 + 8 * i:12 + 8 * i], got['d_params']['light%d.vector' % i])
             assert torch.equal(gp[12 + 8 * i:15 + 8 * i], got['d_params']['light%d.color' % i]) and not bool(gp[15 + 8 * i:17 + 8 * i].any())
-    else:
-        assert torch.equal(out, shade(case, gpu, (False, False, False, False))['out'][:n])
 
 
 KINK_LAYOUT = dict(mask=0, colors=1, normals=4, positions=7, material=10)

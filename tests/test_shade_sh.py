@@ -598,15 +598,15 @@ def _abi(lib, dev, case, n, guard=7):
 @pytest.mark.parametrize('path', ['channel', 'tensor'])
 def test_the_c_abi_writes_inside_its_outputs(gpu, lib, path, n):
     """Guard values around out, grad_gbuffer, grad_colors, grad_params (and the scratch) stay; every element inside is written.
-    At the whole frame the results are the wrapper's, bit for bit."""
+    The results are the wrapper's on the whole frame (which test_every_backward_instantiation holds against the restatement), bit
+    for bit: all of them at the whole frame, the first n pixels' at a shorter one (a pass of one pixel, a partial and a full
+    pass, a second pass of one pixel), where a pixel's values do not depend on how many follow it."""
     case, ref = case_of('pattern_' + path)
     out, gg, gc, gp = _abi(lib, gpu, case, n)
+    got = shade(case, gpu)
+    assert torch.equal(out, got['out'][:n]) and torch.equal(gg, got['d_gbuffer'][:n]) and (gc is None or torch.equal(gc, got['d_colors'][:n]))
     if n == case.n:
-        got = shade(case, gpu)
-        assert torch.equal(out, got['out']) and torch.equal(gg, got['d_gbuffer']) and (gc is None or torch.equal(gc, got['d_colors']))
         assert torch.equal(gp[:27].reshape(9, 3), got['d_coefficients']) and torch.equal(gp[27:], got['d_background'])
-    else:
-        assert torch.equal(out, shade(case, gpu, (False, False, False))['out'][:n])
 
 
 def _pixels(dev, rows, L, kw, go=None):
