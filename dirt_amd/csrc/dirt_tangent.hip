@@ -6,8 +6,10 @@
 // float64), per scene, with the uvs [V, 2] shared by the scenes:
 //
 //     per face (i0, i1, i2):  e1 = p1 - p0, e2 = p2 - p0     (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0
-//         det = du1 dv2 - du2 dv1,  s = sign(det)  (0 for a degenerate uv triangle: the face contributes nothing)
+//         det = du1 dv2 - du2 dv1,  s = sign(det)
 //         t_f = (s dv2) e1 - (s dv1) e2               b_f = (s du1) e2 - (s du2) e1
+//         a face is LIVE iff det is finite and non-zero; a dead face (a degenerate uv triangle, a NaN or Inf uv) has the four
+//         coefficients s dv2, s dv1, s du1, s du2 exactly 0, whatever its uvs hold: it adds nothing to T, Bt or any gradient
 //     per vertex:  T, Bt = the sums of t_f, b_f over the (face, corner) pairs that name the vertex, in list order
 //         x = T - n (n . T)       t = x / |x| where x . x > 0, else 0       w = -1 where cross(n, t) . Bt < 0, else +1
 //         out = (t, w)
@@ -63,8 +65,10 @@ __device__ __forceinline__ void face_uv(const TangentParams& P, int f, FaceUv& q
                  u2 = *reinterpret_cast<const Float2*>(P.uv + (size_t)q.i[2] * 2);
     const float du1 = u1.x - u0.x, dv1 = u1.y - u0.y, du2 = u2.x - u0.x, dv2 = u2.y - u0.y;
     const float det = du1 * dv2 - du2 * dv1;
-    const float s = det > 0.f ? 1.f : (det < 0.f ? -1.f : 0.f);   // sign(det); a NaN counts as degenerate
-    q.a = s * dv2; q.b = s * dv1; q.c = s * du1; q.d = s * du2;
+    const bool live = fabsf(det) < INFINITY && det != 0.f;        // finite and non-zero (a NaN fails the first comparison)
+    const float s = det > 0.f ? 1.f : -1.f;                       // sign(det) of a live face
+    q.a = live ? s * dv2 : 0.f; q.b = live ? s * dv1 : 0.f;       // selects, not products: 0 * NaN is NaN
+    q.c = live ? s * du1 : 0.f; q.d = live ? s * du2 : 0.f;
 }
 
 // T (and, BITANGENT, Bt) of the vertex whose list is entries [beg, end), summed in list order

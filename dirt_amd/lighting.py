@@ -251,11 +251,13 @@ def vertex_tangents(vertices, normals, uvs, faces):
     """Per-vertex tangent frames from the uv parametrisation: [*, V, 3|4], [*, V, 3], [V, 2], [F, 3] -> [*, V, 4], the unit
     tangent (the direction of increasing u, orthogonal to the normal) and the handedness w = -1 or +1 of the bitangent
     w * cross(n, t) against the direction of increasing v.  The normals are taken as given (unit, as `vertex_normals` returns
-    them); the uvs are shared by the scenes and constant (no gradient).  Per face, with s = sign(det) (0 for a degenerate uv
-    triangle, which contributes nothing):
+    them); the uvs are shared by the scenes and constant (no gradient).  Per face, with s = sign(det):
 
         e1 = p1 - p0, e2 = p2 - p0      (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0      det = du1 dv2 - du2 dv1
         t_f = s (dv2 e1 - dv1 e2)       b_f = s (du1 e2 - du2 e1)
+
+    A face is live iff its det is finite and non-zero.  A dead face -- a degenerate uv triangle, a NaN or Inf uv -- has the
+    four coefficients s dv2, s dv1, s du1, s du2 exactly 0: it adds nothing to T, Bt or any gradient, whatever its uvs hold.
 
     Per vertex, T and Bt the sums of t_f and b_f over the faces that name it (once per naming corner):
 
@@ -270,9 +272,12 @@ def vertex_tangents(vertices, normals, uvs, faces):
     e1, e2 = p1 - p0, p2 - p0
     d1, d2 = uv[faces[:, 1]] - uv[faces[:, 0]], uv[faces[:, 2]] - uv[faces[:, 0]]
     du1, dv1, du2, dv2 = d1[:, 0:1], d1[:, 1:2], d2[:, 0:1], d2[:, 1:2]
-    s = torch.sign(du1 * dv2 - du2 * dv1)
-    t_f = (s * dv2) * e1 - (s * dv1) * e2
-    b_f = (s * du1) * e2 - (s * du2) * e1
+    det = du1 * dv2 - du2 * dv1
+    live = torch.isfinite(det) & (det != 0)
+    s, zero = torch.sign(det), torch.zeros_like(det)
+    a, b, c, d = (torch.where(live, s * x, zero) for x in (dv2, dv1, du1, du2))     # (a select: 0 * NaN would be NaN)
+    t_f = a * e1 - b * e2
+    b_f = c * e2 - d * e1
     T, Bt = torch.zeros_like(p), torch.zeros_like(p)
     for k in range(3):
         T = T.index_add(-2, faces[:, k], t_f)

@@ -90,12 +90,14 @@ def _f64(x):
 
 def _face_coefficients(uvs, faces):
     uv = _f64(uvs)
-    d1, d2 = uv[faces[:, 1]] - uv[faces[:, 0]], uv[faces[:, 2]] - uv[faces[:, 0]]
-    du1, dv1, du2, dv2 = d1[:, 0:1], d1[:, 1:2], d2[:, 0:1], d2[:, 1:2]
-    det = du1 * dv2 - du2 * dv1
-    s = np.sign(det)
-    share = np.abs(det) / np.maximum(np.abs(du1 * dv2) + np.abs(du2 * dv1), 1e-300)
-    return s * dv2, s * dv1, s * du1, s * du2, share[:, 0]
+    with np.errstate(invalid='ignore'):
+        d1, d2 = uv[faces[:, 1]] - uv[faces[:, 0]], uv[faces[:, 2]] - uv[faces[:, 0]]
+        du1, dv1, du2, dv2 = d1[:, 0:1], d1[:, 1:2], d2[:, 0:1], d2[:, 1:2]
+        det = du1 * dv2 - du2 * dv1
+        live = np.isfinite(det) & (det != 0)     # a dead face: the four coefficients exactly 0, whatever its uvs hold
+        a, b, c, d = (np.where(live, np.sign(det) * x, 0.) for x in (dv2, dv1, du1, du2))
+        share = np.where(live, np.abs(det) / np.maximum(np.abs(du1 * dv2) + np.abs(du2 * dv1), 1e-300), 0.)
+    return a, b, c, d, share[:, 0]
 
 
 def tangents(vertices, normals, uvs, faces, grad_out=None):
@@ -303,7 +305,13 @@ def draw_mesh(rng, xy, faces, components=3, jitter=0.05, max_rejected=0.05):
         uv[rows] = xy[rows] @ rot + 0.5 + rng.normal(0., 0.4 * jitter * scale, (k, 2))
         n[rows] = _unit(np.array([0., 0., 1.]) + rng.normal(0., 0.3, (k, 3)))
 
-    fill(np.arange(V))
+    return v, n, uv, _redraw(fill, v, n, uv, faces, max_rejected)
+
+
+def _redraw(fill, v, n, uv, faces, max_rejected):
+    """The reject-and-redraw loop of the mesh draws: `fill(rows)` draws those rows of v, n, uv in place; the vertices of a face
+    or with a frame too close to a discontinuity (MARGIN, MIN_SIN) are drawn again.  -> the share rejected from the first draw"""
+    fill(np.arange(len(v)))
     share = None
     for _ in range(20):
         r = tangents(v, n, uv, faces)
@@ -313,9 +321,47 @@ def draw_mesh(rng, xy, faces, components=3, jitter=0.05, max_rejected=0.05):
             share = float(bad.mean())
             assert share < max_rejected, 'share of redrawn vertices %.3f' % share
         if not bad.any():
-            return v, n, uv, share
+            return share
         fill(np.nonzero(bad)[0])
     raise AssertionError('could not draw a mesh off the discontinuities')
+
+
+def torus_mesh(nu, nv, major=1., minor=0.4):
+    """A torus as an (nu + 1) x (nv + 1) grid with both seams split (the last row and column repeat the first in space, with
+    uvs of their own): vertex (i, j) has uv = (i / nu, j / nv), u around the axis and v around the tube; two faces per cell,
+    so a vertex has 1 to 6 faces.  d p / d u x d p / d v points out of the tube: the handedness is +1 everywhere.
+    -> (positions [V, 3], unit normals out of the tube [V, 3], uvs [V, 2], faces [2 nu nv, 3])"""
+    i, j = (x.reshape(-1) for x in np.meshgrid(np.arange(nu + 1), np.arange(nv + 1), indexing='ij'))
+    theta, phi = 2. * np.pi * i / nu, 2. * np.pi * j / nv
+    nrm = np.stack([np.cos(phi) * np.cos(theta), np.cos(phi) * np.sin(theta), np.sin(phi)], 1)
+    pos = major * np.stack([np.cos(theta), np.sin(theta), np.zeros_like(theta)], 1) + minor * nrm
+    ci, cj = (x.reshape(-1) for x in np.meshgrid(np.arange(nu), np.arange(nv), indexing='ij'))
+    at = lambda a, b: a * (nv + 1) + b   # noqa: E731
+    faces = np.concatenate([np.stack([at(ci, cj), at(ci + 1, cj), at(ci + 1, cj + 1)], 1), np.stack([at(ci, cj), at(ci + 1, cj + 1), at(ci, cj + 1)], 1)])
+    return pos, nrm, np.stack([i / nu, j / nv], 1), faces.astype(np.int32)
+
+
+def draw_torus(rng, nu, nv, mirrored=False, components=3, max_rejected=0.05):
+    """`torus_mesh` with jitter, through the reject-and-redraw loop of the sheets: positions by 5 % of the shortest edge, normals
+    as the sheets' (a standard deviation of 0.3 per component, then unit), uvs by 2 % of a cell; mirrored: u -> 1 - u before the
+    jitter, which turns the handedness to -1 everywhere.  -> (vertices [V, components], normals, uvs, faces, share), float32"""
+    pos, nrm, uv0, faces = torus_mesh(nu, nv)
+    if mirrored:
+        uv0[:, 0] = 1. - uv0[:, 0]
+    edges = np.concatenate([pos[faces[:, a]] - pos[faces[:, b]] for a, b in ((0, 1), (1, 2), (2, 0))])
+    sigma = 0.05 * float(np.linalg.norm(edges, axis=1).min())
+    V = len(pos)
+    v, n, uv = np.zeros((V, components), np.float32), np.zeros((V, 3), np.float32), np.zeros((V, 2), np.float32)
+
+    def fill(rows):
+        k = len(rows)
+        v[rows, :3] = pos[rows] + rng.normal(0., sigma, (k, 3))
+        if components == 4:
+            v[rows, 3] = rng.uniform(0.5, 2., k)
+        uv[rows] = uv0[rows] + rng.normal(0., 0.02, (k, 2)) / np.array([nu, nv])
+        n[rows] = _unit(nrm[rows] + rng.normal(0., 0.3, (k, 3)))
+
+    return v, n, uv, faces, _redraw(fill, v, n, uv, faces, max_rejected)
 
 
 def random_pixels(rng, n, cg, on, ot, encoded=True):

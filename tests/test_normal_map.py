@@ -23,8 +23,10 @@ from tests import normal_map_reference as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# worst |f32 - ref64| / mass of the float32 composition on tolerance_cases(), per kind of result (python -m tests.normal_map_reference)
-F32 = {'tangents': 8.76e-8, 'd_vertices': 5.32e-8, 'd_normals': 1.49e-7, 'out': 3.39e-8, 'd_gbuffer': 3.98e-8, 'd_normal_map': 2.22e-8}
+# worst |f32 - ref64| / mass of the float32 composition on tolerance_cases(), per kind of result (python -m tests.normal_map_reference),
+# rounded up.  Measured again with the tori among the cases: 8.759e-8, 5.310e-8, 1.487e-7, 3.384e-8, 3.975e-8, 2.218e-8, the same
+# figures, set by the strips (the tori alone: 7.12e-8, 4.50e-8, 6.53e-8)
+F32 ={'tangents': 8.76e-8, 'd_vertices': 5.32e-8, 'd_normals': 1.49e-7, 'out': 3.39e-8, 'd_gbuffer': 3.98e-8, 'd_normal_map': 2.22e-8}
 KERNEL = 4     # the kernels' allowance over the float32 composition
 
 
@@ -47,9 +49,9 @@ LAYOUTS = {   # name -> (Cg, first normal channel, first tangent channel); every
 
 
 class Mesh:
-    """One mesh comparison: `scenes` draws of a sheet over a strip, a fan or the cube, grad_out [.., V, 4]."""
+    """One mesh comparison: `scenes` draws of a sheet over a strip or a fan, of a torus or of the cube, grad_out [.., V, 4]."""
 
-    def __init__(self, seed, kind, size=0, components=3, scenes=None):
+    def __init__(self, seed, kind, size=0, components=3, scenes=None, mirrored=False):
         rng = np.random.default_rng(seed)
         self.seed, self.components, self.scenes = seed, components, scenes
         if kind == 'cube':
@@ -57,8 +59,14 @@ class Mesh:
             v = (pos + rng.normal(0., 0.05, pos.shape)).astype(np.float32)
             self.v, self.n, self.uv, self.share = v[None], nrm.astype(np.float32)[None], uv.astype(np.float32), 0.
         else:
-            xy, self.faces = R.strip_mesh(size) if kind == 'strip' else R.fan_mesh(size)
-            v, n, uv, share = R.draw_mesh(rng, xy, self.faces, components, jitter=0.05 if kind == 'strip' else 0.02)
+            if kind == 'torus':     # size = (nu, nv); mirrored: False, True, or 'both' for the two as disconnected components of one mesh
+                parts = [R.draw_torus(rng, *size, mirrored=m, components=components) for m in ((False, True) if mirrored == 'both' else (mirrored,))]
+                v, n, uv = (np.concatenate([p[k] for p in parts]) for k in range(3))
+                self.faces = np.concatenate([p[3] + i * len(parts[0][0]) for i, p in enumerate(parts)])     # the second component's indices offset
+                share = max(p[4] for p in parts)
+            else:
+                xy, self.faces = R.strip_mesh(size) if kind == 'strip' else R.fan_mesh(size)
+                v, n, uv, share = R.draw_mesh(rng, xy, self.faces, components, jitter=0.05 if kind == 'strip' else 0.02)
             draws = [(v, n)]
             for b in range(1, scenes or 1):     # the scenes share the uvs: the further ones are the first with its positions and normals jittered
                 vb = v.copy()
@@ -104,6 +112,13 @@ MESHES = {
     'strip%d' % (TG_BLOCK + 1): dict(seed=7005, kind='strip', size=TG_BLOCK + 1),
     'strip_w': dict(seed=7006, kind='strip', size=TG_BLOCK + 1, components=4),
     'scenes3': dict(seed=7007, kind='strip', size=TG_BLOCK + 1, scenes=3),
+    # a closed surface: normals over the whole sphere, 1 to 6 faces per vertex, 294 vertices (38 in a second workgroup)
+    'torus': dict(seed=7008, kind='torus', size=(20, 13)),
+    # the same draw with u -> 1 - u: w = -1 at every vertex.  (A normal jittered past 90 degrees from the surface's -- one vertex in
+    # 2 500 -- turns its vertex's sign, rightly; test_the_cases_hold_what_their_names_say asserts that these seeds drew none.)
+    'torus_mirrored': dict(seed=7008, kind='torus', size=(20, 13), mirrored=True),
+    'torus_both': dict(seed=7010, kind='torus', size=(20, 13), mirrored='both'),        # both signs in one launch, 588 vertices
+    'torus_w3': dict(seed=7011, kind='torus', size=(20, 13), mirrored='both', components=4, scenes=3),
 }
 PIXELS = dict(
     {'flat': dict(seed=7100), 'decoded': dict(seed=7101, encoded=False), 'strength0': dict(seed=7102, strength=0.),
@@ -233,6 +248,19 @@ def test_the_cases_hold_what_their_names_say():
     assert LAYOUTS['c7'][1:] == (0, 3) and LAYOUTS['c7r'][1] > LAYOUTS['c7r'][2]
     for name in ('strip256', 'fan300'):
         assert set(np.unique(case_of(name)[1]['tangents'][..., 3])) <= {-1., 1.}
+    # the tori, from the reference alone: both signs of the handedness, normals all over the sphere, every face count from 1 to 6
+    w = {name: case_of(name)[1]['tangents'][..., 3] for name in MESHES if name.startswith('torus')}
+    assert w['torus'].shape == (1, 294) and (w['torus'] == 1.).all() and (w['torus_mirrored'] == -1.).all()
+    assert w['torus_both'].shape == (1, 588) and (w['torus_both'][0, :294] == 1.).all() and (w['torus_both'][0, 294:] == -1.).all()
+    assert w['torus_w3'].shape == (3, 588) and all(int((row == s).sum()) == 294 for row in w['torus_w3'] for s in (-1., 1.))
+    both = case_of('torus_w3')[0]
+    assert both.v.shape == (3, 588, 4) and both.faces[:520].max() == 293 and both.faces[520:].min() == 294 and len(both.faces) == 1040
+    for name in w:
+        case = case_of(name)[0]
+        nz = np.abs(case.n[..., 2])
+        assert nz.min() < 0.1 and nz.max() > 0.9, name
+        assert sorted(set(np.bincount(case.faces.reshape(-1), minlength=case.V)[:294])) == [1, 2, 3, 6], name
+        assert -(-case.V // TG_BLOCK) == (2 if case.V == 294 else 3)
     for name in PIXELS:
         case, ref = case_of(name)
         assert ref['valid'].all() and (ref['sin'] >= R.MIN_SIN).all() and (ref['z'] >= R.MIN_Z).all(), name
@@ -281,6 +309,53 @@ def test_degenerate_uvs_and_unnamed_vertices_give_no_tangent_and_finite_gradient
     ref = R.tangents(v.detach().numpy(), n.detach().numpy(), uv.numpy(), f.numpy(), np.ones((6, 4), np.float32))
     assert np.array_equal(ref['tangents'][[0, 1, 5]], np.tile([0., 0., 0., 1.], (3, 1))) and ref['det_share'][0] == 0.
     assert np.abs(ref['d_vertices'] - v.grad.numpy()).max() <= 1e-5 and np.abs(ref['d_normals'] - n.grad.numpy()).max() <= 1e-5
+
+
+BAD_UVS = {'nan u': (0, np.nan), 'nan v': (1, np.nan), 'inf u': (0, np.inf)}
+BAD_VERTEX = 13     # of a strip of 30: faces 11, 12, 13 name it; vertices 11, 12, 14, 15 keep one or two live faces each
+
+
+def dead_face_case(kind):
+    """A strip of 30 vertices whose vertex 13 has a non-finite uv, and the restatement of the mesh with the three faces that name
+    it REMOVED (and a finite uv in its place): what the dead-face rule must give at every vertex, vertex 13 having no face left.
+    -> (vertices, normals, uvs, faces, grad_out, reference)"""
+    case = Mesh(seed=7020, kind='strip', size=30)
+    uv = case.uv.copy()
+    column, value = BAD_UVS[kind]
+    uv[BAD_VERTEX, column] = value
+    live = ~(case.faces == BAD_VERTEX).any(1)
+    assert int(live.sum()) == len(case.faces) - 3
+    ref = R.tangents(case.v[0], case.n[0], case.uv, case.faces[live], case.go[0])
+    assert (ref['det_share'] >= R.MARGIN).all() and (ref['w_share'] >= R.MARGIN).all() and (ref['sin'] >= R.MIN_SIN).all()     # still off the discontinuities
+    assert ref['valid'].tolist() == [k != BAD_VERTEX for k in range(30)]
+    return case.v[0], case.n[0], uv, case.faces, case.go[0], ref
+
+
+def check_dead_faces(got, ref, what):
+    """the bad vertex: (0, 0, 0, 1) and no gradient; every other vertex: the mesh without the dead faces; all of it finite"""
+    got = {k: R._f64(v) for k, v in got.items()}
+    assert all(np.isfinite(v).all() for v in got.values()), what
+    assert got['tangents'][BAD_VERTEX].tolist() == [0., 0., 0., 1.], what
+    assert not got['d_vertices'][BAD_VERTEX].any() and not got['d_normals'][BAD_VERTEX].any(), what
+    check(got, ref, R.TANGENT_KINDS, what)
+    assert np.array_equal(got['tangents'][:, 3], ref['tangents'][:, 3]), what
+
+
+@pytest.mark.parametrize('kind', sorted(BAD_UVS))
+def test_a_face_with_a_non_finite_uv_is_dead_in_the_torch_form_and_the_restatement(kind):
+    """A face is live iff its det is finite and non-zero; a dead face has a = b = c = d = 0 exactly.  The restatement of the mesh
+    with the non-finite uv equals that of the mesh without the dead faces, element for element; `lighting.vertex_tangents`
+    matches it in float64 (1e-12 of the masses) and in float32 (the kernels' allowance)."""
+    v, n, uv, faces, go, ref = dead_face_case(kind)
+    ruled = R.tangents(v, n, uv, faces, go)
+    for key in ('tangents', 'd_vertices', 'd_normals', 'mass_tangents', 'mass_d_vertices', 'mass_d_normals'):
+        assert np.array_equal(ruled[key], ref[key]), key
+    assert (ruled['det_share'][BAD_VERTEX - 2:BAD_VERTEX + 1] == 0.).all()
+    got = R.torch_tangents(v, n, uv, faces, go, torch.float64)
+    for k, x in R.ratios(got, ref, R.TANGENT_KINDS).items():
+        assert x <= 1e-12, (kind, k, x)
+    check_dead_faces(got, ref, kind + ' float64')
+    check_dead_faces(R.torch_tangents(v, n, uv, faces, go, torch.float32), ref, kind + ' float32')
 
 
 # ---- CPU tests: the interface
@@ -477,7 +552,7 @@ def test_vertex_tangents_with_one_gradient_wanted(gpu, want):
 
 @pytest.mark.gpu
 def test_vertex_tangents_gives_the_same_bits_on_every_run(gpu):
-    for name in ('fan300', 'scenes3'):
+    for name in ('fan300', 'scenes3', 'torus_both'):
         a, b = fused_tangents(case_of(name)[0], gpu), fused_tangents(case_of(name)[0], gpu)
         for k in a:
             assert torch.equal(a[k], b[k]), (name, k)
@@ -506,6 +581,66 @@ def test_vertex_tangents_of_degenerate_uvs_and_empty_calls(gpu):
         assert out.shape == lead + (0, 4)
         out.sum().backward()
         assert vv.grad.shape == vv.shape
+
+
+def fused_tangents_of(dev, v, n, uv, faces, go):
+    """the fused call and its backward on arrays: vertices [.., V, 3|4], normals, uvs [V, 2], faces, grad_out [.., V, 4]"""
+    from dirt_amd import geometry
+    vt, nt = _dev(dev, v).requires_grad_(True), _dev(dev, n).requires_grad_(True)
+    out = geometry.vertex_tangents(vt, nt, _dev(dev, uv), geometry.MeshTopology(_dev(dev, faces), v.shape[-2]))
+    out.backward(_dev(dev, go))
+    return {'tangents': out.detach(), 'd_vertices': vt.grad, 'd_normals': nt.grad}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('kind', sorted(BAD_UVS))
+def test_a_face_with_a_non_finite_uv_is_dead_in_the_kernels(gpu, kind):
+    """The CPU test's mesh through the three tangent kernels: the vertex with the bad uv gets (0, 0, 0, 1) and no gradient, every
+    other vertex what the mesh without the dead faces gives, and nothing is NaN."""
+    v, n, uv, faces, go, ref = dead_face_case(kind)
+    check_dead_faces(fused_tangents_of(gpu, v, n, uv, faces, go), ref, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('value', [np.nan, np.inf])
+def test_a_non_finite_position_empties_the_frames_of_its_faces_only(gpu, value):
+    """One coordinate of vertex 13 of the strip of 30 is NaN or Inf.  Its faces stay live (the uvs are fine), so T is NaN at their
+    five vertices 11..15, x . x > 0 fails there, and those get t = 0, w = 1, G_T = 0 and d n = 0; every gradient is finite, and all
+    of it is what the restatement, which masks the same way, gives.  (torch's autograd is not compared: it may leave a NaN where
+    the specification says 0.)"""
+    case = Mesh(seed=7020, kind='strip', size=30)
+    v = case.v[0].copy()
+    v[BAD_VERTEX, 1] = value
+    with np.errstate(all='ignore'):
+        ref = R.tangents(v, case.n[0], case.uv, case.faces, case.go[0])
+    near = np.unique(case.faces[(case.faces == BAD_VERTEX).any(1)])
+    assert near.tolist() == [11, 12, 13, 14, 15] and ref['valid'].tolist() == [k not in near for k in range(30)]
+    for key in ('tangents', 'd_vertices', 'd_normals', 'mass_tangents', 'mass_d_vertices', 'mass_d_normals'):
+        assert np.isfinite(ref[key]).all(), key
+    assert np.array_equal(ref['tangents'][near], np.tile([0., 0., 0., 1.], (5, 1))) and not ref['d_normals'][near].any()
+    assert not ref['mass_tangents'][near].any() and not ref['mass_d_normals'][near].any() and not ref['d_vertices'][BAD_VERTEX].any()
+    far = ref['valid']
+    assert (ref['w_share'][far] >= R.MARGIN).all() and (ref['sin'][far] >= R.MIN_SIN).all()
+    got = fused_tangents_of(gpu, v, case.n[0], case.uv, case.faces, case.go[0])
+    check(got, ref, R.TANGENT_KINDS, 'position %s' % value)
+    assert np.array_equal(got['tangents'].cpu().numpy()[:, 3], ref['tangents'][:, 3])
+    assert bool(got['d_vertices'][near].any())     # (the live neighbours' gradients still reach vertices 11, 12, 14, 15)
+
+
+@pytest.mark.gpu
+def test_vertex_tangents_at_the_scene_limit(gpu):
+    """B = 65 535, the most gridDim.y takes (65 536 is refused: test_every_refusal_in_full), of one triangle: the scenes repeat a
+    table of 7 draws; scenes 0..6 against the restatement, and every scene b the bits of scene b % 7, forward and both gradients."""
+    B, period = 65535, 7
+    table = Mesh(seed=7021, kind='strip', size=3, scenes=period)
+    ref = table.reference()
+    which = np.arange(B) % period
+    got = fused_tangents_of(gpu, table.v[which], table.n[which], table.uv, table.faces, table.go[which])
+    assert got['tangents'].shape == (B, 3, 4) and got['d_vertices'].shape == (B, 3, 3)
+    check({k: x[:period] for k, x in got.items()}, ref, R.TANGENT_KINDS, 'scene limit')
+    at = torch.from_numpy(which).to(gpu)
+    for k, x in got.items():
+        assert torch.equal(x.view(torch.int32), x[:period].view(torch.int32)[at]), k
 
 
 # ---- GPU tests: perturb_normals
@@ -617,6 +752,47 @@ def test_invalid_pixels_mixed_into_a_span(gpu):
 
 
 @pytest.mark.gpu
+def test_non_finite_pixels_stay_in_their_own_pixel(gpu):
+    """Five kinds of non-finite pixel scattered over a workgroup's span at a stride of 97, one on the last pixel of a pass and one
+    on the first of the next: a NaN or Inf normal, a NaN tangent, a NaN handedness, a NaN texel.  By the restatement each fails
+    one of the three `> 0` tests, keeps its normal -- non-finite where it was -- and hands grad_out to it alone.  Every other
+    pixel gives what it gives in the clean input: nothing leaks through the LDS rows or the tile walk."""
+    case = Pixels(seed=7161, layout='c12', n=FLAT)
+    clean = case.reference()
+    on, ot = case.on, case.ot
+    put = {   # kind -> (first row, array, column, value)
+        'nan normal': (5, case.g, on + 1, np.nan), 'inf normal': (12, case.g, on, np.inf), 'nan tangent': (19, case.g, ot + 2, np.nan),
+        'nan handedness': (NM_BLOCK - 1 - 2 * 97, case.g, ot + 3, np.nan), 'nan texel': (NM_BLOCK - 2 * 97, case.m, 0, np.nan)}
+    rows = {kind: np.arange(first, FLAT, 97) for kind, (first, _, _, _) in put.items()}
+    assert NM_BLOCK - 1 in rows['nan handedness'] and NM_BLOCK in rows['nan texel']
+    for kind, (_, array, column, value) in put.items():
+        array[rows[kind], column] = value
+    bad = np.concatenate(list(rows.values()))
+    good = np.ones(FLAT, bool)
+    good[bad] = False
+    assert len(np.unique(bad)) == len(bad) == FLAT - int(good.sum()) and len(bad) > 50
+    with np.errstate(all='ignore'):
+        dirty = case.reference()
+    sl_n, sl_t = slice(on, on + 3), slice(ot, ot + 4)
+    # what the restatement says of the bad rows: invalid, the normal kept as it is, grad_out to the normal alone
+    assert not dirty['valid'][bad].any() and dirty['valid'][good].all()
+    assert np.array_equal(dirty['out'][bad][:, sl_n], case.g[bad][:, sl_n].astype(np.float64), equal_nan=True)
+    assert np.array_equal(dirty['d_gbuffer'][bad], case.go[bad].astype(np.float64)) and not dirty['d_normal_map'][bad].any()
+    for key in ('out', 'd_gbuffer', 'd_normal_map'):     # ... and of the others: what the clean input gives
+        assert np.array_equal(dirty[key][good], clean[key][good]), key
+    got = fused_perturb(case, gpu)
+    keys = [key for _, key in R.PIXEL_KINDS]
+    where = torch.from_numpy(good).to(gpu)
+    check({key: got[key][where] for key in keys}, {k: clean[k][good] for key in keys for k in (key, 'mass_' + key)}, R.PIXEL_KINDS, 'non-finite')
+    untouched_bits(case, got)
+    out, dg, dm = (got[k].cpu().numpy() for k in keys)
+    assert np.array_equal(out[bad][:, sl_n].view(np.uint32), case.g[bad][:, sl_n].view(np.uint32))
+    assert np.array_equal(np.isfinite(out), np.isfinite(case.g)) and np.isfinite(dg).all() and np.isfinite(dm).all()
+    assert np.array_equal(dg[bad][:, sl_n], case.go[bad][:, sl_n]) and np.array_equal(dg[bad][:, sl_t], case.go[bad][:, sl_t])
+    assert not dm[bad].any()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('name', ['c7r', 'c257'])
 def test_the_c_abi_writes_nothing_outside_its_outputs(gpu, name):
     """Both entry points called through ctypes with every output between two guard zones: the zones keep their bits, the
@@ -647,27 +823,41 @@ def test_the_c_abi_writes_nothing_outside_its_outputs(gpu, name):
 
 
 @pytest.mark.gpu
-def test_the_tangent_c_abi_writes_nothing_outside_its_outputs(gpu):
+@pytest.mark.parametrize('name,vertex_gradient', [('scenes3', True), ('torus_w3', True), ('torus_w3', False)])
+def test_the_tangent_c_abi_writes_nothing_outside_its_outputs(gpu, name, vertex_gradient):
+    """Both entry points through ctypes, three scenes, every output and the scratch between two guard zones: the zones keep
+    their bits and the outputs match the restatement.  `torus_w3` has four-component vertices: grad_vertices is [3, 588, 4], its
+    fourth components exactly 0 (the store that follows each triple stays inside its row).  Without grad_vertices (NULL, and
+    scratch NULL, 0) the gather is not launched: d normals alone."""
     from dirt_amd import _lib, geometry
     lib = _lib.load()
-    case, ref = case_of('scenes3')
+    case, ref = case_of(name)
     GUARD, PAD = 1.5e30, 4096
-    B, V = 3, case.V
+    B, V, C = 3, case.V, case.components
+    assert case.v.shape == (B, V, C)
     top = geometry.MeshTopology(_dev(gpu, case.faces), V)
     v, n, uv, go = _dev(gpu, case.v), _dev(gpu, case.n), _dev(gpu, case.uv), _dev(gpu, case.go)
-    out, dv, dn, scratch = (torch.full((PAD + B * V * c + PAD,), GUARD, device=gpu) for c in (4, 3, 3, 3))
+    out, dv, dn, scratch = (torch.full((PAD + B * V * c + PAD,), GUARD, device=gpu) for c in (4, C, 3, 3))
     at = lambda t: t.data_ptr() + 4 * PAD   # noqa: E731
     stream = torch.cuda.current_stream(gpu).cuda_stream
-    head = (v.data_ptr(), 3, n.data_ptr(), uv.data_ptr(), top.faces.data_ptr(), top.offsets.data_ptr(), top.entries.data_ptr())
+    head = (v.data_ptr(), C, n.data_ptr(), uv.data_ptr(), top.faces.data_ptr(), top.offsets.data_ptr(), top.entries.data_ptr())
     nbytes = lib.dirt_tangent_scratch_bytes(B, V, top.num_faces)
     assert nbytes == B * V * 12
+    wanted = (at(dv), at(dn), at(scratch), nbytes) if vertex_gradient else (None, at(dn), None, 0)
     assert lib.dirt_tangent_forward(*head, at(out), B, V, top.num_faces, stream) == 0, _lib.last_error()
-    assert lib.dirt_tangent_backward(*head, go.data_ptr(), at(dv), at(dn), at(scratch), nbytes, B, V, top.num_faces, stream) == 0, _lib.last_error()
+    assert lib.dirt_tangent_backward(*head, go.data_ptr(), *wanted, B, V, top.num_faces, stream) == 0, _lib.last_error()
     torch.cuda.synchronize()
     for t in (out, dv, dn, scratch):
         assert bool((t[:PAD] == GUARD).all()) and bool((t[-PAD:] == GUARD).all())
-    got = {'tangents': out[PAD:-PAD].reshape(B, V, 4), 'd_vertices': dv[PAD:-PAD].reshape(B, V, 3), 'd_normals': dn[PAD:-PAD].reshape(B, V, 3)}
-    check(got, ref, R.TANGENT_KINDS, 'c abi tangents')
+    got = {'tangents': out[PAD:-PAD].reshape(B, V, 4), 'd_vertices': dv[PAD:-PAD].reshape(B, V, C), 'd_normals': dn[PAD:-PAD].reshape(B, V, 3)}
+    if vertex_gradient:
+        assert not bool((scratch[PAD:-PAD] == GUARD).any())     # d loss / d T of every vertex of every scene
+        assert C == 3 or not bool(got['d_vertices'][..., 3].any())
+    else:
+        assert bool((dv == GUARD).all()) and bool((scratch == GUARD).all())
+        got['d_vertices'] = None
+    check(got, ref, R.TANGENT_KINDS, 'c abi tangents ' + name)
+    assert torch.equal(got['tangents'][..., 3], _dev(gpu, ref['tangents'][..., 3]).float())
 
 
 @pytest.mark.gpu
