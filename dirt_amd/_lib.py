@@ -29,6 +29,7 @@ FLAG_GRAD_PX4 = 0x10000   # ... or the four-pixels-per-lane kernel where the lib
 FLAG_GRAD_STREAM = 0x20000  # reserved: accepted and ignored (it pinned an experimental kernel, since removed)
 TEX_CLAMP = 1
 TEX_NEAREST = 2
+ENVMAP_GGX, ENVMAP_LAMBERT = 0, 1   # the kind of dirt_envmap_filter_forward / _backward
 SHADE_MAX_LIGHTS = 8
 SHADE_PARAM_HEAD, SHADE_PARAM_LIGHT = 9, 8   # floats of the parameter block: ambient, background, camera; then per light
 SHADE_KINDS = {'diffuse_directional': 0, 'specular_directional': 1, 'diffuse_point': 2}
@@ -63,7 +64,7 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_texture_mip_collapse', 'dirt_texture_sample_mip_forward', 'dirt_texture_sample_mip_backward',
            'dirt_texture_sample_batch_forward', 'dirt_texture_sample_batch_backward_image', 'dirt_texture_mip_build_batch',
            'dirt_texture_mip_collapse_batch', 'dirt_texture_sample_mip_batch_forward', 'dirt_texture_sample_mip_batch_backward',
-           'dirt_texture_cube_forward', 'dirt_texture_cube_backward',
+           'dirt_texture_cube_forward', 'dirt_texture_cube_backward', 'dirt_envmap_filter_forward', 'dirt_envmap_filter_backward',
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward', 'dirt_shade_albedo_forward', 'dirt_shade_albedo_backward',
            'dirt_shade_sh_scratch_bytes', 'dirt_shade_sh_forward', 'dirt_shade_sh_backward',
            'dirt_shade_pbr_scratch_bytes', 'dirt_shade_pbr_forward', 'dirt_shade_pbr_backward',
@@ -157,6 +158,12 @@ def load():
         lib.dirt_texture_cube_forward.restype = i
         lib.dirt_texture_cube_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, ll, ll, i, i, i, i, i, f32, u, vp]
         lib.dirt_texture_cube_backward.restype = i
+    if hasattr(lib, 'dirt_envmap_filter_forward') or not override:   # environment prefilter (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_envmap_filter_forward.argtypes = [fp, fp, fp, i, i, ll, f32, u, vp]
+        lib.dirt_envmap_filter_forward.restype = i
+        lib.dirt_envmap_filter_backward.argtypes = [fp, fp, fp, i, i, ll, f32, u, vp]
+        lib.dirt_envmap_filter_backward.restype = i
     if hasattr(lib, 'dirt_shade_forward') or not override:   # fused G-buffer lighting (ABI 4, additive)
         f32 = ctypes.c_float
         lib.dirt_shade_scratch_bytes.argtypes = [ll, ll, i]

@@ -14,7 +14,12 @@ launch for all scenes (the dirt_texture_*_batch entry points), not a Python loop
 
 `sample_texture_cube` looks a cube map [6, N, N, C] up by direction (an environment map; dirt_texture_cube.hip), with the
 same three filters; `directions_to_cube_indices` and `sample_cube` are its pure-torch form, as `uvs_to_pixel_indices` and
-`sample_texture` are the flat look-up's."""
+`sample_texture` are the flat look-up's.
+
+`prefilter_cube` makes the GGX-prefiltered pyramid of an environment cube (a `CubePyramid`: level k the cube's box-filtered
+level k convolved with a GGX lobe of roughness r_k; dirt_envmap.hip), `convolve_cube` one such convolution (or the cosine
+one, the irradiance), and `sample_cube_pyramid` is the trilinear cube look-up in a pyramid the caller made -- `cube_pyramid`
+the box-filtered one.  `cube_texel_directions` and `convolve_cube_dense` are the convolution's pure-torch form for small cubes."""
 import ctypes
 import functools
 import math
@@ -483,3 +488,293 @@ def sample_texture_cube(cube, directions, filter='bilinear', *, lod=None, lod_bi
     _stage.require_gpu(cube, 'dirt_amd.texture.sample_texture_cube')
     return _SampleTextureCube.apply(cube.to(torch.float32), directions.to(torch.float32), lod, _lib.TEX_NEAREST if filter == 'nearest' else 0,
                                     float(lod_bias), max_level)
+
+
+# ---- prefiltered environment maps: a pyramid whose levels are the cube convolved with a lobe (dirt_envmap.hip) ---------
+
+ROUGHNESS_MIN = 1.0 / 32.0   # the narrowest GGX lobe the filter takes; 0 is the identity
+
+
+class CubePyramid:
+    """A pyramid per face of a cube map in one packed buffer: `packed` [6, floats] float32 (it carries the autograd graph), laid out
+    as `mip_pyramid_batch(cube)`'s, `size` and `channels` of level 0, the `levels` count, and `roughness`: the roughness each level was
+    convolved at (a tuple), or None where the levels are box-filtered means.  `cube_pyramid` and `prefilter_cube` make one;
+    `sample_cube_pyramid` looks it up."""
+
+    def __init__(self, packed, size, channels, levels, roughness=None):
+        self.packed, self.size, self.channels, self.levels = packed, int(size), int(channels), int(levels)
+        self.roughness = None if roughness is None else tuple(float(r) for r in roughness)
+
+    def level(self, k):
+        """Level k as a view [6, n_k, n_k, C] into `packed`."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < self.levels:
+            raise ValueError('CubePyramid.level: level %r of %d' % (k, self.levels))
+        o, n = _cube_level(self.size, self.channels, k)
+        return self.packed[:, o:o + n * n * self.channels].view(6, n, n, self.channels)
+
+
+def _cube_level(size, channels, k):
+    """-> (offset in floats inside a face's packed pyramid, size) of level k."""
+    n = size >> k
+    return (size * size - n * n) // 3 * 4 * channels, n
+
+
+def _check_cube(cube, who):
+    if not isinstance(cube, torch.Tensor) or cube.dim() != 4 or cube.shape[0] != 6 or cube.shape[1] != cube.shape[2] or 0 in cube.shape:
+        raise ValueError('%s expects cube to be 4D [6, size, size, channels], got shape %s' % (who, tuple(getattr(cube, 'shape', ()))))
+    if not cube.is_floating_point():
+        raise ValueError('%s: cube must be a floating-point tensor, got %s' % (who, cube.dtype))
+
+
+def _check_roughness(r, who):
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not (r == 0 or ROUGHNESS_MIN <= r <= 1):
+        raise ValueError('%s: roughness must be a float that is 0 or in [1/32, 1], got %r' % (who, r))
+    return float(r)
+
+
+def _filter_kind(kind, roughness, who):
+    """-> (the entry points' kind, roughness as a float; Lambert: 1.0, which they ignore)"""
+    if kind not in ('ggx', 'lambert'):
+        raise ValueError("%s: kind must be 'ggx' or 'lambert', got %r" % (who, kind))
+    if kind == 'lambert':
+        if roughness is not None:
+            raise ValueError("%s: roughness applies to kind='ggx' only (got kind='lambert', roughness=%r)" % (who, roughness))
+        return _lib.ENVMAP_LAMBERT, 1.0
+    if roughness is None:
+        raise ValueError("%s: kind='ggx' needs a roughness" % who)
+    return _lib.ENVMAP_GGX, _check_roughness(roughness, who)
+
+
+def cube_texel_directions(size, device=None, dtype=torch.float32):
+    """-> (directions [6, size, size, 3], unit vectors through the texel centres of a cube map's faces in OpenGL order, and
+    weights [6, size, size], the texels' solid angles up to a constant: (1 + sc^2 + tc^2)^(-3/2)).  The inverse of
+    `directions_to_cube_indices`: direction [f, r, c] maps back to face f, index (r, c).  Pure torch."""
+    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
+        raise ValueError('cube_texel_directions: size must be a positive int, got %r' % (size,))
+    x = 2. * (torch.arange(size, device=device, dtype=dtype) + 0.5) / size - 1.
+    tc, sc = torch.meshgrid(x, x, indexing='ij')
+    one = torch.ones_like(sc)
+    v = torch.stack([torch.stack(f, -1) for f in ((one, -tc, -sc), (-one, -tc, sc), (sc, one, tc), (sc, -one, -tc), (sc, -tc, one), (-sc, -tc, -one))])
+    inv = 1. / torch.sqrt(1. + sc * sc + tc * tc)
+    return v * inv[None, :, :, None], (inv * inv * inv).expand(6, size, size).contiguous()
+
+
+def convolve_cube_dense(cube, roughness=None, kind='ggx'):
+    """The specification of `convolve_cube` as a dense [6 N^2, 6 N^2] matrix, for small N: pure torch, on any device, in the
+    cube's dtype, differentiable.  cube [6, N, N, C] -> [6, N, N, C]: every texel the mean of all texels, weighted by their solid
+    angles and by k(t) of the cosine t between the two texels' directions -- the clamped cosine t+ ('lambert'), or ('ggx',
+    alpha = roughness^2) t+ max(q(t) - q_c, 0) with q(t) = 1 / (1 + t+^2 (alpha^2 - 1))^2 and q_c = q(1) / 256 while
+    16 alpha^2 < 1, else 0.  roughness 0 is the identity."""
+    who = 'convolve_cube_dense'
+    _check_cube(cube, who)
+    code, r = _filter_kind(kind, roughness, who)
+    if code == _lib.ENVMAP_GGX and r == 0:
+        return cube.clone()
+    n, ct = int(cube.shape[1]), int(cube.shape[3])
+    d, w = cube_texel_directions(n, cube.device, cube.dtype)
+    d = d.reshape(-1, 3)
+    with torch.no_grad():   # the weights depend on the geometry alone (in place: three matrices at a time)
+        e = sum((d[:, None, i] - d[None, :, i]).square_() for i in range(3))   # |d_o - d_s|^2 = 2 - 2 t: 1 - t^2 = e (1 - e / 4) without cancellation
+        k = (1. - 0.5 * e).clamp_min_(0.)                  # t+
+        if code == _lib.ENVMAP_GGX:
+            a2 = r ** 4
+            e = torch.where(k > 0, e * (1. - 0.25 * e), 1.).add_(a2 * k * k)   # 1 - t+^2 (an antipodal pair: 1), then 1 + t+^2 (alpha^2 - 1)
+            q = e.reciprocal_().mul_(a2).square_()         # q(t) alpha^4
+            k.mul_(q.sub_(1. / 256. if 16. * a2 < 1. else 0.).clamp_min_(0.))
+        del e
+        k.mul_(w.reshape(1, -1))
+        k.div_(k.sum(1, keepdim=True))
+    return (k @ cube.reshape(-1, ct)).reshape(6, n, n, ct)
+
+
+def _level_in_place(cube):
+    """(tensor to pass, floats between its faces): a `CubePyramid.level(k)` view -- dense faces a constant stride apart -- is read in
+    place, anything else is made contiguous."""
+    _, n, _, ct = (int(s) for s in cube.shape)
+    if cube.dtype == torch.float32 and tuple(cube.stride()[1:]) == (n * ct, ct, 1) and cube.stride(0) >= n * n * ct:
+        return cube, int(cube.stride(0))
+    return cube.to(torch.float32).contiguous(), n * n * ct
+
+
+def _envmap_filter(src, dst, stride, norm, n, ct, alpha, code, transposed=False):
+    """One level through dirt_envmap_filter_forward (`norm` written) or _backward (`norm` read); src and dst are tensors whose
+    first element is the level's first of face 0, the faces of both `stride` floats apart (the entry points take one stride)."""
+    lib = _lib.load()
+    if transposed:
+        _call(lib.dirt_envmap_filter_backward, dst.device, src.data_ptr(), norm.data_ptr(), dst.data_ptr(), n, ct, stride, alpha, code)
+    else:
+        _call(lib.dirt_envmap_filter_forward, dst.device, src.data_ptr(), dst.data_ptr(), norm.data_ptr(), n, ct, stride, alpha, code)
+
+
+class _ConvolveCube(torch.autograd.Function):
+    """cube [6, N, N, C] (faces `stride` floats apart) -> [6, N, N, C]."""
+
+    @staticmethod
+    def forward(ctx, cube, alpha, code):
+        src, stride = _level_in_place(cube)
+        n, ct = int(cube.shape[1]), int(cube.shape[3])
+        if stride != n * n * ct:   # a level inside a packed pyramid: the output gets the same face stride (one stride per call)
+            out = torch.empty((6, stride), dtype=torch.float32, device=cube.device)[:, :n * n * ct].view(6, n, n, ct)
+        else:
+            out = torch.empty((6, n, n, ct), dtype=torch.float32, device=cube.device)
+        norm = torch.empty((6, n, n), dtype=torch.float32, device=cube.device)
+        _envmap_filter(src, out, stride, norm, n, ct, alpha, code)
+        ctx.save_for_backward(norm)
+        ctx.meta = (n, ct, alpha, code)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        norm, = ctx.saved_tensors
+        n, ct, alpha, code = ctx.meta
+        grad_out = grad_out.to(torch.float32).contiguous()
+        grad_cube = torch.empty_like(grad_out)
+        _envmap_filter(grad_out, grad_cube, n * n * ct, norm, n, ct, alpha, code, transposed=True)
+        return grad_cube, None, None
+
+
+def convolve_cube(cube, roughness=None, kind='ggx'):
+    """One level of an environment map convolved with a lobe on the sphere, by the HIP filter kernel: cube [6, N, N, C] float32
+    (faces in OpenGL order) -> [6, N, N, C], what `convolve_cube_dense` specifies.  kind='ggx': a GGX lobe of `roughness` (a
+    float, 0 -- the identity -- or in [1/32, 1]; not differentiable); kind='lambert': the clamped cosine, the cube's irradiance
+    up to the factor pi (takes no roughness).  A `CubePyramid.level(k)` view is read in place.  Differentiable with respect
+    to the cube: the gradient is the transposed convolution, by the same kernel.  The same bits on every run."""
+    who = 'convolve_cube'
+    _check_cube(cube, who)
+    code, r = _filter_kind(kind, roughness, who)
+    _stage.require_gpu(cube, 'dirt_amd.texture.convolve_cube')
+    if code == _lib.ENVMAP_GGX and r == 0:
+        return cube.to(torch.float32).clone()
+    return _ConvolveCube.apply(cube if cube.dtype == torch.float32 else cube.to(torch.float32), r * r, code)
+
+
+def _pyramid_geometry(cube, max_level, who):
+    _check_cube(cube, who)
+    _check_max_level(max_level)
+    n, ct = int(cube.shape[1]), int(cube.shape[3])
+    levels, floats, _ = _mip_geometry(n, n, ct, max_level)
+    return n, ct, levels, floats
+
+
+def cube_pyramid(cube, max_level=None):
+    """The box-filtered pyramid of a cube map [6, N, N, C] as a `CubePyramid` (roughness None): `mip_pyramid_batch(cube)` with the
+    six faces as scenes, the pyramid `sample_texture_cube(..., filter='trilinear')` builds for itself.  Differentiable."""
+    n, ct, levels, floats = _pyramid_geometry(cube, max_level, 'cube_pyramid')
+    _stage.require_gpu(cube, 'dirt_amd.texture.cube_pyramid')
+    return CubePyramid(_MipPyramid.apply(cube.to(torch.float32), levels, floats, 6), n, ct, levels)
+
+
+class _PrefilterCube(torch.autograd.Function):
+    """cube [6, N, N, C] -> packed [6, floats]: the box pyramid, then level k convolved at roughness[k] (0: copied)."""
+
+    @staticmethod
+    def forward(ctx, cube, roughness, levels, floats):
+        cube = cube.contiguous()
+        n, ct = int(cube.shape[1]), int(cube.shape[3])
+        dev = cube.device
+        box = torch.empty((6, floats), dtype=torch.float32, device=dev)
+        _call_entry('mip_build', 6, dev, (cube.data_ptr(), box.data_ptr()), n, n, ct, levels)
+        packed = torch.empty_like(box)
+        norms = []
+        for k, r in enumerate(roughness):
+            o, nk = _cube_level(n, ct, k)
+            if r == 0:
+                packed[:, o:o + nk * nk * ct] = box[:, o:o + nk * nk * ct]
+                norms.append(None)
+                continue
+            norms.append(torch.empty((6, nk, nk), dtype=torch.float32, device=dev))
+            _envmap_filter(box[0, o:], packed[0, o:], floats, norms[-1], nk, ct, r * r, _lib.ENVMAP_GGX)
+        ctx.save_for_backward(*[x for x in norms if x is not None])
+        ctx.meta = (n, ct, levels, floats, roughness)
+        return packed
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_packed):
+        n, ct, levels, floats, roughness = ctx.meta
+        norms = iter(ctx.saved_tensors)
+        grad_packed = grad_packed.to(torch.float32).contiguous()
+        dev = grad_packed.device
+        grad_box = torch.empty_like(grad_packed)       # every level is fully written
+        for k, r in enumerate(roughness):
+            o, nk = _cube_level(n, ct, k)
+            if r == 0:
+                grad_box[:, o:o + nk * nk * ct] = grad_packed[:, o:o + nk * nk * ct]
+                continue
+            _envmap_filter(grad_packed[0, o:], grad_box[0, o:], floats, next(norms), nk, ct, r * r, _lib.ENVMAP_GGX, transposed=True)
+        grad_cube = torch.empty((6, n, n, ct), dtype=torch.float32, device=dev)
+        _call_entry('mip_collapse', 6, dev, (grad_box.data_ptr(), grad_cube.data_ptr()), n, n, ct, levels)
+        return grad_cube, None, None, None
+
+
+def prefilter_cube(cube, roughness=None, *, max_level=None):
+    """The GGX-prefiltered pyramid of an environment cube [6, N, N, C] (the specular half of split-sum image-based lighting) as a
+    `CubePyramid`: the box pyramid per face (`cube_pyramid`, with its level count and layout), level k then convolved with a GGX
+    lobe of roughness[k] as `convolve_cube` does.  `roughness`: a float per level, each 0 or in [1/32, 1]; default k / (L - 1)
+    for L levels, so that `sample_cube_pyramid(pyramid, directions, roughness * (L - 1))` reads a reflection of that roughness.
+    Differentiable with respect to the cube (the transposed convolution of every level, then the pyramid's collapse); the same
+    bits on every run."""
+    who = 'prefilter_cube'
+    n, ct, levels, floats = _pyramid_geometry(cube, max_level, who)
+    if roughness is None:
+        roughness = tuple(k / (levels - 1) for k in range(levels)) if levels > 1 else (0.0,)
+    if isinstance(roughness, torch.Tensor) or not isinstance(roughness, (tuple, list)) or len(roughness) != levels:
+        raise ValueError('%s: roughness must be a tuple of %d floats, one per level, got %r' % (who, levels, roughness))
+    roughness = tuple(_check_roughness(r, who) for r in roughness)
+    _stage.require_gpu(cube, 'dirt_amd.texture.prefilter_cube')
+    return CubePyramid(_PrefilterCube.apply(cube.to(torch.float32), roughness, levels, floats), n, ct, levels, roughness)
+
+
+class _SampleCubePyramid(torch.autograd.Function):
+    """packed [6, floats], directions [..., 3], lod [...]: `_SampleTextureCube` with the caller's pyramid."""
+
+    @staticmethod
+    def forward(ctx, packed, directions, lod, lod_bias, n, ct, levels):
+        pyr = packed.contiguous()
+        src, stride = _stage.rows_in_place(directions, 3)
+        rows, cols, _ = _pixel_grid(directions.shape)
+        lod_t = lod.to(torch.float32).contiguous()
+        out = torch.empty(tuple(directions.shape[:-1]) + (ct,), dtype=torch.float32, device=pyr.device)
+        _call(_lib.load().dirt_texture_cube_forward, pyr.device, pyr.data_ptr(), _stage.ptr(src), _stage.ptr(lod_t), _stage.ptr(out), rows * cols, n, ct,
+              levels, stride, lod_bias, 0)
+        ctx.save_for_backward(pyr, src, lod_t)
+        ctx.meta = (stride, lod_bias, tuple(directions.shape), rows, cols, n, ct, levels)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pyr, src, lod_t = ctx.saved_tensors
+        stride, lod_bias, dir_shape, rows, cols, n, ct, levels = ctx.meta
+        dev = pyr.device
+        grad_out = grad_out.contiguous().to(torch.float32)
+        grad_pyr = torch.empty_like(pyr)               # cleared by the call
+        grad_dirs = torch.empty(dir_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        grad_lod = torch.empty(dir_shape[:-1], dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        _call(_lib.load().dirt_texture_cube_backward, dev, pyr.data_ptr(), _stage.ptr(src), _stage.ptr(lod_t), _stage.ptr(grad_out), grad_pyr.data_ptr(),
+              _stage.ptr(grad_dirs), _stage.ptr(grad_lod), rows, cols, n, ct, levels, stride, 3, lod_bias, 0)
+        return grad_pyr, grad_dirs, grad_lod, None, None, None, None
+
+
+def sample_cube_pyramid(pyramid, directions, lod, *, lod_bias=0.0):
+    """The trilinear look-up of `sample_texture_cube` in a pyramid the caller made (`cube_pyramid`, `prefilter_cube`): directions
+    [..., 3] and lod shaped like directions[..., 0] -> [..., C], two adjacent levels blended at the level of detail `lod` +
+    `lod_bias`.  The pyramid is not rebuilt: the same kernels read `pyramid.packed`.  Differentiable with respect to
+    `pyramid.packed` (and through it the cube), the directions and lod."""
+    who = 'sample_cube_pyramid'
+    if not isinstance(pyramid, CubePyramid):
+        raise ValueError('%s expects a CubePyramid (cube_pyramid, prefilter_cube), got %s' % (who, type(pyramid).__name__))
+    packed = pyramid.packed
+    if not isinstance(directions, torch.Tensor) or directions.dim() < 1 or directions.shape[-1] != 3:
+        raise ValueError('%s expects directions of shape [..., 3], got %s' % (who, tuple(getattr(directions, 'shape', ()))))
+    if not directions.is_floating_point():
+        raise ValueError('%s: directions must be a floating-point tensor, got %s' % (who, directions.dtype))
+    if packed.device != directions.device:
+        raise ValueError('pyramid and directions must be on the same device (%s vs %s)' % (packed.device, directions.device))
+    if not isinstance(lod, torch.Tensor) or tuple(lod.shape) != tuple(directions.shape[:-1]):
+        raise ValueError('lod must be a tensor shaped like directions[..., 0] %s, got %s' % (tuple(directions.shape[:-1]), tuple(getattr(lod, 'shape', ()))))
+    if lod.device != directions.device:
+        raise ValueError('lod and directions must be on the same device (%s vs %s)' % (lod.device, directions.device))
+    _stage.require_gpu(packed, 'dirt_amd.texture.sample_cube_pyramid')
+    return _SampleCubePyramid.apply(packed, directions.to(torch.float32), lod, float(lod_bias), pyramid.size, pyramid.channels, pyramid.levels)

@@ -334,6 +334,24 @@ int dirt_texture_cube_backward(const float *pyramid, const float *directions, co
                                float *grad_pyramid, float *grad_directions, float *grad_lod, long long rows, long long cols,
                                int size, int channels, int levels, int dir_stride, int grad_dir_stride, float lod_bias,
                                unsigned flags, void *stream);
+/* ENVIRONMENT PREFILTER: one level of a cube map convolved with a lobe on the sphere, and the transpose (the gradient).  These
+ * two replace no reference interface; specification in dirt_amd/csrc/dirt_envmap.hip and DESIGN.md §7.  src, dst, grad_dst and
+ * grad_src point at the level [size, size, channels] (dense) inside face 0; the six faces are `face_stride` floats apart, so a
+ * level of a packed pyramid [6, floats] (face_stride = floats) is read and written where it lies, and a cube [6, size, size,
+ * channels] has face_stride = size * size * channels.  kind: DIRT_ENVMAP_GGX, a GGX lobe of alpha = roughness^2 in (0, 1],
+ * cut off at 1/256 of its peak while 16 alpha^2 < 1; DIRT_ENVMAP_LAMBERT, the clamped cosine (alpha is ignored).  Every output
+ * texel is the weighted mean of the source texels of all six faces, the weights the lobe times the texels' solid angles.
+ * norm [6, size, size]: the sum of an output texel's weights, in the kernel's own scale, written by the forward and read by the
+ * backward only.  grad_src is fully written (no clear).  No atomics: the same bits on every run.  Both return 0 or DIRT_E_*,
+ * described by dirt_texture_last_error(); refused before any device work: sizes or channels < 1, a size above 16384,
+ * face_stride < size * size * channels, an unknown kind, alpha outside (0, 1] for DIRT_ENVMAP_GGX, NULL pointers, an output
+ * that is the input. */
+#define DIRT_ENVMAP_GGX 0u
+#define DIRT_ENVMAP_LAMBERT 1u
+int dirt_envmap_filter_forward(const float *src, float *dst, float *norm, int size, int channels, long long face_stride, float alpha,
+                               unsigned kind, void *stream);
+int dirt_envmap_filter_backward(const float *grad_dst, const float *norm, float *grad_src, int size, int channels,
+                                long long face_stride, float alpha, unsigned kind, void *stream);
 
 /*
  * G-buffer lighting of a deferred shader, fused.  Replaces the torch composition of the reference's shader
