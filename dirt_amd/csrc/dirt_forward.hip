@@ -22,7 +22,7 @@
 //     then -- issued behind them, landing while the coverage loop runs -- the 96-byte heads of their set-up records and their
 //     colours for the shading pass.  Coverage, depth and shading arithmetic are dirt_raster.hip's (dirt_raster_common.h).
 //     Two shapes: four waves per 32 x 32 tile (16 x 16 pixels each), and eight half-size waves for launches of at most 2048
-//     tiles, which end with their heaviest wave.
+//     tiles, which end with their heaviest wave -- there a wave's priority follows the number of candidates it is about to visit.
 #include <type_traits>
 #include "dirt_device.h"
 #include "dirt_launch.h"
@@ -74,6 +74,36 @@ template <class T>
 __device__ __forceinline__ uint32_t lds_address(T* p)
 {
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)p;
+}
+
+// A candidate's coverage record as the coverage loop reads it from LDS: whole 16-byte pieces off one address register --
+// five reads for the record, where field-by-field reads made seven off three address registers.  A wave's time in that loop
+// is its instruction count (profiles/EXPERIMENTS.md, "Raster kernel: the cost of one visit"), and these are per visit.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+static_assert(offsetof(TileRec, bound) == 36 && offsetof(TileRec, box) == 40 && offsetof(TileRec, zp) == 48 && offsetof(TileRec, face) == 72,
+              "fetch_rec reads TileRec by offsets");
+
+// (volatile: the reads stay five ds_read_b128 -- neither narrowed to the fields in use nor re-split; the box's two int16
+// origins are sign-extended by the subtractions that use them)
+__device__ __forceinline__ TileRec fetch_rec(const TileRec* rec)
+{
+    const volatile DIRT_LDS char* q = (const volatile DIRT_LDS char*)rec;
+    const f32x4 p0 = *(const volatile DIRT_LDS f32x4*)(q + 0);    // a[0..2] b[0]
+    const f32x4 p1 = *(const volatile DIRT_LDS f32x4*)(q + 16);   // b[1..2] c[0..1]
+    const u32x4 p2 = *(const volatile DIRT_LDS u32x4*)(q + 32);   // c[2], bound, the box
+    const f64x2 p3 = *(const volatile DIRT_LDS f64x2*)(q + 48);   // zp[0..1]
+    const u32x4 p4 = *(const volatile DIRT_LDS u32x4*)(q + 64);   // zp[2], face, flags
+    TileRec t;
+    t.a[0] = p0.x; t.a[1] = p0.y; t.a[2] = p0.z; t.b[0] = p0.w;
+    t.b[1] = p1.x; t.b[2] = p1.y; t.c[0] = p1.z; t.c[1] = p1.w;
+    t.c[2] = __uint_as_float(p2.x); t.bound = __uint_as_float(p2.y);
+    t.box.i_min = (int16_t)(p2.z & 0xFFFFu); t.box.i_max = (int16_t)(p2.z >> 16);
+    t.box.r_min = (int16_t)(p2.w & 0xFFFFu); t.box.r_max = (int16_t)(p2.w >> 16);
+    t.zp[0] = p3.x; t.zp[1] = p3.y; t.zp[2] = __longlong_as_double((long long)(((unsigned long long)p4.y << 32) | p4.x));
+    t.face = (int32_t)p4.z; t.flags = p4.w;
+    return t;
 }
 
 }  // namespace
@@ -433,6 +463,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
         }
 
         // ---- coverage + depth: every wave visits the candidates whose box touches one of its four blocks ----
+        // (a winner's slot: its list index in round 0; later rounds reuse the slots, and theirs get a bit that puts them past
+        // V2_CAP -- "not in LDS" to the shading pass -- with one scalar OR per visit instead of a test and a select)
+        const int slot_gone = round == 0 ? 0 : 128;
+        static_assert(V2_CAP <= 128, "slot_gone must put a slot past V2_CAP");
         for (int cb = 0; cb < n; cb += 64) {
             const int idx = cb + lane;
             uint32_t mym4 = 0;
@@ -453,26 +487,42 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
             unsigned long long m = __builtin_amdgcn_ballot_w64(mym4 != 0);
             auto visit = [&](const TileRec& t, int k) {
                 const uint32_t m4 = (uint32_t)__builtin_amdgcn_readlane((int)mym4, k);
+                if (NBY == 1) __builtin_assume((m4 & 3u) != 0u);   // (a visited candidate touches the wave's one row of blocks: no test of it)
                 // sample offsets from the face's origin (the top-left pixel of its box): exact small integers
                 float dxl[NB], dyl[NBY];
+                // (the other blocks' offsets by a float add of 8: small integers, exact, one instruction for an integer add and a conversion)
+                dxl[0] = (float)(x0 - (int)t.box.i_min);
+                dyl[0] = (float)((int)t.box.r_min - r0);
 #pragma unroll
-                for (int q = 0; q < NB; ++q) dxl[q] = (float)(x0 + 8 * q - (int)t.box.i_min);
+                for (int q = 1; q < NB; ++q) dxl[q] = dxl[0] + 8.f * (float)q;
 #pragma unroll
-                for (int q = 0; q < NBY; ++q) dyl[q] = (float)((int)t.box.r_min - (r0 + 8 * q));
-                raster_candidate<NB, NBY>(t, recs, round == 0 ? cb + k : V2_CAP, m4, dxl, dyl, px, py, best, cbest);
+                for (int q = 1; q < NBY; ++q) dyl[q] = dyl[0] - 8.f * (float)q;
+                raster_candidate<NB, NBY>(t, recs, (cb + k) | slot_gone, m4, dxl, dyl, px, py, best, cbest);
 #ifdef DIRT_TRACE
                 ++tr_cand;
 #endif
             };
-            // (no software prefetch of the next candidate's record -- two candidates per trip, the second record requested before
-            // the first is worked on, measured the same within noise at K3, K3-2048 and eight scenes per launch for 19 more
-            // registers: profiles/EXPERIMENTS.md round 6)
+            // (The LDS round trip of a record is NOT what a visit waits for: requesting the next candidate's record under the
+            // current one's arithmetic -- the loop rotated, in two stages, no register added -- measured +1.2 ... +2 us on the
+            // kernel at K3, for the dozen scalar instructions the rotation adds per visit; what pays is every instruction a visit
+            // does not issue: profiles/EXPERIMENTS.md, "Raster kernel: the cost of one visit".)
+            // Wave priority by the work ahead, in the eight-wave shape: a launch of resident workgroups ends with its heaviest
+            // wave, and the waves of a SIMD share one instruction issue -- a wave that will visit more candidates than most (6.6
+            // on average at K3, 19 at most) takes its turns ahead of the lighter waves beside it, which have the time to spare.
+            // Back to 0 behind the loop: kept through the shading pass it gave the gain away.  (Not in the four-wave shape, whose
+            // launches run in several rounds of workgroups and end with no particular wave.)
+            if constexpr (WAVES == 8) {
+                const int nv = __popcll(m);
+                if (nv >= 14) __builtin_amdgcn_s_setprio(3);
+                else if (nv >= 10) __builtin_amdgcn_s_setprio(2);
+                else if (nv >= 7) __builtin_amdgcn_s_setprio(1);
+            }
             while (m) {
                 const int k = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                const TileRec t = s_rec[cb + k];
-                visit(t, k);
+                asm("s_bitset0_b64 %0, %1" : "+s"(m) : "s"(k));   // m &= m - 1 as one scalar instruction for three
+                visit(fetch_rec(&s_rec[cb + k]), k);
             }
+            if constexpr (WAVES == 8) __builtin_amdgcn_s_setprio(0);
         }
         FMARK();  // 7 coverage loop done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the shading data has landed

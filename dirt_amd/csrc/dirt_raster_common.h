@@ -39,8 +39,8 @@ struct alignas(16) TileRec {
     float bound;                     // 36
     FaceBox box;                     // 40: (face-local records, make_local_rec: the face's pixel box; its top-left corner is the origin)
     double zp[3];                    // 48: depth plane scaled to the 24-bit range, global coordinates
-    uint32_t flags;                  // 72
-    int32_t face;                    // 76
+    int32_t face;                    // 72: (in front of the flags: with z24 written over them, the 64-bit key (z24 << 32 | face) of the
+    uint32_t flags;                  // 76   depth test is the record's own aligned register pair when it was read as 16-byte pieces)
 };
 static_assert(sizeof(TileRec) == 80, "TileRec is 80 bytes");
 
