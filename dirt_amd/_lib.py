@@ -39,6 +39,7 @@ SHADE_SH_NORMALIZE = 4
 SHADE_SH_PARAMS = 30   # floats of the spherical-harmonic parameter block: 9 coefficients x 3 channels, then the background
 SHADE_PBR_MAX_LIGHTS = 4
 SHADE_PBR_KINDS = {'directional': 0, 'point': 1}   # the bit of a light in light_kinds
+SHADE_IBL_MAX_TABLE = 128   # the largest environment-BRDF table of dirt_shade_ibl_forward
 NORMAL_MAP_ENCODED = 1
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
@@ -68,6 +69,7 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward', 'dirt_shade_albedo_forward', 'dirt_shade_albedo_backward',
            'dirt_shade_sh_scratch_bytes', 'dirt_shade_sh_forward', 'dirt_shade_sh_backward',
            'dirt_shade_pbr_scratch_bytes', 'dirt_shade_pbr_forward', 'dirt_shade_pbr_backward',
+           'dirt_shade_ibl_scratch_bytes', 'dirt_shade_ibl_forward', 'dirt_shade_ibl_backward',
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
            'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward',
@@ -194,6 +196,14 @@ def load():
         lib.dirt_shade_pbr_forward.restype = i
         lib.dirt_shade_pbr_backward.argtypes = [fp] * 9 + [vp, sz, ll, ll] + [i] * 10 + [u, f32, f32, f32, f32, u, vp]
         lib.dirt_shade_pbr_backward.restype = i
+    if hasattr(lib, 'dirt_shade_ibl_forward') or not override:   # image-based G-buffer lighting (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_shade_ibl_scratch_bytes.argtypes = [ll, ll, ll]
+        lib.dirt_shade_ibl_scratch_bytes.restype = sz
+        lib.dirt_shade_ibl_forward.argtypes = [fp] * 8 + [ll, ll, ll] + [i] * 13 + [f32, f32, f32, f32, u, vp]
+        lib.dirt_shade_ibl_forward.restype = i
+        lib.dirt_shade_ibl_backward.argtypes = [fp] * 14 + [vp, sz, ll, ll, ll] + [i] * 13 + [f32, f32, f32, f32, u, vp]
+        lib.dirt_shade_ibl_backward.restype = i
     if hasattr(lib, 'dirt_geometry_forward') or not override:   # fused vertex stage (ABI 4, additive)
         lib.dirt_geometry_scratch_bytes.argtypes = [ll, ll, ll]
         lib.dirt_geometry_scratch_bytes.restype = sz

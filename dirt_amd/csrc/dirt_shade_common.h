@@ -1,5 +1,5 @@
 // dirt_shade_common.h -- what the G-buffer kernels share (dirt_shade.hip and its second unit dirt_shade_albedo.hip: the three
-// reflectance models; dirt_shade_sh.hip: spherical harmonics; dirt_shade_pbr.hip: Cook-Torrance; dirt_normal_map.hip: normal
+// reflectance models; dirt_shade_sh.hip: spherical harmonics; dirt_shade_pbr.hip: Cook-Torrance; dirt_shade_ibl.hip: image-based lighting; dirt_normal_map.hip: normal
 // mapping), each piece written and explained once here.  Device: the tile walk that makes every row of a [pixels, Cg] image
 // leave whole, the channel map it reads, the clamp and its gradient gate.  Host: the refusals every
 // *_check repeats (each file calls them in its own order, with its own checks in between: the order decides which message a
@@ -68,6 +68,32 @@ __device__ __forceinline__ float clamp_gate(const P& p, float pre, float g)
 {
     return (!p.clamp || (pre >= p.lo && pre <= p.hi)) ? g : 0.f;   // closed at both edges; 0 at a NaN
 }
+
+// ---- what the material shaders share (dirt_shade_pbr.hip, dirt_shade_ibl.hip)
+
+// y = x / max(|x|, 1e-12)
+__device__ __forceinline__ void unit3(const float (&x)[3], float (&y)[3], float& len, float& inv)
+{
+    len = sqrtf(dot3(x, x));
+    inv = 1.f / (len < 1.e-12f ? 1.e-12f : len);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) y[j] = x[j] * inv;
+}
+
+// its gradient: gy arrives at y, gx leaves for x
+__device__ __forceinline__ void unit3_backward(const float (&gy)[3], const float (&x)[3], float len, float inv, float (&gx)[3])
+{
+    const float gden = -(dot3(gy, x) * inv) * inv;
+    const float glen = len >= 1.e-12f ? gden : 0.f;            // max passes the gradient at its edge
+    // d |x| / d x = x / |x|, 0 at a zero vector.  The division stands before the choice, not in one arm of it, where it
+    // becomes a branch: a light stays straight-line code
+    const float q = glen / (len == 0.f ? 1.f : len);
+    const float gl = len == 0.f ? 0.f : q;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gx[j] = gy[j] * inv + x[j] * gl;
+}
+
+__device__ __forceinline__ float max0(float x) { return x < 0.f ? 0.f : x; }   // a NaN stays NaN, as torch.clamp leaves it
 
 // dirt_shade.hip: the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a
 // fixed order, one workgroup per value.  One copy for every unit: the others call the launcher.

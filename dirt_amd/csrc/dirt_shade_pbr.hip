@@ -78,30 +78,6 @@ struct PbrLight {
     float x[3], den, D, gl, Vis, w4, w5, F[3], kd[3], B[3];   // B: kd c / pi + D Vis F
 };
 
-// y = x / max(|x|, 1e-12)
-__device__ __forceinline__ void pbr_normalize(const float (&x)[3], float (&y)[3], float& len, float& inv)
-{
-    len = sqrtf(dot3(x, x));
-    inv = 1.f / (len < 1.e-12f ? 1.e-12f : len);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) y[j] = x[j] * inv;
-}
-
-// its gradient: gy arrives at y, gx leaves for x
-__device__ __forceinline__ void pbr_normalize_backward(const float (&gy)[3], const float (&x)[3], float len, float inv, float (&gx)[3])
-{
-    const float gden = -(dot3(gy, x) * inv) * inv;
-    const float glen = len >= 1.e-12f ? gden : 0.f;            // max passes the gradient at its edge
-    // d |x| / d x = x / |x|, 0 at a zero vector.  The division stands before the choice, not in one arm of it, where it
-    // becomes a branch: a light stays straight-line code
-    const float q = glen / (len == 0.f ? 1.f : len);
-    const float gl = len == 0.f ? 0.f : q;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) gx[j] = gy[j] * inv + x[j] * gl;
-}
-
-__device__ __forceinline__ float pbr_max0(float x) { return x < 0.f ? 0.f : x; }   // a NaN stays NaN, as torch.clamp leaves it
-
 // loads a pixel and evaluates what its lights share
 __device__ __forceinline__ void pbr_pixel(const ShadePbrParams& P, const float* __restrict__ prm, long long pix, PbrPixel& px)
 {
@@ -112,10 +88,10 @@ __device__ __forceinline__ void pbr_pixel(const ShadePbrParams& P, const float* 
     const float* __restrict__ mt = P.mat + pix * P.mstride;
     px.r = mt[0]; px.mu = mt[1];
     px.m = P.om >= 0 ? row[P.om] : 1.f;
-    pbr_normalize(px.n, px.N, px.len_n, px.inv_n);
+    unit3(px.n, px.N, px.len_n, px.inv_n);
 #pragma unroll
     for (int j = 0; j < 3; ++j) px.tv[j] = prm[6 + j] - px.p[j];
-    pbr_normalize(px.tv, px.v, px.len_v, px.inv_v);
+    unit3(px.tv, px.v, px.len_v, px.inv_v);
     px.rho = px.r < P.min_roughness ? P.min_roughness : (px.r > 1.f ? 1.f : px.r);
     px.rho2 = px.rho * px.rho;
     px.a2 = px.rho2 * px.rho2;
@@ -125,7 +101,7 @@ __device__ __forceinline__ void pbr_pixel(const ShadePbrParams& P, const float* 
 #pragma unroll
     for (int j = 0; j < 3; ++j) px.F0[j] = P.f0 * px.ommu + px.c[j] * px.mu;
     px.nv_raw = dot3(px.N, px.v);
-    px.nv = pbr_max0(px.nv_raw);
+    px.nv = max0(px.nv_raw);
     px.gv = px.nv * px.omk + px.k;
 }
 
@@ -134,12 +110,12 @@ __device__ __forceinline__ void pbr_light(const float* __restrict__ lp, bool poi
 {
 #pragma unroll
     for (int j = 0; j < 3; ++j) L.tl[j] = point ? lp[j] - px.p[j] : -lp[j];
-    pbr_normalize(L.tl, L.l, L.len_l, L.inv_l);
+    unit3(L.tl, L.l, L.len_l, L.inv_l);
 #pragma unroll
     for (int j = 0; j < 3; ++j) L.th[j] = L.l[j] + px.v[j];
-    pbr_normalize(L.th, L.h, L.len_h, L.inv_h);
+    unit3(L.th, L.h, L.len_h, L.inv_h);
     L.nl_raw = dot3(px.N, L.l); L.nh_raw = dot3(px.N, L.h); L.vh_raw = dot3(px.v, L.h);
-    L.nl = pbr_max0(L.nl_raw); L.nh = pbr_max0(L.nh_raw); L.vh = pbr_max0(L.vh_raw);
+    L.nl = max0(L.nl_raw); L.nh = max0(L.nh_raw); L.vh = max0(L.vh_raw);
     cross3(px.N, L.h, L.x);
     L.den = dot3(L.x, L.x) + px.a2 * (L.nh * L.nh);
     L.D = px.a2 / (PBR_PI * (L.den * L.den));
@@ -302,13 +278,13 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                     gN[j] += (t1[j] + g_nl_raw * L.l[j]) + g_nh_raw * L.h[j];
                     gh[j] += g_nh_raw * px.N[j] + g_vh_raw * px.v[j];
                 }
-                pbr_normalize_backward(gh, L.th, L.len_h, L.inv_h, gth);
+                unit3_backward(gh, L.th, L.len_h, L.inv_h, gth);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     gl[j] = g_nl_raw * px.N[j] + gth[j];
                     gvv[j] += g_vh_raw * L.h[j] + gth[j];
                 }
-                pbr_normalize_backward(gl, L.tl, L.len_l, L.inv_l, gtl);
+                unit3_backward(gl, L.tl, L.len_l, L.inv_l, gtl);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     gp[j] -= point ? gtl[j] : 0.f;
@@ -324,8 +300,8 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                 gN[j] += g_nv_raw * px.v[j];
                 gvv[j] += g_nv_raw * px.N[j];
             }
-            pbr_normalize_backward(gvv, px.tv, px.len_v, px.inv_v, gtv);
-            pbr_normalize_backward(gN, px.n, px.len_n, px.inv_n, gn);
+            unit3_backward(gvv, px.tv, px.len_v, px.inv_v, gtv);
+            unit3_backward(gN, px.n, px.len_n, px.inv_n, gn);
             float gmu = 0.f;
 #pragma unroll
             for (int j = 0; j < 3; ++j) {

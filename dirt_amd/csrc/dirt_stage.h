@@ -1,6 +1,6 @@
 // dirt_stage.h -- what the fused stages around the rasteriser share, each piece written and explained once here:
-//   texture look-up   (dirt_texture.hip, dirt_texture_mip.hip, dirt_texture_cube.hip; what only those three share -- the per-look-up arithmetic, the backward tile scheme, the pixel grid -- is dirt_texture_common.h);
-//   G-buffer lighting (dirt_shade.hip, dirt_shade_sh.hip, dirt_shade_pbr.hip; what only these and dirt_normal_map.hip share -- the tile walk, the clamp, the host checks, the backward's epilogue -- is dirt_shade_common.h);
+//   texture look-up   (dirt_texture.hip, dirt_texture_mip.hip, dirt_texture_cube.hip; what only those three share -- the per-look-up arithmetic, the backward tile scheme, the pixel grid -- is dirt_texture_common.h; a cube look-up's own arithmetic, which dirt_shade_ibl.hip uses too, is dirt_texture_cube.h);
+//   G-buffer lighting (dirt_shade.hip, dirt_shade_sh.hip, dirt_shade_pbr.hip, dirt_shade_ibl.hip; what only these and dirt_normal_map.hip share -- the tile walk, the clamp, the host checks, the backward's epilogue -- is dirt_shade_common.h);
 //   vertex stage      (dirt_geometry.hip);
 //   skinning          (dirt_skin.hip: Float3 / Float4 / load3 / store3, dot3, the wave sum, the four-wave fold, the error channel, the scratch check);
 //   kinematics        (dirt_kinematics.hip: Float4 / load3 / store3, dot3, the error channel, the scratch check);

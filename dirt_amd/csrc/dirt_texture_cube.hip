@@ -18,93 +18,17 @@
 //     (sc, tc, a) with its own n.
 //  6. Gradients to the cube, the directions (that of (sc / a, tc / a): orthogonal to the direction) and lod.
 //
+// The per-look-up arithmetic of spec 2-4 and 6 is dirt_texture_cube.h, which dirt_shade_ibl.hip shares; that unit also launches
+// this one's backward kernels (cube_backward_launch, at the end of this file) for the scatter into its two cubes.
 // Kernels: the forward one look-up per lane.  The backward on 16 x 16-pixel tiles (256 x 1 of a flat list): a bilinear / nearest tile
 // whose valid look-ups lie on ONE face and whose taps' bounding box fits TEX_PATCH texels sums in an LDS patch and sends each touched
 // texel to memory once; a tile that straddles a face edge, or whose box is larger, adds straight to memory.  The trilinear backward
 // does the same with a patch per touched level (at most two adjacent ones) of the pyramid-shaped scratch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "dirt_texture_common.h"
+#include "dirt_texture_cube.h"
 
 namespace dirt {
-
-int mip_level_count(int Ht, int Wt, int max_level);   // dirt_texture_mip.hip
-
-struct CubeParams {
-    const float* pyr;        // [6, face_floats]: a packed pyramid per face (one level: the cube itself)
-    const float* dirs;       // n directions (x, y, z), `dir_stride` floats apart
-    const float* lod;        // n levels of detail, or nullptr (level 0 only)
-    long long n, face_floats;
-    int N, Ct, L, dir_stride, gdir_stride;
-    float lod_bias;
-    unsigned flags;
-    float* out;              // [n, Ct]
-    const float* grad_out;   // [n, Ct]
-    float* grad_pyr;         // [6, face_floats], accumulated into (cleared by the caller of the kernel)
-    float* grad_dirs;        // n triples `gdir_stride` apart, or nullptr
-    float* grad_lod;         // n, or nullptr
-};
-
-// The float offset of the level of size nk in a face's packed pyramid [N x N, ...] x Ct: the levels before it hold
-// N^2 (1 + 1/4 + ...) = 4 (N^2 - nk^2) / 3 texels (a level exists only while the one below is even: N = nk 2^k, and 4^k - 1 is a multiple of 3)
-__host__ __device__ __forceinline__ long long cube_level_offset(int N, int nk, int Ct)
-{
-    return ((long long)N * N - (long long)nk * nk) / 3 * 4 * Ct;
-}
-
-// spec 2, 3: the face of a direction, (sc, tc) over a, and what the gradient needs to go back
-struct CubeLook {
-    bool valid, pos;   // pos: the major component is > 0
-    int major;         // 0, 1, 2 = x, y, z
-    float s, t, a;     // sc / a, tc / a, the magnitude of the major component
-    __device__ __forceinline__ int face() const { return 2 * major + (pos ? 0 : 1); }
-};
-__device__ __forceinline__ CubeLook cube_look(float x, float y, float z)
-{
-    CubeLook q;
-    const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
-    const bool mx = ax >= ay && ax >= az, my = !mx && ay >= az;
-    q.major = mx ? 0 : (my ? 1 : 2);
-    q.a = mx ? ax : (my ? ay : az);
-    q.pos = (mx ? x : (my ? y : z)) > 0.f;
-    q.valid = ax < INFINITY && ay < INFINITY && az < INFINITY && q.a > 0.f;   // (a NaN fails its comparison)
-    const float sc = mx ? (q.pos ? -z : z) : (my ? x : (q.pos ? x : -x));
-    const float tc = my ? (q.pos ? z : -z) : -y;
-    q.s = q.valid ? sc / q.a : 0.f;
-    q.t = q.valid ? tc / q.a : 0.f;
-    return q;
-}
-
-// spec 4: sc / a or tc / a -> the index at a level of size n, and d index / d (sc / a)
-__device__ __forceinline__ float cube_index(float s, int n, float& d)
-{
-    const float x = ((s + 1.f) * 0.5f) * (float)n - 0.5f, top = (float)(n - 1);
-    d = x >= 0.f && x <= top ? 0.5f * (float)n : 0.f;
-    return x < 0.f ? 0.f : (x > top ? top : x);
-}
-
-// the taps of a look-up at a level of size n; 'nearest': one tap of weight 1
-__device__ __forceinline__ Taps cube_taps(const CubeLook& q, int n, bool nearest, float& drow, float& dcol)
-{
-    const float row = cube_index(q.t, n, drow), col = cube_index(q.s, n, dcol);
-    Taps k = bilinear_taps(row, col, n, n);
-    if (nearest) {
-        k.r0 = k.r1 = texel_index(row + 0.5f, n); k.c0 = k.c1 = texel_index(col + 0.5f, n);
-        k.fr = 0.f; k.fc = 0.f; k.wr0 = 1.f; k.wc0 = 1.f;
-    }
-    return k;
-}
-
-// dL/d(sc / a), dL/d(tc / a) -> dL/d(x, y, z) (spec 6): sc and tc over a, and a = |major component|
-__device__ __forceinline__ void cube_direction_gradient(const CubeLook& q, float gs, float gt, float (&g)[3])
-{
-    const float g_sc = gs / q.a, g_tc = gt / q.a;
-    const float g_a = -((gs * q.s + gt * q.t) / q.a);
-    const float g_m = q.pos ? g_a : -g_a;
-    if (q.major == 0) { g[0] = g_m; g[1] = -g_tc; g[2] = q.pos ? -g_sc : g_sc; }
-    else if (q.major == 1) { g[0] = g_sc; g[1] = g_m; g[2] = q.pos ? g_tc : -g_tc; }
-    else { g[0] = q.pos ? g_sc : -g_sc; g[1] = -g_tc; g[2] = g_m; }
-}
 
 // ---- forward: one look-up per lane, CT channels per access ----
 template <int CT>
@@ -412,19 +336,27 @@ int dirt_texture_cube_backward(const float* pyramid, const float* directions, co
     const dirt::TileGrid t = dirt::tile_grid(rows, cols);
     if (t.tiles > 0x7fffffffll || cols > 0x7fffffffll || rows > 0x7fffffffll) TEX_FAIL("%s: pixel grid too large (rows=%lld cols=%lld)", who, rows, cols);
     if (!grad_pyramid) return dirt::stage_ok(report);   // (n == 0 without a gradient buffer: nothing to clear)
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = dirt::clear_floats(grad_pyramid, 6 * p.face_floats, s);
-    if (e == hipSuccess && n > 0) {
-        p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_dirs = grad_directions; p.grad_lod = grad_lod; p.gdir_stride = grad_dir_stride;
-        const bool a16 = (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
-        dirt::dispatch_channels(channels, a16, [&](auto ct) {
-            constexpr int CT = decltype(ct)::value;
-            if (lod) hipLaunchKernelGGL(dirt::texture_cube_backward_mip_kernel<CT>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
-            else hipLaunchKernelGGL(dirt::texture_cube_backward_kernel<CT>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
-        });
-        e = hipGetLastError();
-    }
-    return dirt::stage_hip(report, who, e);
+    p.grad_out = grad_out; p.grad_pyr = grad_pyramid; p.grad_dirs = grad_directions; p.grad_lod = grad_lod; p.gdir_stride = grad_dir_stride;
+    return dirt::stage_hip(report, who, dirt::cube_backward_launch(p, rows, cols, reinterpret_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"
+
+namespace dirt {
+
+// (dirt_texture_cube.h)
+hipError_t cube_backward_launch(const CubeParams& p, long long rows, long long cols, hipStream_t s)
+{
+    hipError_t e = clear_floats(p.grad_pyr, 6 * p.face_floats, s);
+    if (e != hipSuccess || p.n <= 0) return e;
+    const TileGrid t = tile_grid(rows, cols);
+    const bool a16 = (reinterpret_cast<uintptr_t>(p.grad_out) & 15u) == 0;
+    dispatch_channels(p.Ct, a16, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        if (p.lod) hipLaunchKernelGGL(texture_cube_backward_mip_kernel<CT>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
+        else hipLaunchKernelGGL(texture_cube_backward_kernel<CT>, dim3((unsigned)t.tiles), dim3(256), 0, s, p, (int)rows, (int)cols, t.tw, t.th, (int)t.tiles_x);
+    });
+    return hipGetLastError();
+}
+
+}  // namespace dirt

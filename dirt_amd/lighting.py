@@ -232,6 +232,135 @@ def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, me
     return total
 
 
+# ---- split-sum image-based lighting.  Not in the reference: the material of `cook_torrance` under an environment.  The lobe's
+# integral against the environment is split into the environment filtered by the lobe (`texture.prefilter_cube`) times the
+# lobe's own integral against a white environment, which depends on (n . v, roughness) alone and is tabulated once by
+# `environment_brdf`.  These are the specifications `shading.shade_gbuffer_ibl` implements per pixel.
+
+def environment_brdf(size=32, samples=(512, 128)):
+    """The split-sum scale and bias of `cook_torrance`'s specular lobe -> [size, size, 2] float32 (A, B): texel (i, j) holds
+    nv = (j + 0.5) / size (columns) and rho = (i + 0.5) / size (rows), and with n = (0, 0, 1), v = (sqrt(1 - nv^2), 0, nv),
+    a2, k, D, Vis as in `cook_torrance` and Fc = (1 - vh)^5
+
+        A = integral of D Vis (1 - Fc) nl dl        B = integral of D Vis Fc nl dl        over the hemisphere of l,
+
+    so that a constant environment of radiance 1 reflects F0 A + B.  Computed in float64 on the CPU by a fixed quadrature, a
+    stratified GGX importance sampling of the half vector h: with u the distribution function of the density D nh,
+    tan^2 theta_h = a2 u / (1 - u), and l = 2 vh h - v has the density D nh / (4 vh), which cancels D.  The strata are the
+    samples[0] x samples[1] cells of equal size in (y, phi), y = log(u / (1 - u)) in [-40, 40] (du = u (1 - u) dy) and phi over
+    the half circle (the integrand is even in phi), sampled at their midpoints: equal cells in u itself would put the whole
+    tail of a narrow lobe, every theta_h beyond a2 samples[0], into the last one.  Not random, not differentiable, the same
+    bits on every call."""
+    if isinstance(size, bool) or not isinstance(size, int) or size < 2:
+        raise ValueError('environment_brdf: size must be an int >= 2, got %r' % (size,))
+    try:
+        ny, nphi = (int(s) for s in samples)
+    except (TypeError, ValueError):
+        raise ValueError('environment_brdf: samples must be two positive ints (strata of y and of phi), got %r' % (samples,))
+    if ny < 1 or nphi < 1:
+        raise ValueError('environment_brdf: samples must be two positive ints (strata of y and of phi), got %r' % (samples,))
+    f64 = torch.float64
+    centres = (torch.arange(size, dtype=f64) + 0.5) / size
+    span = 40.
+    y = (((torch.arange(ny, dtype=f64) + 0.5) / ny * 2. - 1.) * span)[:, None]
+    du = torch.sigmoid(y) * torch.sigmoid(-y) * (2. * span / ny)    # u (1 - u) dy
+    phi = ((torch.arange(nphi, dtype=f64) + 0.5) / nphi * torch.pi)[None, :]
+    nv = centres[None, None, :]                            # [1, 1, size]
+    vx = torch.sqrt(1. - nv * nv)
+    out = torch.empty((size, size, 2), dtype=f64)
+    for i in range(size):
+        rho = centres[i]
+        a2 = (rho * rho) * (rho * rho)
+        k = (rho + 1.) * (rho + 1.) / 8.
+        tan2 = a2 * torch.exp(y)
+        nh = torch.rsqrt(1. + tan2)
+        sin_h = torch.sqrt(tan2) * nh
+        hx = sin_h * torch.cos(phi)                        # [ny, nphi]; h = (hx, hy, nh), v = (vx, 0, nv): hy drops out of every product
+        vh = hx[..., None] * vx + nh[..., None] * nv       # [ny, nphi, size]
+        nl = 2. * vh * nh[..., None] - nv
+        lit = (vh > 0) & (nl > 0)
+        vis = 0.25 / ((nl * (1. - k) + k) * (nv * (1. - k) + k))
+        w = torch.where(lit, 4. * vis * nl * vh / nh[..., None], torch.zeros((), dtype=f64)) * du[..., None]
+        t = 1. - vh
+        fc = ((t * t) * (t * t)) * t
+        out[i, :, 0] = (w * (1. - fc)).mean(dim=1).sum(dim=0)
+        out[i, :, 1] = (w * fc).mean(dim=1).sum(dim=0)
+    return out.to(torch.float32)
+
+
+def _table_lookup(table, row, col):
+    """table [S, S, C], fractional indices row, col [...] inside it -> [..., C]: the bilinear blend of `texture.sample_cube`"""
+    s = table.shape[0]
+    fr0, fc0 = torch.floor(row), torch.floor(col)
+    fr, fc = (row - fr0)[..., None], (col - fc0)[..., None]
+    r, c = fr0.to(torch.int64), fc0.to(torch.int64)
+
+    def fetch(rows, cols):
+        return table[rows.clamp(0, s - 1), cols.clamp(0, s - 1)]
+
+    return (fetch(r, c) * (1. - fc) * (1. - fr) + fetch(r, c + 1) * fc * (1. - fr)
+            + fetch(r + 1, c) * (1. - fc) * fr + fetch(r + 1, c + 1) * fc * fr)
+
+
+def image_based_lighting(vertex_positions, vertex_normals, vertex_colors, roughness, metalness, camera_position, pyramid_levels,
+                         irradiance, brdf, intensity=(1., 1., 1.), min_roughness=0.04, dielectric_f0=0.04):
+    """Metallic-roughness reflectance under an environment, by the split sum.
+    positions, normals, colours (albedo) [*, V, 3]; roughness, metalness [*, V]; camera_position, intensity [*, 3];
+    pyramid_levels: the L levels [6, n_k, n_k, 3] of a GGX-prefiltered environment (`texture.prefilter_cube(...).level(k)`,
+    level k filtered at roughness k / (L - 1)); irradiance [6, M, M, 3] (`texture.convolve_cube(kind='lambert')`);
+    brdf [S, S, 2] (`environment_brdf`) -> [*, V, 3].  Per point (every normalisation is torch.nn.functional.normalize,
+    x / max(|x|, 1e-12); the cube look-ups are `texture.sample_cube(cube, *texture.directions_to_cube_indices(d, n))`):
+
+        n^ = normalize(n)        v = normalize(cam - p)        nv_raw = n^ . v        nv = max(nv_raw, 0)
+        rho = clamp(r, min_roughness, 1)                        F0_j = dielectric_f0 (1 - mu) + c_j mu
+        R = 2 nv_raw n^ - v                                     (the view vector mirrored at n^; the unclamped product)
+        (A, B) = bilinear look-up of brdf at col = clamp(nv S - 0.5, 0, S - 1), row = clamp(rho S - 0.5, 0, S - 1)
+        S_j = F0_j A + B
+        lam = rho (L - 1), l = floor(lam), f = lam - l:  spec_j = (1 - f) level_l(R) + f level_{l+1}(R)
+        E_j = irradiance(n)                                     (the raw normal: an all-zero n is invalid and gives 0)
+        L_j = intensity_j ((1 - S_j)(1 - mu) c_j E_j + S_j spec_j)
+
+    The diffuse weight is (1 - S_j)(1 - mu): what the specular lobe reflects of a white environment is not available to the
+    diffuse one.  Differentiable in everything but the table's use as an index; works in float64; min_roughness in (0, 1] and
+    dielectric_f0 in [0, 1] are python numbers."""
+    from .texture import directions_to_cube_indices, sample_cube
+    min_roughness, dielectric_f0 = float(min_roughness), float(dielectric_f0)
+    if not 0. < min_roughness <= 1.:
+        raise ValueError('min_roughness must be > 0 and <= 1, got %r' % min_roughness)
+    if not 0. <= dielectric_f0 <= 1.:
+        raise ValueError('dielectric_f0 must lie in [0, 1], got %r' % dielectric_f0)
+    levels = list(pyramid_levels)
+    if not levels:
+        raise ValueError('pyramid_levels must hold at least one level')
+    p = _as(vertex_positions, torch.zeros((), dtype=torch.float32))
+    n, c, r, mu, cam, inten = (_as(x, p) for x in (vertex_normals, vertex_colors, roughness, metalness, camera_position, intensity))
+    table = _as(brdf, p)
+    normalize = lambda x: torch.nn.functional.normalize(x, dim=-1, eps=1.e-12)   # noqa: E731
+    nh_ = normalize(n)
+    v = normalize(cam[..., None, :] - p)
+    rho = torch.clamp(r, min_roughness, 1.)
+    mu1 = mu[..., None]
+    f0 = dielectric_f0 * (1. - mu1) + c * mu1
+    nv_raw = torch.sum(nh_ * v, dim=-1)
+    nv = torch.clamp(nv_raw, min=0.)
+    refl = (2. * nv_raw)[..., None] * nh_ - v
+    size = int(table.shape[0])
+    ab = _table_lookup(table, (rho * float(size) - 0.5).clamp(0., float(size - 1)), (nv * float(size) - 0.5).clamp(0., float(size - 1)))
+    s = f0 * ab[..., :1] + ab[..., 1:]
+    top = float(len(levels) - 1)
+    lam = torch.clamp(rho * top, 0., top)
+    low = torch.floor(lam)
+    f = (lam - low)[..., None]
+    l0 = low.to(torch.int64)
+    l1 = (l0 + 1).clamp(max=len(levels) - 1)
+    looked = torch.stack([sample_cube(_as(lv, p), *directions_to_cube_indices(refl, int(lv.shape[1]))) for lv in levels])   # [L, *, V, 3]
+    pick = lambda l: torch.gather(looked, 0, l[None, ..., None].expand((1,) + tuple(looked.shape[1:])))[0]   # noqa: E731
+    spec = (1. - f) * pick(l0) + f * pick(l1)
+    irr = _as(irradiance, p)
+    e = sample_cube(irr, *directions_to_cube_indices(n, int(irr.shape[1])))
+    return inten[..., None, :] * (((1. - s) * (1. - mu1)) * c * e + s * spec)
+
+
 # ---- tangent-space normal mapping.  Not in the reference: per-vertex tangent frames from the uvs and the per-pixel frame
 # that turns a normal-map texel into a shading normal.  These are the specifications `geometry.vertex_tangents` and
 # `shading.perturb_normals` implement (DESIGN.md §7g).

@@ -522,6 +522,141 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
     return (offsets, kinds, tuple(scalars), lo, hi, flags) + _split_slots(_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights), slots)
 
 
+# ---- split-sum image-based lighting (dirt_shade_ibl.hip)
+
+class _ShadeGBufferIBL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, block, colors, material, packed, irradiance, brdf, meta):
+        """colors / material: None (channels of the G-buffer) or float32 [..., 3] / [..., 2] beside it, read in place under
+        `_stage.rows_in_place`; packed [6, floats], irradiance [6, M, M, 3], brdf [S, S, 2]: float32"""
+        lib = _lib.load()
+        scenes, rows, cols, cg, offsets, sizes, scalars, lo, hi, flags = meta
+        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
+        block, packed, irradiance, brdf = block.contiguous(), packed.contiguous(), irradiance.contiguous(), brdf.contiguous()
+        csrc, cstride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+        msrc, mstride = _stage.rows_in_place(material, 2) if material is not None else (None, 0)
+        if scenes * rows * cols:
+            _stage.call(lib.dirt_shade_ibl_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(),
+                        packed.data_ptr(), irradiance.data_ptr(), brdf.data_ptr(), out.data_ptr(), scenes, rows, cols, cg, cstride, mstride,
+                        *offsets, int(block.shape[0]), *sizes, *scalars, lo, hi, flags)
+        ctx.save_for_backward(gbuffer, block, csrc, msrc, packed, irradiance, brdf)
+        ctx.meta, ctx.strides = meta, (cstride, mstride)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, block, csrc, msrc, packed, irradiance, brdf = ctx.saved_tensors
+        scenes, rows, cols, cg, offsets, sizes, scalars, lo, hi, flags = ctx.meta
+        dev = gbuffer.device
+        empty = not scenes * rows * cols
+        want_p = ctx.needs_input_grad[1]
+        want_c = csrc is not None and ctx.needs_input_grad[2]
+        want_m = msrc is not None and ctx.needs_input_grad[3]
+        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], empty)
+        # dense [..., 3] and [..., 2], whatever the tensors' strides
+        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None
+        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (2,), dtype=torch.float32) if want_m else None
+        # the cubes' gradients: cleared by the call
+        grad_s = torch.empty_like(packed) if ctx.needs_input_grad[4] else None
+        grad_i = torch.empty_like(irradiance) if ctx.needs_input_grad[5] else None
+        if empty:
+            return (grad_g, grad_p, grad_c.zero_() if want_c else None, grad_m.zero_() if want_m else None,
+                    grad_s.zero_() if grad_s is not None else None, grad_i.zero_() if grad_i is not None else None, None, None)
+        grad_out = grad_out.to(torch.float32).contiguous()
+        nbytes = lib.dirt_shade_ibl_scratch_bytes(scenes, rows, cols) if want_p or grad_s is not None or grad_i is not None else 0
+        _stage.call(lib.dirt_shade_ibl_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), packed.data_ptr(),
+                    irradiance.data_ptr(), brdf.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p),
+                    _ptr(grad_s), _ptr(grad_i), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, rows, cols, cg, *ctx.strides, *offsets,
+                    int(block.shape[0]), *sizes, *scalars, lo, hi, flags)
+        return grad_g, grad_p, grad_c, grad_m, grad_s, grad_i, None, None
+
+
+def shade_gbuffer_ibl(gbuffer, specular, irradiance, brdf, *, colors, material, normals, positions, camera_position, mask=None,
+                      intensity=(1., 1., 1.), background=(0., 0., 0.), clamp=(0., 1.), min_roughness=0.04, dielectric_f0=0.04):
+    """Lights a G-buffer per pixel with the material of `shade_gbuffer_pbr` under an environment, by the split sum, in one
+    kernel, differentiably: what `lighting.image_based_lighting` computes per vertex (its docstring is the specification),
+    composited and clamped as `shade_gbuffer` does.
+
+    specular: the 3-channel `CubePyramid` of `texture.prefilter_cube(environment)` with its default roughness ramp k / (L - 1),
+        looked up at the mirrored view vector at lod = roughness (L - 1).
+    irradiance: [6, M, M, 3], `texture.convolve_cube(environment_mip, kind='lambert')`, looked up at the normal as it stands in
+        the G-buffer: an all-zero normal -- a background pixel -- gets no irradiance.
+    brdf: [S, S, 2] with 2 <= S <= 128 on the G-buffer's device, `lighting.environment_brdf(S).to(device)`: built once per fit.
+    gbuffer, colors, material, normals, positions, mask, background, camera_position, clamp, min_roughness, dielectric_f0: as
+        in `shade_gbuffer_pbr`.  intensity: the environment's scale per channel; like background and camera_position 3 numbers
+        or a tensor [3], or [B, 3] with a [B, H, W, Cg] G-buffer, differentiable.
+    One cube pair serves every scene of a batch.
+
+    Returns [..., 3]:  clamp(L * m + background * (1 - m), lo, hi)  with
+    L = intensity ((1 - S)(1 - mu) c E + S spec), S = F0 A + B.  Gradients are those of torch's autograd for that composition
+    (the kinks as in `shade_gbuffer_pbr`; an invalid direction adds nothing) and go to the G-buffer, the colour and material
+    tensors, the three parameters, `specular.packed` (and through it the environment) and `irradiance`; none goes to `brdf`.
+    The cubes' gradients are summed with float atomics where a 16 x 16 tile of pixels straddles faces: they are not the same
+    bits on every run, everything else is.
+
+    Direct lights are added by the caller: `shade_gbuffer_pbr(..., clamp=None) + shade_gbuffer_ibl(..., clamp=None)`, then
+    one clamp."""
+    from .texture import CubePyramid, _cube_level
+    who = 'shade_gbuffer_ibl'
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, who)
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('%s expects a float32 gbuffer, got %s' % (who, gbuffer.dtype))
+    dev = gbuffer.device
+    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    if not isinstance(specular, CubePyramid):
+        raise ValueError('%s expects specular to be the CubePyramid of prefilter_cube, got %s' % (who, type(specular).__name__))
+    if specular.roughness is None:
+        raise ValueError('%s: specular is a box-filtered pyramid (roughness None): the look-up at lod = roughness (L - 1) needs the '
+                         'levels prefilter_cube convolves' % who)
+    ramp = tuple(k / (specular.levels - 1) for k in range(specular.levels)) if specular.levels > 1 else (0.0,)
+    if specular.roughness != ramp:
+        raise ValueError('%s: specular was filtered at the roughnesses %r, the look-up at lod = roughness (L - 1) needs the default '
+                         'ramp k / (L - 1) of prefilter_cube' % (who, specular.roughness))
+    if specular.channels != 3:
+        raise ValueError('%s: specular has %d channels, an environment has 3' % (who, specular.channels))
+    top, top_size = _cube_level(specular.size, 3, specular.levels - 1)
+    if not isinstance(specular.packed, torch.Tensor) or tuple(specular.packed.shape) != (6, top + top_size * top_size * 3):
+        raise ValueError('%s: specular.packed must be [6, %d], the %d levels of a %d x %d x 3 face, got %s'
+                         % (who, top + top_size * top_size * 3, specular.levels, specular.size, specular.size,
+                            tuple(getattr(specular.packed, 'shape', ()))))
+    if not isinstance(irradiance, torch.Tensor) or irradiance.dim() != 4 or irradiance.shape[0] != 6 or irradiance.shape[1] != irradiance.shape[2] \
+            or irradiance.shape[3] != 3 or 0 in irradiance.shape or not irradiance.is_floating_point():
+        raise ValueError('%s expects irradiance to be a floating-point tensor [6, size, size, 3], got %s'
+                         % (who, tuple(getattr(irradiance, 'shape', ()))))
+    if not isinstance(brdf, torch.Tensor) or brdf.dim() != 3 or brdf.shape[0] != brdf.shape[1] or brdf.shape[2] != 2 \
+            or not 2 <= brdf.shape[0] <= _lib.SHADE_IBL_MAX_TABLE or not brdf.is_floating_point():
+        raise ValueError('%s expects brdf to be a floating-point tensor [S, S, 2] with 2 <= S <= %d (lighting.environment_brdf), got %s'
+                         % (who, _lib.SHADE_IBL_MAX_TABLE, tuple(getattr(brdf, 'shape', ()))))
+    for name, t in (('specular', specular.packed), ('irradiance', irradiance), ('brdf', brdf)):
+        if t.device != dev:
+            raise ValueError('%s is on %s, the G-buffer on %s' % (name, t.device, dev))
+    offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('material', material, 2, True), ('normals', normals, 3, True),
+                                         ('positions', positions, 3, True), ('mask', mask, 1, False)))
+    scalars = []
+    for name, x, text, ok in (('min_roughness', min_roughness, '> 0 and <= 1', lambda v: 0. < v <= 1.),
+                              ('dielectric_f0', dielectric_f0, 'in [0, 1]', lambda v: 0. <= v <= 1.)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not ok(float(x)):
+            raise ValueError('%s must be a number %s, got %r' % (name, text, x))
+        scalars.append(float(x))
+    if camera_position is None:
+        raise ValueError('%s needs camera_position' % who)
+    lo, hi = _clamp_bounds(clamp)
+    flags = _lib.SHADE_CLAMP if clamp is not None else 0
+    # the parameter block: [1 or B, 9] in the layout of `_param_head`, the intensity in the ambient slot
+    slots = [(0, _value(intensity, 3, 'intensity', dev, batch))] + _param_head((0., 0., 0.), background, camera_position, dev, batch)[1:]
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_ibl')
+    block = _splice_block(dev, *_split_slots(_lib.SHADE_PARAM_HEAD, slots))
+    # a scene's pixel grid: the image's rows and columns, one row for a flat list
+    rows, cols = (int(gbuffer.shape[-3]), int(gbuffer.shape[-2])) if gbuffer.dim() >= 3 else (1, pixels)
+    sizes = (specular.size, specular.levels, int(irradiance.shape[1]), int(brdf.shape[0]))
+    meta = (scenes, rows, cols, cg, tuple(offsets), sizes, tuple(scalars), lo, hi, flags)
+    as_input = lambda x: x.to(torch.float32) if isinstance(x, torch.Tensor) else None   # noqa: E731
+    return _ShadeGBufferIBL.apply(g, block, as_input(colors), as_input(material), specular.packed.to(torch.float32),
+                                  irradiance.to(torch.float32), brdf.to(torch.float32), meta)
+
+
 # ---- tangent-space normal mapping (dirt_normal_map.hip)
 
 class _PerturbNormals(torch.autograd.Function):

@@ -482,6 +482,45 @@ int dirt_shade_pbr_backward(const float *gbuffer, const float *colors, const flo
                             float min_roughness, float dielectric_f0, float clamp_lo, float clamp_hi, unsigned flags, void *stream);
 
 /*
+ * Split-sum image-based lighting of a G-buffer, fused (the specification is DESIGN.md §7b and
+ * dirt_amd/lighting.py::image_based_lighting).  Per pixel, with the attributes, N, v, rho and F0_j of dirt_shade_pbr_forward:
+ *     nv_raw = N . v   nv = max(nv_raw, 0)   R = 2 nv_raw N - v
+ *     (A, B) = bilinear look-up of table [S, S, 2] at column clamp(nv S - 0.5, 0, S - 1), row clamp(rho S - 0.5, 0, S - 1)
+ *     S_j = F0_j A + B
+ *     spec_j = the trilinear look-up of dirt_texture_cube_forward in `pyramid` at R, lod = rho (levels - 1)
+ *     E_j    = its bilinear look-up in `irradiance` at n (not normalised: an all-zero normal gives 0)
+ *     out_j = clamp(intensity_j ((1 - S_j)(1 - mu) c_j E_j + S_j spec_j) m + background_j (1 - m), clamp_lo, clamp_hi)
+ *   gbuffer [scenes, rows * cols, Cg], colors, material, the channel offsets, min_roughness, dielectric_f0, the clamp and flags:
+ *   as dirt_shade_pbr_forward.  rows x cols: a scene's pixel grid (a flat list: rows = 1); the backward scatters into the
+ *   cubes on its 16 x 16 tiles.  params [param_scenes, DIRT_SHADE_PARAM_HEAD]: intensity[3], background[3], camera[3].
+ *   pyramid [6, floats]: a packed pyramid per face of `levels` levels (1 .. the level count of `size`) and 3 channels, level 0
+ *   of size `size`, laid out as dirt_texture_mip_build_batch makes it; irradiance [6, irradiance_size, irradiance_size, 3];
+ *   table [table_size, table_size, 2], table_size in 2..DIRT_SHADE_IBL_MAX_TABLE.  One set serves every scene.
+ * Backward: grad_gbuffer, grad_colors, grad_material, grad_params as dirt_shade_pbr_backward's; grad_pyramid like pyramid and
+ * grad_irradiance like irradiance, cleared and then added into by the kernels of dirt_texture_cube_backward (float atomics
+ * where a tile straddles faces: not the same bits on every run; everything else is).  Each may be NULL and is then not
+ * computed -- all six NULL: success, nothing is launched.  grad_params, grad_pyramid and grad_irradiance need `scratch` of
+ * dirt_shade_ibl_scratch_bytes(scenes, rows, cols) bytes (0: invalid sizes).  No gradient goes to the table.  Zero scenes or
+ * pixels: success, the cubes' gradients are cleared.  Failures: dirt_last_error().
+ */
+#define DIRT_SHADE_IBL_MAX_TABLE 128
+size_t dirt_shade_ibl_scratch_bytes(long long scenes, long long rows, long long cols);
+int dirt_shade_ibl_forward(const float *gbuffer, const float *colors, const float *material, const float *params,
+                           const float *pyramid, const float *irradiance, const float *table, float *out, long long scenes,
+                           long long rows, long long cols, int Cg, int color_stride, int material_stride, int off_colors,
+                           int off_material, int off_normals, int off_positions, int off_mask, int param_scenes, int size,
+                           int levels, int irradiance_size, int table_size, float min_roughness, float dielectric_f0,
+                           float clamp_lo, float clamp_hi, unsigned flags, void *stream);
+int dirt_shade_ibl_backward(const float *gbuffer, const float *colors, const float *material, const float *params,
+                            const float *pyramid, const float *irradiance, const float *table, const float *grad_out,
+                            float *grad_gbuffer, float *grad_colors, float *grad_material, float *grad_params, float *grad_pyramid,
+                            float *grad_irradiance, void *scratch, size_t scratch_bytes, long long scenes, long long rows,
+                            long long cols, int Cg, int color_stride, int material_stride, int off_colors, int off_material,
+                            int off_normals, int off_positions, int off_mask, int param_scenes, int size, int levels,
+                            int irradiance_size, int table_size, float min_roughness, float dielectric_f0, float clamp_lo,
+                            float clamp_hi, unsigned flags, void *stream);
+
+/*
  * The vertex stage in front of the rasteriser, fused.  Replaces the torch composition of the reference's samples
  * (samples/deferred.py:40-51): world4 = v4 @ model, clip = world4 @ view_projection (row vectors), and the vertex normals
  * of dirt/lighting.py:21-28,31-89 (`vertex_normals`) or, with DIRT_GEOM_PRE_SPLIT, of dirt/lighting.py:97-129
