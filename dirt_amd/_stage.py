@@ -125,6 +125,14 @@ def grad_outputs(operands, want, empty_call):
     return [g.zero_() if g is not None else None for g in grads] if empty_call else grads
 
 
+def dense_grads(grad_out, widths, want, empty_call):
+    """The gradient outputs of tensors that stand beside a G-buffer (colours, material, a normal map: `widths` their channels):
+    dense float32 [..., width] over the pixels of `grad_out`, whatever the tensors' own strides; None where not wanted,
+    zeroed for an empty call, as `grad_outputs`."""
+    grads = [grad_out.new_empty(tuple(grad_out.shape[:-1]) + (w,), dtype=torch.float32) if on else None for w, on in zip(widths, want)]
+    return [g.zero_() if g is not None else None for g in grads] if empty_call else grads
+
+
 def float32_contiguous(*grads):
     """The incoming gradients of a backward with several outputs, as the kernels read them; None (an output nobody used) stays
     None."""

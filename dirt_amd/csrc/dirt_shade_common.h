@@ -1,11 +1,12 @@
 // dirt_shade_common.h -- what the G-buffer kernels share (dirt_shade.hip and its second unit dirt_shade_albedo.hip: the three
 // reflectance models; dirt_shade_sh.hip: spherical harmonics; dirt_shade_pbr.hip: Cook-Torrance; dirt_shade_ibl.hip: image-based lighting; dirt_normal_map.hip: normal
-// mapping), each piece written and explained once here.  Device: the tile walk that makes every row of a [pixels, Cg] image
-// leave whole, the channel map it reads, the clamp and its gradient gate.  Host: the refusals every
-// *_check repeats (each file calls them in its own order, with its own checks in between: the order decides which message a
-// caller with two faults sees), the scratch size, and what follows a backward launch.  NOT shared: the wave-sum / lane-0 /
-// barrier / fold tail of the backward kernels (dirt_stage.h says why at fold_waves_to_row), the three shade_*_source
-// functions and the pixel arithmetic: these are what the files differ in.
+// mapping), each piece written and explained once here.  Device: the tile walk that makes every row of a [pixels, Cg] image leave
+// whole, the channel map it reads, the clamp and its gradient gate; of the two material shaders (Cook-Torrance, image-based
+// lighting) a pixel's material before any light and the channel map's source function.  Host: the refusals every *_check repeats
+// (each file calls them in its own order, with its own checks in between: the order decides which message a caller with two faults
+// sees), the scratch size, what follows a backward launch; of the material shaders the parameter struct's fields they have in
+// common.  NOT shared: the wave-sum / lane-0 / barrier / fold tail of the backward kernels (dirt_stage.h says why at
+// fold_waves_to_row), the other units' shade_*_source functions, the channel map's fill, the pixel arithmetic: what the files differ in.
 #pragma once
 #include "dirt_stage.h"
 
@@ -95,6 +96,60 @@ __device__ __forceinline__ void unit3_backward(const float (&gy)[3], const float
 
 __device__ __forceinline__ float max0(float x) { return x < 0.f ? 0.f : x; }   // a NaN stays NaN, as torch.clamp leaves it
 
+// what the lights of a pixel share, whatever lights it (P below: ShadePbrParams or ShadeIblParams, which name these fields alike)
+struct MaterialPixel {
+    float c[3], n[3], p[3], r, mu, m;
+    float N[3], len_n, inv_n;        // the unit normal
+    float tv[3], v[3], len_v, inv_v; // cam - p and its unit vector
+    float rho, ommu, F0[3], nv_raw, nv;
+};
+
+// loads a pixel and evaluates that, in two parts, one behind the other: dirt_shade_pbr.hip has its GGX terms of rho between
+// them (as one function, with those terms behind it, that unit's kernels were scheduled otherwise: 1693 lines of assembly differed)
+template <class P>
+__device__ __forceinline__ void material_load(const P& p, const float* __restrict__ prm, long long pix, MaterialPixel& px)
+{
+    const float* __restrict__ row = p.g + pix * p.Cg;
+    load3(p.col + pix * p.cstride, px.c);
+    load3(row + p.on, px.n);
+    load3(row + p.op, px.p);
+    const float* __restrict__ mt = p.mat + pix * p.mstride;
+    px.r = mt[0]; px.mu = mt[1];
+    px.m = p.om >= 0 ? row[p.om] : 1.f;
+    unit3(px.n, px.N, px.len_n, px.inv_n);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) px.tv[j] = prm[6 + j] - px.p[j];
+    unit3(px.tv, px.v, px.len_v, px.inv_v);
+    px.rho = px.r < p.min_roughness ? p.min_roughness : (px.r > 1.f ? 1.f : px.r);
+}
+
+template <class P>
+__device__ __forceinline__ void material_fresnel(const P& p, MaterialPixel& px)
+{
+    px.ommu = 1.f - px.mu;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) px.F0[j] = p.f0 * px.ommu + px.c[j] * px.mu;
+    px.nv_raw = dot3(px.N, px.v);
+    px.nv = max0(px.nv_raw);
+}
+
+// floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], d roughness, d metalness, dm, 0 (odd: no bank conflicts); its zero
+// (a lane's twelve stores into its row stay in each kernel: in a helper here, its arrays by reference, by pointer or by value,
+// every kernel of dirt_shade_pbr.hip came out with other registers, 27869 lines of assembly)
+constexpr int MATERIAL_ROW = 13, MATERIAL_ZERO = 12;
+
+// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (oc / omat are -1 with a tensor: no channel is theirs)
+template <class P>
+__device__ __forceinline__ int material_source(const P& p, int ch)
+{
+    if (p.oc >= 0 && (unsigned)(ch - p.oc) < 3u) return ch - p.oc;
+    if ((unsigned)(ch - p.on) < 3u) return 3 + ch - p.on;
+    if ((unsigned)(ch - p.op) < 3u) return 6 + ch - p.op;
+    if (p.omat >= 0 && (unsigned)(ch - p.omat) < 2u) return 9 + ch - p.omat;
+    if (ch == p.om) return 11;
+    return MATERIAL_ZERO;
+}
+
 // dirt_shade.hip: the rows of partial sums of one scene (or of all of them, for a block shared by the batch) added up in a
 // fixed order, one workgroup per value.  One copy for every unit: the others call the launcher.
 void shade_launch_reduce(const float* partial, float* grad_params, long long rows, int NP, int param_scenes, hipStream_t s);
@@ -137,6 +192,66 @@ inline int shade_check_clamp(const char* who, unsigned flags, float lo, float hi
 
 // floats between two scenes' parameter blocks of NP floats: 0 = one block for every scene
 inline int shade_pstride(int param_scenes, int NP) { return param_scenes == 1 ? 0 : NP; }
+
+// ---- host, what the material shaders share: the arguments both units' entry points take, under the names they take them by
+// (colors / material: a tensor of its own, which has no channels -- its offset is not read --, or nullptr for channels) ...
+struct MaterialArgs {
+    const float *gbuffer, *colors, *material;
+    long long scenes;
+    int Cg, color_stride, material_stride, off_colors, off_material, off_normals, off_positions, off_mask, param_scenes;
+    float min_roughness, f0, lo, hi; unsigned flags;
+};
+
+// ... three refusals, which each unit calls in this order with its own in between, a fourth for a backward's missing tensors ...
+inline int material_check_sizes(const char* who, const MaterialArgs& a, long long pixels)
+{
+    if (int rc = shade_check_sizes(who, a.scenes, pixels, a.Cg)) return rc;
+    if (a.colors && a.color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, a.color_stride);
+    if (a.material && a.material_stride < 2) STAGE_FAIL("%s: material_stride=%d, a pixel's material is 2 floats", who, a.material_stride);
+    return DIRT_OK;
+}
+
+inline int material_check_layout(const char* who, const MaterialArgs& a)
+{
+    if (a.param_scenes != 1 && a.param_scenes != a.scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, a.param_scenes, a.scenes);
+    if (a.flags & ~DIRT_SHADE_CLAMP) STAGE_FAIL("%s: unknown flags 0x%x", who, a.flags);
+    const int off[5] = {a.off_colors, a.off_material, a.off_normals, a.off_positions, a.off_mask}, width[5] = {3, 2, 3, 3, 1};
+    const bool absent[5] = {a.colors != nullptr, a.material != nullptr, false, false, a.off_mask == -1};
+    const char* const names[5] = {"colors", "material", "normals", "positions", "mask"};
+    return shade_check_attributes(who, a.Cg, 5, off, width, absent, names);
+}
+
+inline int material_check_scalars(const char* who, const MaterialArgs& a)
+{
+    if (!(a.min_roughness > 0.f && a.min_roughness <= 1.f)) STAGE_FAIL("%s: min_roughness=%g is not in (0, 1]", who, a.min_roughness);
+    if (!(a.f0 >= 0.f && a.f0 <= 1.f)) STAGE_FAIL("%s: dielectric_f0=%g is not in [0, 1]", who, a.f0);
+    return shade_check_clamp(who, a.flags, a.lo, a.hi);
+}
+
+inline int material_check_grads(const char* who, const MaterialArgs& a, const float* grad_colors, const float* grad_material)
+{
+    if (grad_colors && !a.colors) STAGE_FAIL("%s: grad_colors without colors (the channel path's is part of grad_gbuffer)", who);
+    if (grad_material && !a.material) STAGE_FAIL("%s: grad_material without material (the channel path's is part of grad_gbuffer)", who);
+    return DIRT_OK;
+}
+
+// ... and the fields of the parameter struct P that follow from them: after the checks everything but the pointers and what
+// the unit adds (pixels of a scene, NP floats of a parameter block); before the launch (below) where a pixel's attributes are read
+template <class P>
+inline void material_fill(P& p, const MaterialArgs& a, long long pixels, int NP)
+{
+    p.pixels = pixels; p.Cg = a.Cg; p.oc = a.colors ? -1 : a.off_colors; p.omat = a.material ? -1 : a.off_material;
+    p.on = a.off_normals; p.op = a.off_positions; p.om = a.off_mask;
+    p.cstride = a.colors ? a.color_stride : a.Cg; p.mstride = a.material ? a.material_stride : a.Cg;
+    p.pstride = shade_pstride(a.param_scenes, NP);
+    p.clamp = (a.flags & DIRT_SHADE_CLAMP) ? 1 : 0;
+    p.lo = a.lo; p.hi = a.hi; p.min_roughness = a.min_roughness; p.f0 = a.f0;
+}
+template <class P>
+inline void material_inputs(P& p, const MaterialArgs& a)
+{
+    p.g = a.gbuffer; p.col = a.colors ? a.colors : a.gbuffer + a.off_colors; p.mat = a.material ? a.material : a.gbuffer + a.off_material;
+}
 
 // the scratch of a backward pass: one row of NP partial sums per workgroup; 0 for sizes the entry points refuse
 inline size_t shade_scratch_bytes(long long scenes, long long pixels, int span, int NP)

@@ -25,14 +25,14 @@
 // The parameter block is [scenes or 1, 9] floats in the layout of dirt_shade.hip's head: intensity (in the ambient slot),
 // background, camera.
 //
-// Kernels: the tiling, the clamp and the host checks of dirt_shade_common.h; the look-ups of dirt_texture_cube.h.  Forward one
-// pixel per lane: 16 texels of the pyramid, 4 of the irradiance cube, 4 of the table, read through the cache (the table is
-// 8 KB at S = 32 and every lane of a wave reads neighbouring texels of it).  Backward IBL_ITER passes of 256 pixels per
-// workgroup inside one scene: the forward again with the derivative of every look-up by its own index, d gbuffer through an
-// LDS tile, the tensors' gradients by one dense store per lane, the nine parameter sums wave_sum -> fold_waves_to_row -> one
-// row per workgroup -> shade_launch_reduce.  No atomics.  What the two cubes' gradients need it leaves in caller scratch per
-// pixel -- R, lod, and the gradients arriving at spec and at E -- and the entry point hands those to cube_backward_launch
-// twice: the scatter stays with the kernels that have the LDS-patch scheme.
+// Kernels: the tiling, the clamp, MaterialPixel, the channel map and the host checks of dirt_shade_common.h; the look-ups of
+// dirt_texture_cube.h.  Forward one pixel per lane: 16 texels of the pyramid, 4 of the irradiance cube, 4 of the table, read
+// through the cache (the table is 8 KB at S = 32 and every lane of a wave reads neighbouring texels of it).  Backward IBL_ITER
+// passes of 256 pixels per workgroup inside one scene: the forward again with the derivative of every look-up by its own index,
+// d gbuffer through an LDS tile, the tensors' gradients by one dense store per lane, the nine parameter sums wave_sum ->
+// fold_waves_to_row -> one row per workgroup -> shade_launch_reduce.  No atomics.  What the two cubes' gradients need it leaves
+// in caller scratch per pixel -- R, lod, and the gradients arriving at spec and at E -- and the entry point hands those to
+// cube_backward_launch twice: the scatter stays with the kernels that have the LDS-patch scheme.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dirt_shade_common.h"
@@ -44,41 +44,27 @@ constexpr int IBL_BLOCK = 256;     // lanes of a workgroup, pixels of one of its
 constexpr int IBL_ITER = 4;       // passes of a backward workgroup
 constexpr int IBL_SPAN = IBL_BLOCK * IBL_ITER;   // pixels of a backward workgroup
 constexpr int IBL_NP = DIRT_SHADE_PARAM_HEAD;    // floats of the parameter block
-constexpr int IBL_ROW = 13;        // floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], d roughness, d metalness, dm, 0 (odd: no bank conflicts)
-constexpr int IBL_ZERO = 12;       // the row's zero
 constexpr int IBL_PIXEL_FLOATS = 10;   // per-pixel floats of the scratch: R[3], lod, d spec[3], d E[3]
 
 struct ShadeIblParams {
-    const float* g;        // [scenes, pixels, Cg]
-    const float* col;      // a pixel's colour: three floats, cstride apart (g + off_colors with cstride = Cg, or the colour tensor)
-    const float* mat;      // a pixel's roughness and metalness: two floats, mstride apart (likewise)
+    const float *g, *col, *mat;   // the G-buffer, a pixel's colour and its material: as ShadePbrParams'
     const float* prm;      // [scenes or 1, 9]
     const float* pyr;      // [6, face_floats]: the prefiltered pyramid, 3 channels
     const float* irr;      // [6, M, M, 3]
     const float* tab;      // [S, S, 2]
     float* out;            // [scenes, pixels, 3]
     const float* gout;     // [scenes, pixels, 3]
-    float* gg;             // [scenes, pixels, Cg] or nullptr
-    float* gcol;           // [scenes, pixels, 3] or nullptr (colour tensor)
-    float* gmat;           // [scenes, pixels, 2] or nullptr (material tensor)
-    float* partial;        // [scenes, blocks, 9] or nullptr
+    float *gg, *gcol, *gmat;   // their gradients, each or nullptr: as ShadePbrParams'
+    float* partial;       // [scenes, blocks, 9] or nullptr
     float* s_dir;          // [scenes, pixels, 3]: R; these four or nullptr (no cube wants its gradient)
     float* s_lod;          // [scenes, pixels]
     float* s_gspec;        // [scenes, pixels, 3]: what arrives at spec
     float* s_girr;         // [scenes, pixels, 3]: what arrives at E
-    long long pixels;      // of one scene
-    long long face_floats;
+    long long pixels, face_floats;   // pixels of one scene, floats of a face of the pyramid
     int Cg, cstride, mstride, oc, omat, on, op, om, pstride;   // as ShadePbrParams'
     int N, L, M, S;        // pyramid size and levels, irradiance size, table size
     int clamp;
     float lo, hi, min_roughness, f0;
-};
-
-struct IblPixel {
-    float c[3], n[3], p[3], r, mu, m;
-    float N[3], len_n, inv_n;        // the unit normal
-    float tv[3], v[3], len_v, inv_v; // cam - p and its unit vector
-    float rho, ommu, F0[3], nv_raw, nv;
 };
 
 // a bilinear look-up of three channels and, per channel, its derivative by sc / a and tc / a (0 where the index is clamped)
@@ -93,27 +79,6 @@ struct IblEval {
     float spec[3], A, B, A_nv, A_rho, B_nv, B_rho;
     float S[3], wd[3], T[3];         // S_j; (1 - S_j)(1 - mu) c_j; the light before the intensity
 };
-
-__device__ __forceinline__ void ibl_pixel(const ShadeIblParams& P, const float* __restrict__ prm, long long pix, IblPixel& px)
-{
-    const float* __restrict__ row = P.g + pix * P.Cg;
-    load3(P.col + pix * P.cstride, px.c);
-    load3(row + P.on, px.n);
-    load3(row + P.op, px.p);
-    const float* __restrict__ mt = P.mat + pix * P.mstride;
-    px.r = mt[0]; px.mu = mt[1];
-    px.m = P.om >= 0 ? row[P.om] : 1.f;
-    unit3(px.n, px.N, px.len_n, px.inv_n);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) px.tv[j] = prm[6 + j] - px.p[j];
-    unit3(px.tv, px.v, px.len_v, px.inv_v);
-    px.rho = px.r < P.min_roughness ? P.min_roughness : (px.r > 1.f ? 1.f : px.r);
-    px.ommu = 1.f - px.mu;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) px.F0[j] = P.f0 * px.ommu + px.c[j] * px.mu;
-    px.nv_raw = dot3(px.N, px.v);
-    px.nv = max0(px.nv_raw);
-}
 
 // one level [n, n, 3] of a face at the look-up q
 template <bool GRAD>
@@ -150,7 +115,7 @@ __device__ __forceinline__ float ibl_table_index(float x, int S, float& d)
 }
 
 template <bool GRAD>
-__device__ __forceinline__ void ibl_eval(const ShadeIblParams& P, const IblPixel& px, IblEval& e)
+__device__ __forceinline__ void ibl_eval(const ShadeIblParams& P, const MaterialPixel& px, IblEval& e)
 {
     // the table
     float drow, dcol;
@@ -207,8 +172,8 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_forward_kernel(ShadeIblPa
     if (i >= P.pixels) return;
     const long long pix = (long long)blockIdx.y * P.pixels + i;
     const float* __restrict__ prm = P.prm + (size_t)blockIdx.y * P.pstride;
-    IblPixel px;
-    ibl_pixel(P, prm, pix, px);
+    MaterialPixel px;
+    material_load(P, prm, pix, px); material_fresnel(P, px);
     IblEval e;
     ibl_eval<false>(P, px, e);
     const float om = 1.f - px.m;
@@ -218,17 +183,6 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_forward_kernel(ShadeIblPa
     store3(P.out + pix * 3, o);
 }
 
-// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (oc / omat are -1 with a tensor: no channel is theirs)
-__device__ __forceinline__ int shade_ibl_source(const ShadeIblParams& P, int ch)
-{
-    if (P.oc >= 0 && (unsigned)(ch - P.oc) < 3u) return ch - P.oc;
-    if ((unsigned)(ch - P.on) < 3u) return 3 + ch - P.on;
-    if ((unsigned)(ch - P.op) < 3u) return 6 + ch - P.op;
-    if (P.omat >= 0 && (unsigned)(ch - P.omat) < 2u) return 9 + ch - P.omat;
-    if (ch == P.om) return 11;
-    return IBL_ZERO;
-}
-
 // ---- backward.  PARAMS: the parameter block wants its gradient; GBUF: the G-buffer does.  The gradients of a colour /
 // material tensor leave by one store per lane where P.gcol / P.gmat is there, the cubes' per-pixel scratch where P.s_dir is.
 template <bool PARAMS, bool GBUF>
@@ -236,7 +190,7 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_backward_kernel(ShadeIblP
 {
     constexpr int NP = IBL_NP;
     constexpr int NA = PARAMS ? NP : 1;
-    __shared__ float s_g[GBUF ? IBL_BLOCK * IBL_ROW : 1];
+    __shared__ float s_g[GBUF ? IBL_BLOCK * MATERIAL_ROW : 1];
     __shared__ unsigned char s_src[GBUF ? DIRT_SHADE_MAX_CHANNELS : 1];
     __shared__ float s_part[PARAMS ? 4 * NP : 1];
     const int tid = threadIdx.x;
@@ -247,8 +201,8 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_backward_kernel(ShadeIblP
     const int Cg = P.Cg;
     const TileWalk walk = tile_walk<IBL_BLOCK>(Cg, tid);
     if constexpr (GBUF) {
-        for (int ch = tid; ch < Cg; ch += IBL_BLOCK) s_src[ch] = (unsigned char)shade_ibl_source(P, ch);
-        s_g[tid * IBL_ROW + IBL_ZERO] = 0.f;
+        for (int ch = tid; ch < Cg; ch += IBL_BLOCK) s_src[ch] = (unsigned char)material_source(P, ch);
+        s_g[tid * MATERIAL_ROW + MATERIAL_ZERO] = 0.f;
     }
     for (int it = 0; it < IBL_ITER; ++it) {
         const long long first = ((long long)blockIdx.x * IBL_ITER + it) * IBL_BLOCK;   // (uniform)
@@ -256,8 +210,8 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_backward_kernel(ShadeIblP
         const int npx = (int)(P.pixels - first < IBL_BLOCK ? P.pixels - first : IBL_BLOCK);
         const long long pix = (long long)blockIdx.y * P.pixels + first + tid;
         if (tid < npx) {
-            IblPixel px;
-            ibl_pixel(P, prm, pix, px);
+            MaterialPixel px;
+            material_load(P, prm, pix, px); material_fresnel(P, px);
             IblEval e;
             ibl_eval<true>(P, px, e);
             float go[3];
@@ -334,7 +288,7 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_backward_kernel(ShadeIblP
                 store3(P.s_girr + pix * 3, girr);
             }
             if constexpr (GBUF) {
-                float* __restrict__ r = s_g + tid * IBL_ROW;
+                float* __restrict__ r = s_g + tid * MATERIAL_ROW;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     r[j] = gc[j];
@@ -345,7 +299,7 @@ __global__ __launch_bounds__(IBL_BLOCK) void shade_ibl_backward_kernel(ShadeIblP
             }
         }
         if constexpr (GBUF)
-            tile_rows_out<IBL_BLOCK, IBL_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
+            tile_rows_out<IBL_BLOCK, MATERIAL_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
     }
     if constexpr (PARAMS) {
         const int wave = tid >> 6, lane = tid & 63;
@@ -368,40 +322,24 @@ extern "C" {
 
 static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
-// what this file's entry points refuse (the shared refusals: dirt_shade_common.h); `colors` / `material`: whether they are tensors of their own
-static int shade_ibl_check(const char* who, bool colors, bool material, long long scenes, long long rows, long long cols, int Cg,
-                           int color_stride, int material_stride, int off_colors, int off_material, int off_normals, int off_positions,
-                           int off_mask, int param_scenes, int size, int levels, int irradiance_size, int table_size, float min_roughness,
-                           float f0, float lo, float hi, unsigned flags, dirt::ShadeIblParams& P)
+// what this file's entry points refuse (the shared refusals, and `a`: dirt_shade_common.h)
+static int shade_ibl_check(const char* who, const dirt::MaterialArgs& a, long long rows, long long cols, int size, int levels,
+                           int irradiance_size, int table_size, dirt::ShadeIblParams& P)
 {
     if (rows < 0 || cols < 0 || (rows > 0 && cols > (1ll << 40) / rows))
         STAGE_FAIL("%s: bad pixel grid (rows=%lld cols=%lld)", who, rows, cols);
-    if (int rc = dirt::shade_check_sizes(who, scenes, rows * cols, Cg)) return rc;
-    if (colors && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
-    if (material && material_stride < 2) STAGE_FAIL("%s: material_stride=%d, a pixel's material is 2 floats", who, material_stride);
-    if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
-    if (flags & ~DIRT_SHADE_CLAMP) STAGE_FAIL("%s: unknown flags 0x%x", who, flags);
-    const int off[5] = {off_colors, off_material, off_normals, off_positions, off_mask}, width[5] = {3, 2, 3, 3, 1};
-    const bool absent[5] = {colors, material, false, false, off_mask == -1};
-    const char* const names[5] = {"colors", "material", "normals", "positions", "mask"};
-    if (int rc = dirt::shade_check_attributes(who, Cg, 5, off, width, absent, names)) return rc;
+    if (int rc = dirt::material_check_sizes(who, a, rows * cols)) return rc;
+    if (int rc = dirt::material_check_layout(who, a)) return rc;
     if (size < 1 || size > 32768) STAGE_FAIL("%s: pyramid size %d, 1..32768", who, size);
     const int most = dirt::mip_level_count(size, size, -1);
     if (levels < 1 || levels > most) STAGE_FAIL("%s: %d levels, a %d x %d face has 1..%d", who, levels, size, size, most);
     if (irradiance_size < 1 || irradiance_size > 32768) STAGE_FAIL("%s: irradiance size %d, 1..32768", who, irradiance_size);
     if (table_size < 2 || table_size > DIRT_SHADE_IBL_MAX_TABLE)
         STAGE_FAIL("%s: table size %d, 2..%d", who, table_size, DIRT_SHADE_IBL_MAX_TABLE);
-    if (!(min_roughness > 0.f && min_roughness <= 1.f)) STAGE_FAIL("%s: min_roughness=%g is not in (0, 1]", who, min_roughness);
-    if (!(f0 >= 0.f && f0 <= 1.f)) STAGE_FAIL("%s: dielectric_f0=%g is not in [0, 1]", who, f0);
-    if (int rc = dirt::shade_check_clamp(who, flags, lo, hi)) return rc;
-    P.pixels = rows * cols; P.Cg = Cg; P.oc = colors ? -1 : off_colors; P.omat = material ? -1 : off_material;
-    P.on = off_normals; P.op = off_positions; P.om = off_mask;
-    P.cstride = colors ? color_stride : Cg; P.mstride = material ? material_stride : Cg;
-    P.pstride = dirt::shade_pstride(param_scenes, dirt::IBL_NP);
+    if (int rc = dirt::material_check_scalars(who, a)) return rc;
+    dirt::material_fill(P, a, rows * cols, dirt::IBL_NP);
     P.N = size; P.L = levels; P.M = irradiance_size; P.S = table_size;
     P.face_floats = dirt::cube_face_floats(size, levels, 3);
-    P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0;
-    P.lo = lo; P.hi = hi; P.min_roughness = min_roughness; P.f0 = f0;
     return DIRT_OK;
 }
 
@@ -418,16 +356,15 @@ int dirt_shade_ibl_forward(const float* gbuffer, const float* colors, const floa
                            float min_roughness, float dielectric_f0, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
 {
     const char* who = "dirt_shade_ibl_forward";
+    const dirt::MaterialArgs a{gbuffer, colors, material, scenes, Cg, color_stride, material_stride, off_colors, off_material, off_normals,
+                               off_positions, off_mask, param_scenes, min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags};
     dirt::ShadeIblParams P{};
-    int rc = shade_ibl_check(who, colors != nullptr, material != nullptr, scenes, rows, cols, Cg, color_stride, material_stride, off_colors,
-                             off_material, off_normals, off_positions, off_mask, param_scenes, size, levels, irradiance_size, table_size,
-                             min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags, P);
-    if (rc) return rc;
+    if (int rc = shade_ibl_check(who, a, rows, cols, size, levels, irradiance_size, table_size, P)) return rc;
     if (scenes * P.pixels == 0) return dirt::stage_ok(report);
     if (!gbuffer || !params || !out) STAGE_FAIL("%s: gbuffer / params / out is NULL", who);
     if (!pyramid || !irradiance || !table) STAGE_FAIL("%s: pyramid / irradiance / table is NULL", who);
     if (P.pixels > 0x7fffffffll * dirt::IBL_BLOCK) STAGE_FAIL("%s: too many pixels per scene", who);
-    P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.mat = material ? material : gbuffer + off_material;
+    dirt::material_inputs(P, a);
     P.prm = params; P.pyr = pyramid; P.irr = irradiance; P.tab = table; P.out = out;
     const dim3 grid((unsigned)((P.pixels + dirt::IBL_BLOCK - 1) / dirt::IBL_BLOCK), (unsigned)scenes);
     hipLaunchKernelGGL(dirt::shade_ibl_forward_kernel, grid, dim3(dirt::IBL_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
@@ -443,13 +380,12 @@ int dirt_shade_ibl_backward(const float* gbuffer, const float* colors, const flo
                             float dielectric_f0, float clamp_lo, float clamp_hi, unsigned flags, void* stream)
 {
     const char* who = "dirt_shade_ibl_backward";
+    const dirt::MaterialArgs a{gbuffer, colors, material, scenes, Cg, color_stride, material_stride, off_colors, off_material, off_normals,
+                               off_positions, off_mask, param_scenes, min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags};
     dirt::ShadeIblParams P{};
-    int rc = shade_ibl_check(who, colors != nullptr, material != nullptr, scenes, rows, cols, Cg, color_stride, material_stride, off_colors,
-                             off_material, off_normals, off_positions, off_mask, param_scenes, size, levels, irradiance_size, table_size,
-                             min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags, P);
+    int rc = shade_ibl_check(who, a, rows, cols, size, levels, irradiance_size, table_size, P);
+    if (!rc) rc = dirt::material_check_grads(who, a, grad_colors, grad_material);
     if (rc) return rc;
-    if (grad_colors && !colors) STAGE_FAIL("%s: grad_colors without colors (the channel path's is part of grad_gbuffer)", who);
-    if (grad_material && !material) STAGE_FAIL("%s: grad_material without material (the channel path's is part of grad_gbuffer)", who);
     const bool cubes = grad_pyramid || grad_irradiance;
     if (!grad_gbuffer && !grad_params && !grad_colors && !grad_material && !cubes) return dirt::stage_ok(report);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -472,7 +408,7 @@ int dirt_shade_ibl_backward(const float* gbuffer, const float* colors, const flo
     const long long grid_rows = rows == 1 ? 1 : scenes * rows, grid_cols = rows == 1 ? n : cols;
     if (cubes && (dirt::tile_grid(grid_rows, grid_cols).tiles > 0x7fffffffll || grid_cols > 0x7fffffffll || grid_rows > 0x7fffffffll))
         STAGE_FAIL("%s: pixel grid too large (scenes=%lld rows=%lld cols=%lld)", who, scenes, rows, cols);
-    P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.mat = material ? material : gbuffer + off_material;
+    dirt::material_inputs(P, a);
     P.prm = params; P.pyr = pyramid; P.irr = irradiance; P.tab = table;
     P.gout = grad_out; P.gg = grad_gbuffer; P.gcol = grad_colors; P.gmat = grad_material;
     P.partial = static_cast<float*>(scratch);

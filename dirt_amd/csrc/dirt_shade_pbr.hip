@@ -23,9 +23,9 @@
 // then per light {vector[3], colour[3], 0, 0}.  The light kinds (one bit per light), the two scalars of the material model,
 // the clamp and the flag are launch arguments.
 //
-// Kernels: the tiling, the clamp and the host checks of dirt_shade_common.h.  Forward one pixel per lane; a pixel's colours
-// are three floats and its material two floats `cstride` / `mstride` apart, which is channels of the G-buffer (stride Cg)
-// as well as a tensor of their own, so
+// Kernels: the tiling, the clamp and, with dirt_shade_ibl.hip, a pixel's material (MaterialPixel), the channel map and the host
+// checks of dirt_shade_common.h.  Forward one pixel per lane; a pixel's colours are three floats and its material two floats
+// `cstride` / `mstride` apart, which is channels of the G-buffer (stride Cg) as well as a tensor of their own, so
 // the forward is one kernel for the four source combinations.  Backward four passes of 256 pixels per workgroup inside one
 // scene: the forward again, d gbuffer through an LDS tile so that every row leaves whole, the tensors' gradients by one dense
 // store per lane, the parameter sums in registers under compile-time indices (hence the template on the light count), then
@@ -40,8 +40,6 @@ constexpr int PBR_BLOCK = 256;     // lanes of a workgroup, pixels of one of its
 constexpr int PBR_ITER = 4;        // passes of a backward workgroup
 constexpr int PBR_SPAN = PBR_BLOCK * PBR_ITER;   // pixels of a backward workgroup
 constexpr int PBR_HEAD = DIRT_SHADE_PARAM_HEAD, PBR_LIGHT = DIRT_SHADE_PARAM_LIGHT;
-constexpr int PBR_ROW = 13;        // floats of a pixel's row in the LDS tile: dc[3], dn[3], dp[3], d roughness, d metalness, dm, 0 (odd: no bank conflicts)
-constexpr int PBR_ZERO = 12;       // the row's zero
 constexpr float PBR_PI = 3.14159265358979323846f, PBR_INV_PI = 0.31830988618379067154f;
 
 struct ShadePbrParams {
@@ -63,13 +61,8 @@ struct ShadePbrParams {
     float lo, hi, min_roughness, f0;
 };
 
-// what the lights of a pixel share
-struct PbrPixel {
-    float c[3], n[3], p[3], r, mu, m;
-    float N[3], len_n, inv_n;        // the unit normal
-    float tv[3], v[3], len_v, inv_v; // cam - p and its unit vector
-    float rho, rho2, a2, k, omk, ommu, F0[3], nv_raw, nv, gv;
-};
+// what the lights of a pixel share: the material's, and the GGX terms
+struct PbrPixel : MaterialPixel { float rho2, a2, k, omk, gv; };
 
 // one light at a pixel
 struct PbrLight {
@@ -81,27 +74,12 @@ struct PbrLight {
 // loads a pixel and evaluates what its lights share
 __device__ __forceinline__ void pbr_pixel(const ShadePbrParams& P, const float* __restrict__ prm, long long pix, PbrPixel& px)
 {
-    const float* __restrict__ row = P.g + pix * P.Cg;
-    load3(P.col + pix * P.cstride, px.c);
-    load3(row + P.on, px.n);
-    load3(row + P.op, px.p);
-    const float* __restrict__ mt = P.mat + pix * P.mstride;
-    px.r = mt[0]; px.mu = mt[1];
-    px.m = P.om >= 0 ? row[P.om] : 1.f;
-    unit3(px.n, px.N, px.len_n, px.inv_n);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) px.tv[j] = prm[6 + j] - px.p[j];
-    unit3(px.tv, px.v, px.len_v, px.inv_v);
-    px.rho = px.r < P.min_roughness ? P.min_roughness : (px.r > 1.f ? 1.f : px.r);
+    material_load(P, prm, pix, px);
     px.rho2 = px.rho * px.rho;
     px.a2 = px.rho2 * px.rho2;
     px.k = ((px.rho + 1.f) * (px.rho + 1.f)) * 0.125f;
     px.omk = 1.f - px.k;
-    px.ommu = 1.f - px.mu;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) px.F0[j] = P.f0 * px.ommu + px.c[j] * px.mu;
-    px.nv_raw = dot3(px.N, px.v);
-    px.nv = max0(px.nv_raw);
+    material_fresnel(P, px);   // (behind the terms of rho: dirt_shade_common.h says why)
     px.gv = px.nv * px.omk + px.k;
 }
 
@@ -159,17 +137,6 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrPa
     store3(P.out + pix * 3, o);
 }
 
-// which value of a pixel's LDS row goes to channel `ch` of d gbuffer (oc / omat are -1 with a tensor: no channel is theirs)
-__device__ __forceinline__ int shade_pbr_source(const ShadePbrParams& P, int ch)
-{
-    if (P.oc >= 0 && (unsigned)(ch - P.oc) < 3u) return ch - P.oc;
-    if ((unsigned)(ch - P.on) < 3u) return 3 + ch - P.on;
-    if ((unsigned)(ch - P.op) < 3u) return 6 + ch - P.op;
-    if (P.omat >= 0 && (unsigned)(ch - P.omat) < 2u) return 9 + ch - P.omat;
-    if (ch == P.om) return 11;
-    return PBR_ZERO;
-}
-
 // ---- backward.  NL: the light count; PARAMS: the parameter block wants its gradient; GBUF: the G-buffer does.  The
 // gradients of a colour / material tensor leave by one store per lane where P.gcol / P.gmat is there.
 template <int NL, bool PARAMS, bool GBUF>
@@ -177,7 +144,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
 {
     constexpr int NP = PBR_HEAD + PBR_LIGHT * NL;
     constexpr int NA = PARAMS ? NP : 1;
-    __shared__ float s_g[GBUF ? PBR_BLOCK * PBR_ROW : 1];
+    __shared__ float s_g[GBUF ? PBR_BLOCK * MATERIAL_ROW : 1];
     __shared__ unsigned char s_src[GBUF ? DIRT_SHADE_MAX_CHANNELS : 1];
     __shared__ float s_part[PARAMS ? 4 * NP : 1];
     const int tid = threadIdx.x;
@@ -188,8 +155,8 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
     const int Cg = P.Cg;
     const TileWalk walk = tile_walk<PBR_BLOCK>(Cg, tid);
     if constexpr (GBUF) {
-        for (int ch = tid; ch < Cg; ch += PBR_BLOCK) s_src[ch] = (unsigned char)shade_pbr_source(P, ch);
-        s_g[tid * PBR_ROW + PBR_ZERO] = 0.f;
+        for (int ch = tid; ch < Cg; ch += PBR_BLOCK) s_src[ch] = (unsigned char)material_source(P, ch);
+        s_g[tid * MATERIAL_ROW + MATERIAL_ZERO] = 0.f;
     }
     for (int it = 0; it < PBR_ITER; ++it) {
         const long long first = ((long long)blockIdx.x * PBR_ITER + it) * PBR_BLOCK;   // (uniform)
@@ -317,7 +284,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
             if (P.gcol) store3(P.gcol + pix * 3, gc);
             if (P.gmat) { P.gmat[pix * 2] = gr; P.gmat[pix * 2 + 1] = gmu; }
             if constexpr (GBUF) {
-                float* __restrict__ r = s_g + tid * PBR_ROW;
+                float* __restrict__ r = s_g + tid * MATERIAL_ROW;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     r[j] = gc[j];
@@ -328,7 +295,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
             }
         }
         if constexpr (GBUF)
-            tile_rows_out<PBR_BLOCK, PBR_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
+            tile_rows_out<PBR_BLOCK, MATERIAL_ROW>(s_g, s_src, P.gg + ((long long)blockIdx.y * P.pixels + first) * Cg, npx, Cg, tid, walk);
     }
     if constexpr (PARAMS) {
         const int wave = tid >> 6, lane = tid & 63;
@@ -357,34 +324,16 @@ extern "C" {
 
 static constexpr dirt::ErrorSetter report = dirt::set_last_error;   // the error channel of this file's entry points
 
-// what this file's entry points refuse (the shared refusals: dirt_shade_common.h); `colors` / `material`: whether they are tensors of their own
-static int shade_pbr_check(const char* who, bool colors, bool material, long long scenes, long long pixels, int Cg, int color_stride,
-                           int material_stride, int off_colors, int off_material, int off_normals, int off_positions, int off_mask,
-                           int param_scenes, int lights, unsigned light_kinds, float min_roughness, float f0, float lo, float hi,
-                           unsigned flags, dirt::ShadePbrParams& P)
+// what this file's entry points refuse (the shared refusals, and `a`: dirt_shade_common.h)
+static int shade_pbr_check(const char* who, const dirt::MaterialArgs& a, long long pixels, int lights, unsigned light_kinds, dirt::ShadePbrParams& P)
 {
-    if (int rc = dirt::shade_check_sizes(who, scenes, pixels, Cg)) return rc;
-    if (colors && color_stride < 3) STAGE_FAIL("%s: color_stride=%d, a pixel's colour is 3 floats", who, color_stride);
-    if (material && material_stride < 2) STAGE_FAIL("%s: material_stride=%d, a pixel's material is 2 floats", who, material_stride);
+    if (int rc = dirt::material_check_sizes(who, a, pixels)) return rc;
     if (lights < 0 || lights > DIRT_SHADE_PBR_MAX_LIGHTS) STAGE_FAIL("%s: %d lights, at most %d", who, lights, DIRT_SHADE_PBR_MAX_LIGHTS);
     if (light_kinds >> lights) STAGE_FAIL("%s: light_kinds 0x%x has bits beyond %d lights", who, light_kinds, lights);
-    if (param_scenes != 1 && param_scenes != scenes) STAGE_FAIL("%s: param_scenes=%d is neither 1 nor scenes=%lld", who, param_scenes, scenes);
-    if (flags & ~DIRT_SHADE_CLAMP) STAGE_FAIL("%s: unknown flags 0x%x", who, flags);
-    // an attribute that is a tensor has no channels (its offset is not read)
-    const int off[5] = {off_colors, off_material, off_normals, off_positions, off_mask}, width[5] = {3, 2, 3, 3, 1};
-    const bool absent[5] = {colors, material, false, false, off_mask == -1};
-    const char* const names[5] = {"colors", "material", "normals", "positions", "mask"};
-    if (int rc = dirt::shade_check_attributes(who, Cg, 5, off, width, absent, names)) return rc;
-    if (!(min_roughness > 0.f && min_roughness <= 1.f)) STAGE_FAIL("%s: min_roughness=%g is not in (0, 1]", who, min_roughness);
-    if (!(f0 >= 0.f && f0 <= 1.f)) STAGE_FAIL("%s: dielectric_f0=%g is not in [0, 1]", who, f0);
-    if (int rc = dirt::shade_check_clamp(who, flags, lo, hi)) return rc;
-    P.pixels = pixels; P.Cg = Cg; P.oc = colors ? -1 : off_colors; P.omat = material ? -1 : off_material;
-    P.on = off_normals; P.op = off_positions; P.om = off_mask;
-    P.cstride = colors ? color_stride : Cg; P.mstride = material ? material_stride : Cg;
+    if (int rc = dirt::material_check_layout(who, a)) return rc;
+    if (int rc = dirt::material_check_scalars(who, a)) return rc;
+    dirt::material_fill(P, a, pixels, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
     P.nl = lights; P.kinds = light_kinds;
-    P.pstride = dirt::shade_pstride(param_scenes, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights);
-    P.clamp = (flags & DIRT_SHADE_CLAMP) ? 1 : 0;
-    P.lo = lo; P.hi = hi; P.min_roughness = min_roughness; P.f0 = f0;
     return DIRT_OK;
 }
 
@@ -401,15 +350,14 @@ int dirt_shade_pbr_forward(const float* gbuffer, const float* colors, const floa
                            void* stream)
 {
     const char* who = "dirt_shade_pbr_forward";
+    const dirt::MaterialArgs a{gbuffer, colors, material, scenes, Cg, color_stride, material_stride, off_colors, off_material, off_normals,
+                               off_positions, off_mask, param_scenes, min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags};
     dirt::ShadePbrParams P{};
-    int rc = shade_pbr_check(who, colors != nullptr, material != nullptr, scenes, pixels, Cg, color_stride, material_stride, off_colors,
-                             off_material, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, min_roughness,
-                             dielectric_f0, clamp_lo, clamp_hi, flags, P);
-    if (rc) return rc;
+    if (int rc = shade_pbr_check(who, a, pixels, lights, light_kinds, P)) return rc;
     if (scenes * pixels == 0) return dirt::stage_ok(report);
     if (!gbuffer || !params || !out) STAGE_FAIL("%s: gbuffer / params / out is NULL", who);
     if (pixels > 0x7fffffffll * dirt::PBR_BLOCK) STAGE_FAIL("%s: too many pixels per scene", who);
-    P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.mat = material ? material : gbuffer + off_material;
+    dirt::material_inputs(P, a);
     P.prm = params; P.out = out;
     const dim3 grid((unsigned)((pixels + dirt::PBR_BLOCK - 1) / dirt::PBR_BLOCK), (unsigned)scenes);
     hipLaunchKernelGGL(dirt::shade_pbr_forward_kernel, grid, dim3(dirt::PBR_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), P);
@@ -424,13 +372,12 @@ int dirt_shade_pbr_backward(const float* gbuffer, const float* colors, const flo
                             void* stream)
 {
     const char* who = "dirt_shade_pbr_backward";
+    const dirt::MaterialArgs a{gbuffer, colors, material, scenes, Cg, color_stride, material_stride, off_colors, off_material, off_normals,
+                               off_positions, off_mask, param_scenes, min_roughness, dielectric_f0, clamp_lo, clamp_hi, flags};
     dirt::ShadePbrParams P{};
-    int rc = shade_pbr_check(who, colors != nullptr, material != nullptr, scenes, pixels, Cg, color_stride, material_stride, off_colors,
-                             off_material, off_normals, off_positions, off_mask, param_scenes, lights, light_kinds, min_roughness,
-                             dielectric_f0, clamp_lo, clamp_hi, flags, P);
+    int rc = shade_pbr_check(who, a, pixels, lights, light_kinds, P);
+    if (!rc) rc = dirt::material_check_grads(who, a, grad_colors, grad_material);
     if (rc) return rc;
-    if (grad_colors && !colors) STAGE_FAIL("%s: grad_colors without colors (the channel path's is part of grad_gbuffer)", who);
-    if (grad_material && !material) STAGE_FAIL("%s: grad_material without material (the channel path's is part of grad_gbuffer)", who);
     if (scenes * pixels == 0 || (!grad_gbuffer && !grad_params && !grad_colors && !grad_material)) return dirt::stage_ok(report);
     if (!gbuffer || !params || !grad_out) STAGE_FAIL("%s: gbuffer / params / grad_out is NULL", who);
     if (grad_params) {
@@ -440,7 +387,7 @@ int dirt_shade_pbr_backward(const float* gbuffer, const float* colors, const flo
     }
     const long long blocks = dirt::shade_blocks(pixels, dirt::PBR_SPAN);
     if (blocks > 0x7fffffffll) STAGE_FAIL("%s: too many pixels per scene", who);
-    P.g = gbuffer; P.col = colors ? colors : gbuffer + off_colors; P.mat = material ? material : gbuffer + off_material;
+    dirt::material_inputs(P, a);
     P.prm = params; P.gout = grad_out; P.gg = grad_gbuffer; P.gcol = grad_colors; P.gmat = grad_material;
     P.partial = static_cast<float*>(scratch);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

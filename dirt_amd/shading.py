@@ -107,6 +107,39 @@ def _split_slots(width, slots):
     return const, tensors
 
 
+def _check_gbuffer(gbuffer, who):
+    """What every `_check_*` opens with: refuses a G-buffer that is not floating-point, -> (its device, B of a [B, H, W, Cg] one
+    or None)."""
+    if not gbuffer.dtype.is_floating_point:
+        raise ValueError('%s expects a float32 gbuffer, got %s' % (who, gbuffer.dtype))
+    return gbuffer.device, int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+
+
+def _as_input(x):
+    """colors / material / a cube as an autograd Function takes it: a tensor as float32, a channel index as None"""
+    return x.to(torch.float32) if isinstance(x, torch.Tensor) else None
+
+
+def _forward_operands(gbuffer, block, colors, material=None):
+    """What the lighting forward passes open with: -> (the output [..., 3], the contiguous block, the colour and the material
+    tensor beside the G-buffer as they are passed under `_stage.rows_in_place` -- None for channels of the G-buffer --, their
+    strides).  (Written out, not looped: this runs in every call.)"""
+    out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
+    csrc, cstride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+    msrc, mstride = _stage.rows_in_place(material, 2) if material is not None else (None, 0)
+    return out, block.contiguous(), csrc, msrc, cstride, mstride
+
+
+def _backward_operands(want, grad_out, gbuffer, block, empty, csrc, msrc=None):
+    """What the lighting backward passes open with (`want`: the Function's needs_input_grad): -> (the gradients of the G-buffer
+    and the block (`_stage.grad_outputs`), of the saved colour and material tensors, inputs 2 and 3 (`_stage.dense_grads`; None,
+    not given, wants none), the incoming gradient as the kernels read it -- None for an `empty` call, whose gradients are
+    zeroed and complete)."""
+    grad_g, grad_p = _stage.grad_outputs((gbuffer, block), want[:2], empty)
+    grad_c, grad_m = _stage.dense_grads(grad_out, (3, 2), (csrc is not None and want[2], msrc is not None and want[3]), empty)
+    return grad_g, grad_p, grad_c, grad_m, None if empty else grad_out.to(torch.float32).contiguous()
+
+
 class _ShadeGBuffer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gbuffer, block, colors, meta):
@@ -114,10 +147,8 @@ class _ShadeGBuffer(torch.autograd.Function):
         pixels lie a constant stride apart (`_stage.rows_in_place`)"""
         lib = _lib.load()
         scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = meta
-        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
-        block = block.contiguous()
+        out, block, src, _, stride, _ = _forward_operands(gbuffer, block, colors)
         tail = (int(block.shape[0]), nl, kinds, sided, lo, hi, flags)
-        src, stride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
         if scenes * pixels and src is None:
             _stage.call(lib.dirt_shade_forward, gbuffer.device, gbuffer.data_ptr(), block.data_ptr(), out.data_ptr(), scenes, pixels, cg,
                         *offsets, *tail)
@@ -135,14 +166,10 @@ class _ShadeGBuffer(torch.autograd.Function):
         gbuffer, block, src = ctx.saved_tensors
         scenes, pixels, cg, offsets, kinds, sided, nl, lo, hi, flags = ctx.meta
         dev = gbuffer.device
-        want_p = ctx.needs_input_grad[1]
-        want_c = src is not None and ctx.needs_input_grad[2]
-        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
-        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None   # dense [..., 3], whatever the colours' strides
-        if not scenes * pixels:
-            return grad_g, grad_p, grad_c.zero_() if want_c else None, None
-        grad_out = grad_out.to(torch.float32).contiguous()
-        nbytes = lib.dirt_shade_scratch_bytes(scenes, pixels, nl) if want_p else 0
+        grad_g, grad_p, grad_c, _, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, not scenes * pixels, src)
+        if grad_out is None:
+            return grad_g, grad_p, grad_c, None
+        nbytes = lib.dirt_shade_scratch_bytes(scenes, pixels, nl) if grad_p is not None else 0
         tail = (_ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg)
         if src is None:
             _stage.call(lib.dirt_shade_backward, dev, gbuffer.data_ptr(), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_p),
@@ -185,7 +212,7 @@ def shade_gbuffer(gbuffer, lights, *, colors, normals, positions=None, mask=None
                                                                             camera_position, background, clamp)
     block = _splice_block(gbuffer.device, const, tensors)
     meta = (scenes, pixels, cg, tuple(offsets), kinds, sided, len(lights), lo, hi, flags)
-    return _ShadeGBuffer.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
+    return _ShadeGBuffer.apply(g, block, _as_input(colors), meta)
 
 
 def _splice_block(dev, const, tensors):
@@ -210,10 +237,7 @@ def _check_arguments(gbuffer, lights, colors, normals, positions, mask, ambient,
     """Everything `shade_gbuffer` refuses with a ValueError, on the tensor's shape and device alone (no device work): ->
     (channel offsets, light kinds, sidedness, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])]).
     `colors` as a tensor: the offsets' first entry is -1."""
-    if not gbuffer.dtype.is_floating_point:
-        raise ValueError('shade_gbuffer expects a float32 gbuffer, got %s' % gbuffer.dtype)
-    dev = gbuffer.device
-    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    dev, batch = _check_gbuffer(gbuffer, 'shade_gbuffer')
     offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('normals', normals, 3, True), ('positions', positions, 3, False),
                                          ('mask', mask, 1, False)))
     if len(lights) > _lib.SHADE_MAX_LIGHTS:
@@ -307,9 +331,7 @@ class _ShadeGBufferSH(torch.autograd.Function):
         """colors: None (three channels of the G-buffer) or float32 [..., 3] beside it, read in place under `_stage.rows_in_place`"""
         lib = _lib.load()
         scenes, pixels, cg, offsets, scale, lo, hi, flags = meta
-        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
-        block = block.contiguous()
-        src, stride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
+        out, block, src, _, stride, _ = _forward_operands(gbuffer, block, colors)
         if scenes * pixels:
             _stage.call(lib.dirt_shade_sh_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(src), block.data_ptr(), out.data_ptr(), scenes, pixels,
                         cg, stride, *offsets, int(block.shape[0]), *scale, lo, hi, flags)
@@ -324,14 +346,10 @@ class _ShadeGBufferSH(torch.autograd.Function):
         gbuffer, block, src = ctx.saved_tensors
         scenes, pixels, cg, offsets, scale, lo, hi, flags = ctx.meta
         dev = gbuffer.device
-        want_p = ctx.needs_input_grad[1]
-        want_c = src is not None and ctx.needs_input_grad[2]
-        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
-        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None   # dense [..., 3], whatever the colours' strides
-        if not scenes * pixels:
-            return grad_g, grad_p, grad_c.zero_() if want_c else None, None
-        grad_out = grad_out.to(torch.float32).contiguous()
-        nbytes = lib.dirt_shade_sh_scratch_bytes(scenes, pixels) if want_p else 0
+        grad_g, grad_p, grad_c, _, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, not scenes * pixels, src)
+        if grad_out is None:
+            return grad_g, grad_p, grad_c, None
+        nbytes = lib.dirt_shade_sh_scratch_bytes(scenes, pixels) if grad_p is not None else 0
         _stage.call(lib.dirt_shade_sh_backward, dev, gbuffer.data_ptr(), _ptr(src), block.data_ptr(), grad_out.data_ptr(), _ptr(grad_g),
                     _ptr(grad_c), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg, ctx.color_stride, *offsets,
                     int(block.shape[0]), *scale, lo, hi, flags)
@@ -359,16 +377,13 @@ def shade_gbuffer_sh(gbuffer, coefficients, *, colors, normals, mask=None, backg
                                                                         normalize, band_scale)
     block = _splice_block(gbuffer.device, const, tensors)
     meta = (scenes, pixels, cg, tuple(offsets), scale, lo, hi, flags)
-    return _ShadeGBufferSH.apply(g, block, colors.to(torch.float32) if isinstance(colors, torch.Tensor) else None, meta)
+    return _ShadeGBufferSH.apply(g, block, _as_input(colors), meta)
 
 
 def _check_sh_arguments(gbuffer, coefficients, colors, normals, mask, background, clamp, normalize, band_scale):
     """Everything `shade_gbuffer_sh` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel
     offsets (colors, normals, mask), band scales, lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])])."""
-    if not gbuffer.dtype.is_floating_point:
-        raise ValueError('shade_gbuffer_sh expects a float32 gbuffer, got %s' % gbuffer.dtype)
-    dev = gbuffer.device
-    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    dev, batch = _check_gbuffer(gbuffer, 'shade_gbuffer_sh')
     offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('normals', normals, 3, True), ('mask', mask, 1, False)))
     if not isinstance(coefficients, torch.Tensor) or not coefficients.dtype.is_floating_point:
         raise ValueError('coefficients must be a floating-point tensor, got %s' % (getattr(coefficients, 'dtype', type(coefficients).__name__),))
@@ -415,15 +430,12 @@ class _ShadeGBufferPBR(torch.autograd.Function):
         `_stage.rows_in_place`"""
         lib = _lib.load()
         scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = meta
-        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
-        block = block.contiguous()
-        csrc, cstride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
-        msrc, mstride = _stage.rows_in_place(material, 2) if material is not None else (None, 0)
+        out, block, csrc, msrc, *strides = _forward_operands(gbuffer, block, colors, material)
         if scenes * pixels:
             _stage.call(lib.dirt_shade_pbr_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), out.data_ptr(),
-                        scenes, pixels, cg, cstride, mstride, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
+                        scenes, pixels, cg, *strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
         ctx.save_for_backward(gbuffer, block, csrc, msrc)
-        ctx.meta, ctx.strides = meta, (cstride, mstride)
+        ctx.meta, ctx.strides = meta, strides
         return out
 
     @staticmethod
@@ -433,17 +445,10 @@ class _ShadeGBufferPBR(torch.autograd.Function):
         gbuffer, block, csrc, msrc = ctx.saved_tensors
         scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = ctx.meta
         dev = gbuffer.device
-        want_p = ctx.needs_input_grad[1]
-        want_c = csrc is not None and ctx.needs_input_grad[2]
-        want_m = msrc is not None and ctx.needs_input_grad[3]
-        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], not scenes * pixels)
-        # dense [..., 3] and [..., 2], whatever the tensors' strides
-        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None
-        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (2,), dtype=torch.float32) if want_m else None
-        if not scenes * pixels:
-            return grad_g, grad_p, grad_c.zero_() if want_c else None, grad_m.zero_() if want_m else None, None
-        grad_out = grad_out.to(torch.float32).contiguous()
-        nbytes = lib.dirt_shade_pbr_scratch_bytes(scenes, pixels, nl) if want_p else 0
+        grad_g, grad_p, grad_c, grad_m, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, not scenes * pixels, csrc, msrc)
+        if grad_out is None:
+            return grad_g, grad_p, grad_c, grad_m, None
+        nbytes = lib.dirt_shade_pbr_scratch_bytes(scenes, pixels, nl) if grad_p is not None else 0
         _stage.call(lib.dirt_shade_pbr_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), grad_out.data_ptr(),
                     _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg,
                     *ctx.strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
@@ -480,8 +485,7 @@ def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, 
                                                                                    dielectric_f0)
     block = _splice_block(gbuffer.device, const, tensors)
     meta = (scenes, pixels, cg, tuple(offsets), len(lights), kinds, scalars, lo, hi, flags)
-    as_input = lambda x: x.to(torch.float32) if isinstance(x, torch.Tensor) else None   # noqa: E731
-    return _ShadeGBufferPBR.apply(g, block, as_input(colors), as_input(material), meta)
+    return _ShadeGBufferPBR.apply(g, block, _as_input(colors), _as_input(material), meta)
 
 
 def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask, ambient, camera_position, background, clamp,
@@ -489,20 +493,12 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
     """Everything `shade_gbuffer_pbr` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel
     offsets (colors, material, normals, positions, mask), light kinds, (min_roughness, dielectric_f0), lo, hi, flags, the
     block's constant row, [(first slot, tensor [1 or B, width])])."""
-    if not gbuffer.dtype.is_floating_point:
-        raise ValueError('shade_gbuffer_pbr expects a float32 gbuffer, got %s' % gbuffer.dtype)
-    dev = gbuffer.device
-    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    dev, batch = _check_gbuffer(gbuffer, 'shade_gbuffer_pbr')
     offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('material', material, 2, True), ('normals', normals, 3, True),
                                          ('positions', positions, 3, True), ('mask', mask, 1, False)))
     if len(lights) > _lib.SHADE_PBR_MAX_LIGHTS:
         raise ValueError('shade_gbuffer_pbr takes at most %d lights, got %d' % (_lib.SHADE_PBR_MAX_LIGHTS, len(lights)))
-    scalars = []
-    for name, x, text, ok in (('min_roughness', min_roughness, '> 0 and <= 1', lambda v: 0. < v <= 1.),
-                              ('dielectric_f0', dielectric_f0, 'in [0, 1]', lambda v: 0. <= v <= 1.)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not ok(float(x)):
-            raise ValueError('%s must be a number %s, got %r' % (name, text, x))
-        scalars.append(float(x))
+    scalars = _material_scalars(min_roughness, dielectric_f0)
     if camera_position is None:
         raise ValueError('shade_gbuffer_pbr needs camera_position')
     lo, hi = _clamp_bounds(clamp)
@@ -519,7 +515,18 @@ def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, 
         slots.append((base, _value(rec[1], 3, 'light %d %s' % (l, 'position' if rec[0] == 'point' else 'direction'), dev, batch)))
         slots.append((base + 3, _value(rec[2], 3, 'light %d color' % l, dev, batch)))
         kinds |= _PBR_KINDS[rec[0]] << l
-    return (offsets, kinds, tuple(scalars), lo, hi, flags) + _split_slots(_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights), slots)
+    return (offsets, kinds, scalars, lo, hi, flags) + _split_slots(_lib.SHADE_PARAM_HEAD + _lib.SHADE_PARAM_LIGHT * len(lights), slots)
+
+
+def _material_scalars(min_roughness, dielectric_f0):
+    """The two python numbers of the material model, refused outside their ranges -> (min_roughness, dielectric_f0) as floats."""
+    scalars = []
+    for name, x, text, ok in (('min_roughness', min_roughness, '> 0 and <= 1', lambda v: 0. < v <= 1.),
+                              ('dielectric_f0', dielectric_f0, 'in [0, 1]', lambda v: 0. <= v <= 1.)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not ok(float(x)):
+            raise ValueError('%s must be a number %s, got %r' % (name, text, x))
+        scalars.append(float(x))
+    return tuple(scalars)
 
 
 # ---- split-sum image-based lighting (dirt_shade_ibl.hip)
@@ -531,16 +538,14 @@ class _ShadeGBufferIBL(torch.autograd.Function):
         `_stage.rows_in_place`; packed [6, floats], irradiance [6, M, M, 3], brdf [S, S, 2]: float32"""
         lib = _lib.load()
         scenes, rows, cols, cg, offsets, sizes, scalars, lo, hi, flags = meta
-        out = torch.empty(tuple(gbuffer.shape[:-1]) + (3,), dtype=torch.float32, device=gbuffer.device)
-        block, packed, irradiance, brdf = block.contiguous(), packed.contiguous(), irradiance.contiguous(), brdf.contiguous()
-        csrc, cstride = _stage.rows_in_place(colors, 3) if colors is not None else (None, 0)
-        msrc, mstride = _stage.rows_in_place(material, 2) if material is not None else (None, 0)
+        out, block, csrc, msrc, *strides = _forward_operands(gbuffer, block, colors, material)
+        packed, irradiance, brdf = packed.contiguous(), irradiance.contiguous(), brdf.contiguous()
         if scenes * rows * cols:
             _stage.call(lib.dirt_shade_ibl_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(),
-                        packed.data_ptr(), irradiance.data_ptr(), brdf.data_ptr(), out.data_ptr(), scenes, rows, cols, cg, cstride, mstride,
+                        packed.data_ptr(), irradiance.data_ptr(), brdf.data_ptr(), out.data_ptr(), scenes, rows, cols, cg, *strides,
                         *offsets, int(block.shape[0]), *sizes, *scalars, lo, hi, flags)
         ctx.save_for_backward(gbuffer, block, csrc, msrc, packed, irradiance, brdf)
-        ctx.meta, ctx.strides = meta, (cstride, mstride)
+        ctx.meta, ctx.strides = meta, strides
         return out
 
     @staticmethod
@@ -551,21 +556,11 @@ class _ShadeGBufferIBL(torch.autograd.Function):
         scenes, rows, cols, cg, offsets, sizes, scalars, lo, hi, flags = ctx.meta
         dev = gbuffer.device
         empty = not scenes * rows * cols
-        want_p = ctx.needs_input_grad[1]
-        want_c = csrc is not None and ctx.needs_input_grad[2]
-        want_m = msrc is not None and ctx.needs_input_grad[3]
-        grad_g, grad_p = _stage.grad_outputs((gbuffer, block), ctx.needs_input_grad[:2], empty)
-        # dense [..., 3] and [..., 2], whatever the tensors' strides
-        grad_c = grad_out.new_empty(grad_out.shape, dtype=torch.float32) if want_c else None
-        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (2,), dtype=torch.float32) if want_m else None
-        # the cubes' gradients: cleared by the call
-        grad_s = torch.empty_like(packed) if ctx.needs_input_grad[4] else None
-        grad_i = torch.empty_like(irradiance) if ctx.needs_input_grad[5] else None
+        grad_g, grad_p, grad_c, grad_m, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, empty, csrc, msrc)
+        grad_s, grad_i = _stage.grad_outputs((packed, irradiance), ctx.needs_input_grad[4:6], empty)   # the cubes': cleared by the call
         if empty:
-            return (grad_g, grad_p, grad_c.zero_() if want_c else None, grad_m.zero_() if want_m else None,
-                    grad_s.zero_() if grad_s is not None else None, grad_i.zero_() if grad_i is not None else None, None, None)
-        grad_out = grad_out.to(torch.float32).contiguous()
-        nbytes = lib.dirt_shade_ibl_scratch_bytes(scenes, rows, cols) if want_p or grad_s is not None or grad_i is not None else 0
+            return grad_g, grad_p, grad_c, grad_m, grad_s, grad_i, None, None
+        nbytes = lib.dirt_shade_ibl_scratch_bytes(scenes, rows, cols) if grad_p is not None or grad_s is not None or grad_i is not None else 0
         _stage.call(lib.dirt_shade_ibl_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), packed.data_ptr(),
                     irradiance.data_ptr(), brdf.data_ptr(), grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p),
                     _ptr(grad_s), _ptr(grad_i), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, rows, cols, cg, *ctx.strides, *offsets,
@@ -598,13 +593,27 @@ def shade_gbuffer_ibl(gbuffer, specular, irradiance, brdf, *, colors, material, 
 
     Direct lights are added by the caller: `shade_gbuffer_pbr(..., clamp=None) + shade_gbuffer_ibl(..., clamp=None)`, then
     one clamp."""
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shade_gbuffer_ibl')
+    offsets, sizes, scalars, lo, hi, flags, const, tensors = _check_ibl_arguments(gbuffer, specular, irradiance, brdf, colors, material, normals,
+                                                                                   positions, mask, intensity, camera_position, background, clamp,
+                                                                                   min_roughness, dielectric_f0)
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_ibl')
+    block = _splice_block(gbuffer.device, const, tensors)
+    # a scene's pixel grid: the image's rows and columns, one row for a flat list
+    rows, cols = (int(gbuffer.shape[-3]), int(gbuffer.shape[-2])) if gbuffer.dim() >= 3 else (1, pixels)
+    meta = (scenes, rows, cols, cg, tuple(offsets), sizes, scalars, lo, hi, flags)
+    return _ShadeGBufferIBL.apply(g, block, _as_input(colors), _as_input(material), _as_input(specular.packed), _as_input(irradiance),
+                                  _as_input(brdf), meta)
+
+
+def _check_ibl_arguments(gbuffer, specular, irradiance, brdf, colors, material, normals, positions, mask, intensity, camera_position,
+                         background, clamp, min_roughness, dielectric_f0):
+    """Everything `shade_gbuffer_ibl` refuses with a ValueError, on types, shapes and devices alone (no device work): -> (channel
+    offsets (colors, material, normals, positions, mask), (pyramid size, levels, irradiance size, table size), (min_roughness,
+    dielectric_f0), lo, hi, flags, the block's constant row, [(first slot, tensor [1 or B, width])])."""
     from .texture import CubePyramid, _cube_level
     who = 'shade_gbuffer_ibl'
-    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, who)
-    if not gbuffer.dtype.is_floating_point:
-        raise ValueError('%s expects a float32 gbuffer, got %s' % (who, gbuffer.dtype))
-    dev = gbuffer.device
-    batch = int(gbuffer.shape[0]) if gbuffer.dim() == 4 else None
+    dev, batch = _check_gbuffer(gbuffer, who)
     if not isinstance(specular, CubePyramid):
         raise ValueError('%s expects specular to be the CubePyramid of prefilter_cube, got %s' % (who, type(specular).__name__))
     if specular.roughness is None:
@@ -634,27 +643,15 @@ def shade_gbuffer_ibl(gbuffer, specular, irradiance, brdf, *, colors, material, 
             raise ValueError('%s is on %s, the G-buffer on %s' % (name, t.device, dev))
     offsets = _channel_offsets(gbuffer, (('colors', colors, 3, True), ('material', material, 2, True), ('normals', normals, 3, True),
                                          ('positions', positions, 3, True), ('mask', mask, 1, False)))
-    scalars = []
-    for name, x, text, ok in (('min_roughness', min_roughness, '> 0 and <= 1', lambda v: 0. < v <= 1.),
-                              ('dielectric_f0', dielectric_f0, 'in [0, 1]', lambda v: 0. <= v <= 1.)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not ok(float(x)):
-            raise ValueError('%s must be a number %s, got %r' % (name, text, x))
-        scalars.append(float(x))
+    scalars = _material_scalars(min_roughness, dielectric_f0)
     if camera_position is None:
         raise ValueError('%s needs camera_position' % who)
     lo, hi = _clamp_bounds(clamp)
     flags = _lib.SHADE_CLAMP if clamp is not None else 0
     # the parameter block: [1 or B, 9] in the layout of `_param_head`, the intensity in the ambient slot
     slots = [(0, _value(intensity, 3, 'intensity', dev, batch))] + _param_head((0., 0., 0.), background, camera_position, dev, batch)[1:]
-    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shade_gbuffer_ibl')
-    block = _splice_block(dev, *_split_slots(_lib.SHADE_PARAM_HEAD, slots))
-    # a scene's pixel grid: the image's rows and columns, one row for a flat list
-    rows, cols = (int(gbuffer.shape[-3]), int(gbuffer.shape[-2])) if gbuffer.dim() >= 3 else (1, pixels)
     sizes = (specular.size, specular.levels, int(irradiance.shape[1]), int(brdf.shape[0]))
-    meta = (scenes, rows, cols, cg, tuple(offsets), sizes, tuple(scalars), lo, hi, flags)
-    as_input = lambda x: x.to(torch.float32) if isinstance(x, torch.Tensor) else None   # noqa: E731
-    return _ShadeGBufferIBL.apply(g, block, as_input(colors), as_input(material), specular.packed.to(torch.float32),
-                                  irradiance.to(torch.float32), brdf.to(torch.float32), meta)
+    return (offsets, sizes, scalars, lo, hi, flags) + _split_slots(_lib.SHADE_PARAM_HEAD, slots)
 
 
 # ---- tangent-space normal mapping (dirt_normal_map.hip)
@@ -681,10 +678,9 @@ class _PerturbNormals(torch.autograd.Function):
         gbuffer, src = ctx.saved_tensors
         scenes, pixels, cg, offsets, strength, flags = ctx.meta
         grad_g, = _stage.grad_outputs((gbuffer,), ctx.needs_input_grad[:1], not scenes * pixels)
-        # dense [..., 3], whatever the normal map's strides
-        grad_m = grad_out.new_empty(tuple(grad_out.shape[:-1]) + (3,), dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        grad_m, = _stage.dense_grads(grad_out, (3,), ctx.needs_input_grad[1:2], not scenes * pixels)
         if not scenes * pixels:
-            return grad_g, grad_m.zero_() if grad_m is not None else None, None
+            return grad_g, grad_m, None
         grad_out = grad_out.to(torch.float32).contiguous()
         _stage.call(lib.dirt_normal_map_backward, gbuffer.device, gbuffer.data_ptr(), src.data_ptr(), grad_out.data_ptr(), _ptr(grad_g),
                     _ptr(grad_m), scenes, pixels, cg, ctx.map_stride, *offsets, strength, flags)
@@ -718,8 +714,7 @@ def perturb_normals(gbuffer, normal_map, *, normals, tangents, strength=1.0, enc
 def _check_normal_map_arguments(gbuffer, normal_map, normals, tangents, strength, encoded):
     """Everything `perturb_normals` refuses with a ValueError, on shapes and devices alone (no device work): -> (channel offsets
     (normals, tangents), strength, flags)"""
-    if not gbuffer.dtype.is_floating_point:
-        raise ValueError('perturb_normals expects a float32 gbuffer, got %s' % gbuffer.dtype)
+    _check_gbuffer(gbuffer, 'perturb_normals')
     offsets = _channel_offsets(gbuffer, (('normals', normals, 3, True), ('tangents', tangents, 4, True)))
     want = tuple(gbuffer.shape[:-1]) + (3,)
     if not isinstance(normal_map, torch.Tensor) or not normal_map.dtype.is_floating_point:

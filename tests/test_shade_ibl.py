@@ -422,6 +422,34 @@ def test_the_functions_are_exported_and_declared():
     assert '#include "dirt_texture_cube.h"' in cube and '#include "dirt_texture_cube.h"' in source
 
 
+def test_one_copy_of_what_the_material_shaders_share():
+    """What Cook-Torrance and image-based lighting have in common is declared in dirt_shade_common.h and in neither unit; what
+    gave another assembly there (the header says so at each) is written out in both."""
+    read = lambda name: open(os.path.join(ROOT, 'dirt_amd', 'csrc', name)).read()   # noqa: E731
+    shared, pbr, ibl = read('dirt_shade_common.h'), read('dirt_shade_pbr.hip'), read('dirt_shade_ibl.hip')
+    for helper in ('struct MaterialPixel {', 'void material_load(', 'void material_fresnel(', 'int material_source(', 'MATERIAL_ROW = 13',
+                   'MATERIAL_ZERO = 12', 'struct MaterialArgs {', 'int material_check_sizes(', 'int material_check_layout(',
+                   'int material_check_scalars(', 'int material_check_grads(', 'void material_fill(', 'void material_inputs('):
+        assert shared.count(helper) == 1 and helper not in pbr and helper not in ibl, helper
+    for unit in (pbr, ibl):
+        assert '#include "dirt_shade_common.h"' in unit
+        for used in ('material_load(P, prm, pix, px)', 'material_fresnel(P, px)', 'material_source(P, ch)', 'dirt::material_check_sizes(who, a, ',
+                     'dirt::material_check_layout(who, a)', 'dirt::material_check_scalars(who, a)', 'dirt::material_fill(P, a, ',
+                     'dirt::material_check_grads(who, a, grad_colors, grad_material)'):
+            assert used in unit, used
+        assert unit.count('dirt::material_inputs(P, a);') == 2 and unit.count('const dirt::MaterialArgs a{') == 2
+        # the messages and the assignments the helpers carry stand in no unit
+        for text in ('color_stride=%d', 'material_stride=%d', 'param_scenes=%d', 'unknown flags', 'min_roughness=%g', 'dielectric_f0=%g',
+                     'grad_colors without colors', 'grad_material without material', 'P.cstride =', 'P.mstride =', 'P.col =', 'P.min_roughness ='):
+            assert text not in unit and text.replace('P.', 'p.') in shared, text
+        # per kernel: the fill of the channel map and a lane's stores into its row of the tile
+        assert 's_src[ch] = (unsigned char)material_source(P, ch);' in unit and 'r[9] = gr; r[10] = gmu; r[11] = gm;' in unit
+    assert 's_src[ch] =' not in shared.replace('s_src[ch] = its source function', '') and 'r[9] = gr' not in shared
+    assert 'struct PbrPixel : MaterialPixel { float rho2, a2, k, omk, gv; };' in pbr and 'IblPixel' not in ibl and 'MaterialPixel px;' in ibl
+    for name in ('PBR_ROW', 'PBR_ZERO', 'IBL_ROW', 'IBL_ZERO', 'shade_pbr_source', 'shade_ibl_source', 'ibl_pixel'):
+        assert name not in pbr + ibl + shared, name
+
+
 @pytest.fixture(scope='module')
 def lib():
     from dirt_amd import _lib, build

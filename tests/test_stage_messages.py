@@ -1,5 +1,5 @@
 """The full text of what the fused stages refuse (`vertex_stage`, `skin_vertices`, `pose_skeleton`, `blend_shapes`,
-`shade_gbuffer`, and the texture look-up `sample_texture_uv` / `mip_pyramid`), and `to(device)` of their built-once index objects.  The stage test files match substrings of these
+`shade_gbuffer`, `shade_gbuffer_ibl`, and the texture look-up `sample_texture_uv` / `mip_pyramid`), and `to(device)` of their built-once index objects.  The stage test files match substrings of these
 messages; this table pins every character, so that the code the wrappers share cannot change a text unnoticed.  Nothing here
 needs the library or a GPU: every refusal comes from types, shapes, dtypes and devices alone.
 """
@@ -31,6 +31,66 @@ def many(t):
 def shade_checks(gbuffer, lights=(), ambient=(0., 0., 0.)):
     """the checks of `shade_gbuffer` behind its device check, which every CPU tensor fails"""
     return shading._check_arguments(gbuffer, list(lights), 4, 7, 1, 0, ambient, None, (0., 0., 0.), (0., 1.))
+
+
+RAMP = (0., 0.5, 1.)
+G12 = torch.zeros(4, 5, 12)
+
+
+def pyramid(floats=63, channels=3, levels=3, roughness=RAMP):
+    return texture_module.CubePyramid(torch.zeros(6, floats), 4, channels, levels, roughness)
+
+
+def ibl(g=G12, specular=pyramid(), irradiance=torch.zeros(6, 2, 2, 3), brdf=torch.zeros(8, 8, 2), **keywords):
+    """`shade_gbuffer_ibl` through its public name: every check stands in front of its device check, which every CPU tensor fails"""
+    arguments = dict(colors=4, material=10, normals=7, positions=1, mask=0, camera_position=(0., 0., 4.))
+    arguments.update(keywords)
+    return shading.shade_gbuffer_ibl(g, specular, irradiance, brdf, **arguments)
+
+
+IBL_BRDF = 'shade_gbuffer_ibl expects brdf to be a floating-point tensor [S, S, 2] with 2 <= S <= 128 (lighting.environment_brdf), got %s'
+IBL_IRRADIANCE = 'shade_gbuffer_ibl expects irradiance to be a floating-point tensor [6, size, size, 3], got %s'
+IBL_REFUSALS = [   # (keywords of `ibl`, the text): in the order of the checks
+    (dict(g=torch.zeros(5)), 'shade_gbuffer_ibl expects gbuffer [H, W, Cg], [B, H, W, Cg] or [N, Cg], got (5,)'),
+    (dict(g=G12.to(torch.int32)), 'shade_gbuffer_ibl expects a float32 gbuffer, got torch.int32'),
+    (dict(specular=torch.zeros(6, 63)), 'shade_gbuffer_ibl expects specular to be the CubePyramid of prefilter_cube, got Tensor'),
+    (dict(specular=pyramid(roughness=None)),
+     'shade_gbuffer_ibl: specular is a box-filtered pyramid (roughness None): the look-up at lod = roughness (L - 1) needs the levels '
+     'prefilter_cube convolves'),
+    (dict(specular=pyramid(roughness=(0., 0.25, 1.))),
+     'shade_gbuffer_ibl: specular was filtered at the roughnesses (0.0, 0.25, 1.0), the look-up at lod = roughness (L - 1) needs the '
+     'default ramp k / (L - 1) of prefilter_cube'),
+    (dict(specular=pyramid(84, channels=4)), 'shade_gbuffer_ibl: specular has 4 channels, an environment has 3'),
+    (dict(specular=pyramid(60)), 'shade_gbuffer_ibl: specular.packed must be [6, 63], the 3 levels of a 4 x 4 x 3 face, got (6, 60)'),
+    (dict(specular=pyramid(levels=2, roughness=(0., 1.))),
+     'shade_gbuffer_ibl: specular.packed must be [6, 60], the 2 levels of a 4 x 4 x 3 face, got (6, 63)'),
+    (dict(irradiance=torch.zeros(6, 2, 3, 3)), IBL_IRRADIANCE % '(6, 2, 3, 3)'),
+    (dict(irradiance=torch.zeros(6, 2, 2, 4)), IBL_IRRADIANCE % '(6, 2, 2, 4)'),
+    (dict(brdf=torch.zeros(1, 1, 2)), IBL_BRDF % '(1, 1, 2)'),
+    (dict(brdf=torch.zeros(129, 129, 2)), IBL_BRDF % '(129, 129, 2)'),
+    (dict(brdf=torch.zeros(8, 8, 3)), IBL_BRDF % '(8, 8, 3)'),
+    (dict(brdf=torch.zeros(8, 8, 2, device='meta')), 'brdf is on meta, the G-buffer on cpu'),
+    (dict(irradiance=torch.zeros(6, 2, 2, 3, device='meta')), 'irradiance is on meta, the G-buffer on cpu'),
+    (dict(colors=torch.zeros(4, 5, 4)), "colors as a tensor must have shape [4, 5, 3] (the G-buffer's [4, 5, 12] with 3 channels), got [4, 5, 4]"),
+    (dict(material=None), 'material must be the index of a G-buffer channel, got None'),
+    (dict(material=6), 'material (channel 6) overlaps colors (channel 4)'),
+    (dict(positions=None), 'positions must be the index of a G-buffer channel, got None'),
+    (dict(mask=12), 'mask at channel 12 does not fit in the 12 channels of the G-buffer'),
+    (dict(min_roughness=0.), 'min_roughness must be a number > 0 and <= 1, got 0.0'),
+    (dict(dielectric_f0=1.5), 'dielectric_f0 must be a number in [0, 1], got 1.5'),
+    (dict(camera_position=None), 'shade_gbuffer_ibl needs camera_position'),
+    (dict(clamp=(1., 0.)), 'clamp needs lo <= hi, got (1.0, 0.0)'),
+    (dict(intensity=(1., 2.)), 'intensity must be 3 numbers, got 2'),
+    (dict(intensity=torch.zeros(2, 3)), 'intensity must have shape [3], got [2, 3]'),
+    (dict(background=torch.zeros(4)), 'background must have shape [3], got [4]'),
+    # two faults: the earlier check speaks
+    (dict(specular=pyramid(84, channels=4), brdf=torch.zeros(8, 8, 3)), 'shade_gbuffer_ibl: specular has 4 channels, an environment has 3'),
+    (dict(irradiance=torch.zeros(6, 2, 3, 3), material=6), IBL_IRRADIANCE % '(6, 2, 3, 3)'),
+    (dict(brdf=torch.zeros(8, 8, 2, device='meta'), colors=torch.zeros(4, 5, 4)), 'brdf is on meta, the G-buffer on cpu'),
+    (dict(material=6, min_roughness=0.), 'material (channel 6) overlaps colors (channel 4)'),
+    (dict(dielectric_f0=1.5, camera_position=None), 'dielectric_f0 must be a number in [0, 1], got 1.5'),
+    (dict(camera_position=None, clamp=(1., 0.)), 'shade_gbuffer_ibl needs camera_position'),
+]
 
 
 def trilinear(texture=TEX, uvs=UV, **keywords):
@@ -159,6 +219,9 @@ REFUSALS = [
     (lambda: trilinear(uvs=UV_LIST, lod=torch.zeros(5), max_level=0), RuntimeError, 'dirt_amd.texture.sample_texture_uv' + CPU),
     (lambda: texture_module.mip_pyramid(TEX), RuntimeError, 'dirt_amd.texture.mip_pyramid' + CPU),
     (lambda: texture_module.mip_pyramid(torch.zeros(8, 8)), ValueError, 'mip_pyramid expects texture to be 3D [height, width, channels], got shape (8, 8)'),
+    # shade_gbuffer_ibl (at the end: a row's number is part of its test's name) ------------------------------------------------
+] + [(lambda kw=kw: ibl(**kw), ValueError, text) for kw, text in IBL_REFUSALS] + [
+    (lambda: ibl(), RuntimeError, 'dirt_amd.shading.shade_gbuffer_ibl' + CPU),
 ]
 
 
