@@ -41,6 +41,8 @@ SHADE_PBR_MAX_LIGHTS = 4
 SHADE_PBR_KINDS = {'directional': 0, 'point': 1}   # the bit of a light in light_kinds
 SHADE_IBL_MAX_TABLE = 128   # the largest environment-BRDF table of dirt_shade_ibl_forward
 NORMAL_MAP_ENCODED = 1
+SHADOW_MAX_LIGHTS = 4   # = SHADE_PBR_MAX_LIGHTS: the lights of dirt_shadow_forward, one map and one matrix each
+SHADOW_KERNELS = (1, 3, 5)   # the sides of its percentage-closer filter
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
 GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
@@ -75,7 +77,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_kinematics_scratch_bytes', 'dirt_kinematics_forward', 'dirt_kinematics_backward',
            'dirt_blend_scratch_bytes', 'dirt_blend_forward', 'dirt_blend_backward',
            'dirt_tangent_scratch_bytes', 'dirt_tangent_forward', 'dirt_tangent_backward',
-           'dirt_normal_map_forward', 'dirt_normal_map_backward')
+           'dirt_normal_map_forward', 'dirt_normal_map_backward',
+           'dirt_shadow_scratch_bytes', 'dirt_shadow_forward', 'dirt_shadow_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -244,6 +247,14 @@ def load():
         lib.dirt_normal_map_forward.restype = i
         lib.dirt_normal_map_backward.argtypes = [fp, fp, fp, fp, fp, ll, ll, i, i, i, i, f32, u, vp]
         lib.dirt_normal_map_backward.restype = i
+    if hasattr(lib, 'dirt_shadow_forward') or not override:   # shadow-map look-up (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_shadow_scratch_bytes.argtypes = [ll, ll, ll, i]
+        lib.dirt_shadow_scratch_bytes.restype = sz
+        lib.dirt_shadow_forward.argtypes = [fp] * 4 + [ll, ll] + [i] * 10 + [f32, f32, f32, vp]
+        lib.dirt_shadow_forward.restype = i
+        lib.dirt_shadow_backward.argtypes = [fp] * 7 + [vp, sz, ll, ll, ll] + [i] * 10 + [f32, f32, f32, vp]
+        lib.dirt_shadow_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -3,6 +3,9 @@
 Same signatures and conventions as the reference: `vertices` [*, V, 3|4] with any leading batch dimensions and a
 topology `faces` [F, 3] shared by the batch.  Where the reference builds a sparse [F, V, ...] tensor and reduces
 it (dirt/lighting.py:64-79) this uses one `index_add_` over the vertex axis -- same sums, linear memory."""
+import math
+import numbers
+
 import torch
 
 
@@ -436,3 +439,93 @@ def perturb_normals(normals, tangents, normal_map, strength=1.0, encoded=True):
     Bv = w * torch.linalg.cross(N, T, dim=-1)
     out, ok_y = _guarded_unit((dx * T + dy * Bv) + dz * N)
     return torch.where(ok_n & ok_x & ok_y, out, n)
+
+
+# ---- shadow maps.  Not in the reference: the per-point look-up of a depth image rendered from a light (`shading.render_shadow_map`)
+# with a percentage-closer filter and a smooth comparison, so that the visibility is differentiable in the point, in the map and in
+# the light's matrix.  This is the specification `shading.shadow_visibility` implements per pixel.
+
+SHADOW_MAX_LIGHTS = 4
+SHADOW_KERNELS = (1, 3, 5)
+
+
+def shadow_visibility(points, normals, shadow_maps, light_matrices, *, mask=None, kernel=3, bias=0.0, softness, normal_offset=0.0):
+    """The share of each light that reaches each point, from the lights' depth maps: points [N, 3] (world space), normals [N, 3]
+    or None (needed only with normal_offset != 0), shadow_maps [L, Hs, Ws] (clip-space z of the nearest surface, as
+    `shading.render_shadow_map` draws it), light_matrices [L, 4, 4] (world -> the light's clip space, right-multiplying row
+    vectors as everything in `matrices`), mask [N] or None -> [N, L], 1 = lit, 0 = in shadow.  kernel (1, 3 or 5), bias,
+    softness (> 0) and normal_offset are python numbers and carry no gradient.  Per point and light:
+
+        q = p + normal_offset n / max(|n|, 1e-12)                    (x, y, z, w) = [q, 1] @ M            d = z
+        col = (x / w + 1) Ws / 2 - 0.5          row = (1 - y / w) Hs / 2 - 0.5
+            (the fractional texel-centre indices of the image `rasterise` draws with M: row 0 is the top, window y = Hs - 0.5)
+        h = (kernel - 1) / 2      r0 = floor(row) - h,  fr = row - floor(row)      c0 = floor(col) - h,  fc = col - floor(col)
+        wr[0] = 1 - fr,  wr[kernel] = fr,  wr[a] = 1 between; wc likewise with fc
+        S(r, c) = s((Z[r, c] - d + bias) / softness + 1/2) for a texel of the map,  1 for one outside it
+        s(t) = u u (3 - 2 u),  u = clamp(t, 0, 1)
+        v = (1 / kernel^2) sum_{a, b = 0..kernel} wr[a] wc[b] S(r0 + a, c0 + b)
+        out = 1 - m (1 - v)
+
+    v is the mean of kernel^2 bilinear blends of the comparison S, at the texel offsets -h .. h, written as one window of
+    (kernel + 1)^2 texels.  A point that is not in front of the light (not w > 0, a NaN included) or whose whole window lies
+    off the map has v = 1 and no gradient, and adds none to the matrix either; a texel outside the map receives none.  floor and the inside tests carry no
+    gradient; the clamp passes none outside (0, 1) (and s' is 0 at both ends)."""
+    kernel, bias, softness, normal_offset = _shadow_scalars(kernel, bias, softness, normal_offset)
+    p = _as(points, torch.zeros((), dtype=torch.float32))
+    maps, mats = _as(shadow_maps, p), _as(light_matrices, p)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError('points must have shape [N, 3], got %s' % (tuple(p.shape),))
+    if maps.dim() != 3 or not 1 <= maps.shape[0] <= SHADOW_MAX_LIGHTS or 0 in maps.shape:
+        raise ValueError('shadow_maps must have shape [L, Hs, Ws] with 1 <= L <= %d, got %s' % (SHADOW_MAX_LIGHTS, tuple(maps.shape)))
+    if tuple(mats.shape) != (maps.shape[0], 4, 4):
+        raise ValueError('light_matrices must have shape [%d, 4, 4], got %s' % (maps.shape[0], tuple(mats.shape)))
+    q = p
+    if normal_offset != 0.:
+        if normals is None:
+            raise ValueError('normal_offset needs normals')
+        q = p + normal_offset * torch.nn.functional.normalize(_as(normals, p), dim=-1, eps=1.e-12)
+    finite = torch.isfinite(q).all(dim=1)
+    q = torch.where(finite[:, None], q, torch.zeros_like(q))   # (a select: the matrix's gradient is q^T d clip, and NaN * 0 would be NaN)
+    L, Hs, Ws = (int(s) for s in maps.shape)
+    h = (kernel - 1) // 2
+    taps = torch.arange(kernel + 1, device=p.device)
+    one = torch.ones_like(q[:, 0])
+    out = []
+    for l in range(L):
+        M = mats[l]
+        x, y, d, w = (((q[:, 0] * M[0, j] + q[:, 1] * M[1, j]) + q[:, 2] * M[2, j]) + M[3, j] for j in range(4))
+        front = finite & (w > 0)
+        ws = torch.where(front, w, one)
+        col = (x / ws + 1.) * (0.5 * Ws) - 0.5
+        row = (1. - y / ws) * (0.5 * Hs) - 0.5
+        fr0, fc0 = torch.floor(row.detach()), torch.floor(col.detach())
+        on = front & (fr0 + (h + 1) >= 0) & (fr0 - h <= Hs - 1) & (fc0 + (h + 1) >= 0) & (fc0 - h <= Ws - 1)
+        zero = torch.zeros_like(row)
+        row, col, fr0, fc0 = torch.where(on, row, zero), torch.where(on, col, zero), torch.where(on, fr0, zero), torch.where(on, fc0, zero)
+        fr, fc = row - fr0, col - fc0
+        r = (fr0.long() - h)[:, None] + taps
+        c = (fc0.long() - h)[:, None] + taps
+        inside = ((r >= 0) & (r < Hs))[:, :, None] & ((c >= 0) & (c < Ws))[:, None, :]
+        Z = maps[l][r.clamp(0, Hs - 1)[:, :, None], c.clamp(0, Ws - 1)[:, None, :]]
+        u = torch.clamp(((Z - d[:, None, None]) + bias) / softness + 0.5, 0., 1.)
+        S = torch.where(inside, (u * u) * (3. - 2. * u), torch.ones_like(u))
+        middle = [one] * (kernel - 1)
+        wr, wc = torch.stack([1. - fr] + middle + [fr], dim=1), torch.stack([1. - fc] + middle + [fc], dim=1)
+        v = torch.sum(wr[:, :, None] * wc[:, None, :] * S, dim=(1, 2)) * (1. / (kernel * kernel))
+        out.append(torch.where(on, v, one))
+    v = torch.stack(out, dim=1)
+    if mask is None:
+        return v
+    return 1. - _as(mask, p)[:, None] * (1. - v)
+
+
+def _shadow_scalars(kernel, bias, softness, normal_offset):
+    """The four python numbers of `shadow_visibility`, refused outside their ranges -> (kernel, bias, softness, normal_offset)."""
+    if isinstance(kernel, bool) or kernel not in SHADOW_KERNELS:
+        raise ValueError('kernel must be 1, 3 or 5, got %r' % (kernel,))
+    for name, x in (('bias', bias), ('softness', softness), ('normal_offset', normal_offset)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x):
+            raise ValueError('%s must be a finite number, got %r' % (name, x))
+    if not softness > 0:
+        raise ValueError('softness must be > 0, got %r' % (softness,))
+    return int(kernel), float(bias), float(softness), float(normal_offset)

@@ -76,6 +76,25 @@ def perspective_projection(near, far, right, aspect, name=None):
     return out
 
 
+def orthographic_projection(near, far, right, aspect, name=None):
+    """OpenGL orthographic projection (glOrtho, symmetric), camera looking down -z: the box |x| <= right, |y| <= right * aspect,
+    -far <= z <= -near goes to the clip cube with w = 1; parameters broadcast to [A1..An], result [A1..An, 4, 4].  `aspect` =
+    height / width of the viewport, as in `perspective_projection`.  Not in the reference: the projection of a directional
+    light's shadow map (`shading.render_shadow_map`)."""
+    args = [a for a in (near, far, right, aspect) if isinstance(a, torch.Tensor)]
+    like = args[0] if args else None
+    near, far, right, aspect = (_t(a, like) for a in (near, far, right, aspect))
+    top = right * aspect
+    near, far, right, top = torch.broadcast_tensors(near, far, right, top)
+    out = near.new_zeros(near.shape + (4, 4))  # indexed [*, in, out]
+    out[..., 0, 0] = 1. / right
+    out[..., 1, 1] = 1. / top
+    out[..., 2, 2] = -2. / (far - near)
+    out[..., 3, 2] = -(far + near) / (far - near)
+    out[..., 3, 3] = 1.
+    return out
+
+
 def compose(*matrices):
     """Product of the given transforms, the first applied first (dirt/matrices.py:183-207)."""
     if len(matrices) == 0:

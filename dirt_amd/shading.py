@@ -727,3 +727,161 @@ def _check_normal_map_arguments(gbuffer, normal_map, normals, tangents, strength
     if isinstance(strength, bool) or not isinstance(strength, numbers.Real):
         raise ValueError('strength must be a number, got %r' % (strength,))
     return offsets, float(strength), _lib.NORMAL_MAP_ENCODED if encoded else 0
+
+
+# ---- shadow maps (dirt_shadow.hip)
+
+class _ShadowVisibility(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gbuffer, maps, matrices, meta):
+        """maps [1 or B, L, Hs, Ws], matrices [1 or B, L, 4, 4]: float32"""
+        lib = _lib.load()
+        scenes, rows, cols, cg, offsets, lights, hs, ws, scalars = meta
+        maps, matrices = maps.contiguous(), matrices.contiguous()
+        out = torch.empty(tuple(gbuffer.shape[:-1]) + (lights,), dtype=torch.float32, device=gbuffer.device)
+        if scenes * rows * cols:
+            _stage.call(lib.dirt_shadow_forward, gbuffer.device, gbuffer.data_ptr(), maps.data_ptr(), matrices.data_ptr(), out.data_ptr(),
+                        scenes, rows * cols, cg, *offsets, lights, hs, ws, int(maps.shape[0]), int(matrices.shape[0]), *scalars)
+        ctx.save_for_backward(gbuffer, maps, matrices)
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        gbuffer, maps, matrices = ctx.saved_tensors
+        scenes, rows, cols, cg, offsets, lights, hs, ws, scalars = ctx.meta
+        dev = gbuffer.device
+        empty = not scenes * rows * cols
+        grad_g, grad_s, grad_m = _stage.grad_outputs((gbuffer, maps, matrices), ctx.needs_input_grad[:3], empty)
+        if empty:
+            return grad_g, grad_s, grad_m, None
+        grad_out = grad_out.to(torch.float32).contiguous()
+        nbytes = lib.dirt_shadow_scratch_bytes(scenes, rows, cols, lights) if grad_m is not None else 0
+        _stage.call(lib.dirt_shadow_backward, dev, gbuffer.data_ptr(), maps.data_ptr(), matrices.data_ptr(), grad_out.data_ptr(), _ptr(grad_g),
+                    _ptr(grad_s), _ptr(grad_m), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, rows, cols, cg, *offsets, lights, hs, ws,
+                    int(maps.shape[0]), int(matrices.shape[0]), *scalars)
+        return grad_g, grad_s, grad_m, None
+
+
+def shadow_visibility(gbuffer, shadow_maps, light_matrices, *, positions, normals=None, mask=None, kernel=3, bias=0.0, softness,
+                      normal_offset=0.0):
+    """The share of each light that reaches each pixel of a G-buffer, looked up in the lights' shadow maps in one kernel,
+    differentiably: what `lighting.shadow_visibility` computes per point (its docstring is the specification).
+
+    gbuffer: float32 [H, W, Cg], [B, H, W, Cg] or a flat [N, Cg] on the GPU; a contiguous one is read in place.
+    positions, normals, mask: the first channel of each attribute inside a pixel (3, 3 and 1 channels; any order, no
+        overlap).  `positions` holds world-space positions; `normals` is needed only with normal_offset != 0; mask=None:
+        every pixel is covered.
+    shadow_maps: float32 [L, Hs, Ws] with 1 <= L <= 4 (the light count of `shade_gbuffer_pbr`), the clip-space z of the
+        nearest surface as each light sees it: `render_shadow_map` draws one.
+    light_matrices: [L, 4, 4], world -> each light's clip space, right-multiplying row vectors as everything in `matrices`
+        and `vertex_stage`'s view_projection: the matrix its map was drawn with.
+    With a [B, H, W, Cg] G-buffer either may have a leading B ([B, L, Hs, Ws], [B, L, 4, 4]): an operand shared by the scenes
+        has no leading B, one with a leading B has one value per scene.
+    kernel: the side of the percentage-closer filter, 1, 3 or 5.  bias: added to the map's depth before the comparison (in
+        clip z).  softness > 0: the width in clip z over which the comparison goes from shadow to light.  normal_offset: the
+        distance in world units the point is moved along its unit normal before it is projected.  Python numbers, no gradient.
+
+    Returns [..., L]:  1 - m (1 - v)  with v in [0, 1] the filtered comparison: 1 = lit, 0 = in shadow; an uncovered pixel, one
+    behind the light and one whose filter window lies off the map are lit.  Gradients are those of torch's autograd for
+    `lighting.shadow_visibility` and go to the position channels of the G-buffer, its normal channels when used and its mask
+    channel (every other channel gets an exact zero), to `shadow_maps` and to `light_matrices`.  The maps' gradient is summed
+    with float atomics: it is not the same bits on every run, everything else is.
+
+    A shadowed light is `shade_gbuffer_pbr(gbuffer, [light_i], ..., ambient=(0, 0, 0), background=(0, 0, 0), clamp=None) *
+    vis[..., i:i + 1]`; sum these over the lights, add the ambient or image-based term (`shade_gbuffer_ibl(..., clamp=None)`)
+    and the background, then apply one clamp."""
+    g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shadow_visibility')
+    offsets, lights, hs, ws, scalars = _check_shadow_arguments(gbuffer, shadow_maps, light_matrices, positions, normals, mask, kernel, bias,
+                                                               softness, normal_offset)
+    _stage.require_gpu(gbuffer, 'dirt_amd.shading.shadow_visibility')
+    rows, cols = (int(gbuffer.shape[-3]), int(gbuffer.shape[-2])) if gbuffer.dim() >= 3 else (1, pixels)
+    maps, matrices = shadow_maps.to(torch.float32), light_matrices.to(torch.float32)
+    maps = maps if maps.dim() == 4 else maps[None]
+    matrices = matrices if matrices.dim() == 4 else matrices[None]
+    return _ShadowVisibility.apply(g, maps, matrices, (scenes, rows, cols, cg, tuple(offsets), lights, hs, ws, scalars))
+
+
+def _check_shadow_arguments(gbuffer, shadow_maps, light_matrices, positions, normals, mask, kernel, bias, softness, normal_offset):
+    """Everything `shadow_visibility` refuses with a ValueError, on types, shapes and devices alone (no device work): -> (channel
+    offsets (positions, normals, mask), lights, map height, map width, (kernel, bias, softness, normal_offset))."""
+    from .lighting import _shadow_scalars
+    who = 'shadow_visibility'
+    dev, batch = _check_gbuffer(gbuffer, who)
+    ranks = (3, 4) if batch is not None else (3,)
+    forms = '[L, Hs, Ws] or [B, L, Hs, Ws]' if batch is not None else '[L, Hs, Ws]'
+    if not isinstance(shadow_maps, torch.Tensor) or not shadow_maps.is_floating_point() or shadow_maps.dim() not in ranks \
+            or not 1 <= shadow_maps.shape[-3] <= _lib.SHADOW_MAX_LIGHTS or 0 in shadow_maps.shape[-2:]:
+        raise ValueError('%s expects shadow_maps to be a floating-point tensor %s with 1 <= L <= %d and no empty map, got %s'
+                         % (who, forms, _lib.SHADOW_MAX_LIGHTS, tuple(getattr(shadow_maps, 'shape', ()))))
+    lights, hs, ws = (int(s) for s in shadow_maps.shape[-3:])
+    forms = '[%d, 4, 4] or [B, %d, 4, 4]' % (lights, lights) if batch is not None else '[%d, 4, 4]' % lights
+    if not isinstance(light_matrices, torch.Tensor) or not light_matrices.is_floating_point() or light_matrices.dim() not in ranks \
+            or tuple(light_matrices.shape[-3:]) != (lights, 4, 4):
+        raise ValueError('%s expects light_matrices to be a floating-point tensor %s, a matrix per map, got %s'
+                         % (who, forms, tuple(getattr(light_matrices, 'shape', ()))))
+    for name, t in (('shadow_maps', shadow_maps), ('light_matrices', light_matrices)):
+        if t.dim() == 4 and int(t.shape[0]) != batch:
+            raise ValueError('%s: %d scenes of gbuffer, %d of %s' % (who, batch, int(t.shape[0]), name))
+        if t.device != dev:
+            raise ValueError('%s is on %s, the G-buffer on %s' % (name, t.device, dev))
+    offsets = _channel_offsets(gbuffer, (('positions', positions, 3, True), ('normals', normals, 3, False), ('mask', mask, 1, False)))
+    scalars = _shadow_scalars(kernel, bias, softness, normal_offset)
+    if scalars[3] != 0. and normals is None:
+        raise ValueError('%s: normal_offset=%r needs normals' % (who, normal_offset))
+    return offsets, lights, hs, ws, scalars
+
+
+def _shadow_map_operands(vertices, light_matrix, size, far):
+    """What `render_shadow_map` hands to the rasteriser, for one scene or a batch: -> (background [..., Hs, Ws, 1] = far, clip
+    vertices [..., V, 4] = [v, 1] @ M, vertex colours [..., V, 1] = clip z)."""
+    try:
+        hs, ws = (size, size) if isinstance(size, numbers.Integral) else size
+        ok = all(isinstance(s, numbers.Integral) and not isinstance(s, bool) and s >= 1 for s in (hs, ws))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('size must be a positive int or (height, width), got %r' % (size,))
+    if isinstance(far, bool) or not isinstance(far, numbers.Real) or not math.isfinite(far):
+        raise ValueError('far must be a finite number, the clip z of the light\'s far plane, got %r' % (far,))
+    v = vertices.to(torch.float32)
+    clip = torch.matmul(torch.cat([v, torch.ones_like(v[..., :1])], dim=-1), light_matrix.to(torch.float32))
+    background = torch.full(tuple(v.shape[:-2]) + (int(hs), int(ws), 1), float(far), dtype=torch.float32, device=v.device)
+    return background, clip, clip[..., 2:3]
+
+
+def render_shadow_map(vertices, faces, light_matrix, size, far):
+    """The shadow map of one light: vertices [V, 3] (world space), faces [F, 3], light_matrix [4, 4] (world -> the light's clip
+    space, row vectors: `matrices.compose(view, matrices.orthographic_projection(...))` for a directional light, with
+    `perspective_projection` for a spot light), size (an int or (Hs, Ws)) -> float32 [Hs, Ws], the clip-space z of the nearest
+    surface per texel and `far` where there is none.  One 1-channel `rasterise` with the clip z as the vertex colour (clip z is
+    linear in the world position, so the perspective-correct interpolation is exact for either projection); differentiable
+    to the vertices and the matrix through the rasteriser's gradient.
+
+    far: required, the clip z of the light's far plane (1 for an orthographic light, the far distance for a perspective one).
+    The rasteriser's gradient at a silhouette scales with the step between the surface and the background, so a huge sentinel
+    in place of the far plane would blow it up.
+
+    `shadow_visibility` takes `torch.stack` of the lights' maps with the stack of their matrices."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError('render_shadow_map expects vertices [V, 3], got %s' % (tuple(getattr(vertices, 'shape', ())),))
+    if not isinstance(light_matrix, torch.Tensor) or tuple(light_matrix.shape) != (4, 4):
+        raise ValueError('render_shadow_map expects light_matrix [4, 4], got %s' % (tuple(getattr(light_matrix, 'shape', ())),))
+    from .rasterise_ops import rasterise
+    background, clip, depth = _shadow_map_operands(vertices, light_matrix, size, far)
+    return rasterise(background, clip, depth, faces)[..., 0]
+
+
+def render_shadow_map_batch(vertices, faces, light_matrices, size, far):
+    """`render_shadow_map` for a batch: vertices [B, V, 3], faces [F, 3] (one topology for the batch) or [B, F, 3],
+    light_matrices [B, 4, 4] or [4, 4] (one light for every scene) -> [B, Hs, Ws], by one `rasterise_batch`."""
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 3 or vertices.shape[2] != 3:
+        raise ValueError('render_shadow_map_batch expects vertices [B, V, 3], got %s' % (tuple(getattr(vertices, 'shape', ())),))
+    if not isinstance(light_matrices, torch.Tensor) or tuple(light_matrices.shape) not in ((4, 4), (int(vertices.shape[0]), 4, 4)):
+        raise ValueError('render_shadow_map_batch expects light_matrices [4, 4] or [%d, 4, 4], got %s'
+                         % (int(vertices.shape[0]), tuple(getattr(light_matrices, 'shape', ())),))
+    from .rasterise_ops import rasterise_batch
+    background, clip, depth = _shadow_map_operands(vertices, light_matrices, size, far)
+    return rasterise_batch(background, clip, depth, faces)[..., 0]

@@ -734,6 +734,46 @@ int dirt_normal_map_backward(const float *gbuffer, const float *normal_map, cons
                              int off_normals, int off_tangents, float strength, unsigned flags, void *stream);
 
 /*
+ * The look-up of shadow maps from a G-buffer, fused; specification in dirt_amd/csrc/dirt_shadow.hip and DESIGN.md §7h
+ * (dirt_amd/lighting.py::shadow_visibility).  Per pixel and light, with K = kernel and h = (K - 1) / 2:
+ *     q = p + normal_offset n / max(|n|, 1e-12)      (x, y, z, w) = [q, 1] @ M (row vectors)      d = z
+ *     col = (x / w + 1) Ws / 2 - 0.5      row = (1 - y / w) Hs / 2 - 0.5      (r0, fr), (c0, fc): floor - h and fraction
+ *     v = (1 / K^2) sum_{a, b = 0..K} wr[a] wc[b] S(r0 + a, c0 + b),   wr[0] = 1 - fr, wr[K] = fr, 1 between; wc likewise
+ *     S = s((Z[r, c] - d + bias) / softness + 1/2) inside the map, 1 outside;   s(t) = u u (3 - 2 u), u = clamp(t, 0, 1)
+ *     out = 1 - m (1 - v);   v = 1 where not w > 0 or where the whole window lies off the map
+ *   gbuffer [scenes, pixels, Cg] with three channels of world positions at off_positions, three of normals at off_normals
+ *   (-1: none; needed when normal_offset != 0, not read otherwise) and the mask at off_mask (-1: every pixel is covered);
+ *   maps [map_scenes, lights, Hs, Ws] and matrices [matrix_scenes, lights, 4, 4] with map_scenes and matrix_scenes each 1
+ *   (one set serves every scene) or `scenes`; lights: 1..DIRT_SHADOW_MAX_LIGHTS; kernel: 1, 3 or 5; softness > 0
+ *   -> out [scenes, pixels, lights].  One launch.
+ * Backward: rows x cols is a scene's pixel grid (a flat list: rows = 1); grad_out [scenes, rows * cols, lights] ->
+ *   grad_gbuffer [scenes, rows * cols, Cg] (every row written whole, exact zeros in the channels no attribute uses),
+ *   grad_maps like maps (cleared, then added into with float atomics: one per touched texel of a 16 x 16 tile whose window
+ *   box fits the LDS patch, one per tap otherwise and for a flat list; not the same bits on every run) and grad_matrices
+ *   like matrices (per-workgroup sums in `scratch` of dirt_shadow_scratch_bytes(scenes, rows, cols, lights) bytes -- 0:
+ *   invalid sizes --, added in a fixed order: the same bits on every run, as grad_gbuffer).  Each may be NULL and is then
+ *   not computed -- all three NULL: success, nothing is launched.  Zero scenes or pixels: success, grad_maps and
+ *   grad_matrices are cleared.
+ * Refused before any device work, with a sentence in dirt_last_error(): negative sizes, more than 65535 scenes or 2^40
+ *   pixels, a channel count outside 1..DIRT_SHADE_MAX_CHANNELS, a light count outside 1..DIRT_SHADOW_MAX_LIGHTS, a map
+ *   that is empty or has more than 2^31 - 1 texels, map_scenes or matrix_scenes that is neither 1 nor scenes, a kernel
+ *   other than 1, 3, 5, a softness that is not a finite number > 0, a bias or normal_offset that is not finite, a
+ *   normal_offset without normals, attributes that do not fit or overlap, a NULL operand, a pixel grid the backward's
+ *   tiles cannot index, a scratch that is missing, too small or misaligned.
+ */
+#define DIRT_SHADOW_MAX_LIGHTS 4
+size_t dirt_shadow_scratch_bytes(long long scenes, long long rows, long long cols, int lights);
+int dirt_shadow_forward(const float *gbuffer, const float *maps, const float *matrices, float *out, long long scenes,
+                        long long pixels, int Cg, int off_positions, int off_normals, int off_mask, int lights, int Hs, int Ws,
+                        int map_scenes, int matrix_scenes, int kernel, float bias, float softness, float normal_offset,
+                        void *stream);
+int dirt_shadow_backward(const float *gbuffer, const float *maps, const float *matrices, const float *grad_out,
+                         float *grad_gbuffer, float *grad_maps, float *grad_matrices, void *scratch, size_t scratch_bytes,
+                         long long scenes, long long rows, long long cols, int Cg, int off_positions, int off_normals,
+                         int off_mask, int lights, int Hs, int Ws, int map_scenes, int matrix_scenes, int kernel, float bias,
+                         float softness, float normal_offset, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
