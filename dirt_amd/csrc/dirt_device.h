@@ -29,6 +29,37 @@ __device__ __forceinline__ void st_off(void* base, uint32_t off, T v)
     *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v;
 }
 
+// The same stores WRITTEN THROUGH the XCD's L2 (`sc1`): the bytes leave for memory while the launch still computes, not as
+// dirty lines that are written back after its last wave, and the line is dropped from that L2 -- for outputs that nothing of
+// the launch, and nobody on this XCD soon after it, reads again.  16 and 8 bytes only: narrower write-through
+// stores cost several times a plain store's time per byte.
+//   16 bytes: a raw buffer store with the sc1 bit (aux = 16) through a descriptor of the whole address range behind `base`
+//             (no stride, no bounds to speak of: offsets up to 2^32 - 17): `buffer_store_dwordx4 ... offen sc1`.  A store the
+//             compiler knows -- it counts it in vmcnt as it counts a plain one -- at the price of four SGPRs per base.
+//    8 bytes: a relaxed agent-scope atomic store, which is `global_store_dwordx2 ... sc1`.
+typedef uint32_t dirt_u32x4 __attribute__((ext_vector_type(4)));
+template <class T>
+__device__ __forceinline__ void st_off_wt(void* base, uint32_t off, T v)
+{
+    static_assert(sizeof(T) == 16 || sizeof(T) == 8, "write-through stores: 16 or 8 bytes");
+    if constexpr (sizeof(T) == 16) {
+        dirt_u32x4 d;
+        __builtin_memcpy(&d, &v, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(d, __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000), (int)off, 0, 16);
+    } else {
+        unsigned long long d;
+        __builtin_memcpy(&d, &v, 8);
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(base) + off), d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// (written through or not by a compile-time rule of the kernel)
+template <bool WT, class T>
+__device__ __forceinline__ void st_off_if(void* base, uint32_t off, T v)
+{
+    if constexpr (WT) st_off_wt<T>(base, off, v);
+    else st_off<T>(base, off, v);
+}
+
 struct Float3 { float x, y, z; };   // three channels of a pixel or of a vertex colour: one 12-byte load / store (4-byte aligned)
 
 // One set-up triangle, 128 bytes, 128-byte aligned so a record is one L2 line and can be fetched

@@ -336,6 +336,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
     p.grid.shift = a_shift; p.grid.bins_x = a_bins_x; p.grid.big = a_big; p.grid.cell_chunk_stride = a_chunk_stride;
     constexpr int NB = 2, NBY = WAVES == 8 ? 1 : 2, TILE = 32, PPL = NB * NBY, THREADS = 64 * WAVES, RH = 8 * NBY;
     constexpr bool COLOURS = MODE == 0;
+    // The one-round 4-channel shape writes its outputs -- `pixels`, the state planes -- THROUGH the L2 (st_off_wt): its early tiles'
+    // bytes leave while its heaviest waves still compute, not as dirty lines after the last wave (K3 step -1.1 us of the -1.7;
+    // DESIGN.md 4.3).  Plain elsewhere: in launches of several rounds the write-back overlaps the next round anyway, and the
+    // gradient kernel then misses the lines in its XCD's L2 (K3-2048 raster 49.5 -> 57.9 us, eight scenes per launch 97.9 ->
+    // 111.5 written through); with 3 channels, whose pixels are 12-byte stores, the planes alone cost the step +0.3 us.
+    constexpr bool WT = WAVES == 8 && CSPEC == 4;
     constexpr int SPARTS = COLOURS ? 9 : 6;
     using Slot = ShadeSlot<COLOURS>;
     __shared__ __align__(16) TileRec s_rec[V2_CAP];
@@ -642,10 +648,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 8 : DIRT_V2_WAVES) void ra
         if (!inside) continue;
         // the backward pass's state and the visibility export
         if (p.vis) st_off<int32_t>(vis_base, rel * 4u, f);
-        if (p.state_a) store_state(sa_base, sb_base, rel * 8u, has, b0, b1, b2, cw, f);
+        if (p.state_a) store_state<WT>(sa_base, sb_base, rel * 8u, has, b0, b1, b2, cw, f);
         if (MODE != 0) continue;
         const uint32_t off = rel * (uint32_t)(C * sizeof(float));
-        if (CSPEC == 4) st_off<float4>(out_base, off, o);
+        if (CSPEC == 4) st_off_if<WT, float4>(out_base, off, o);
         else if (CSPEC == 3) { st_off<float>(out_base, off, o.x); st_off<float>(out_base, off + 4u, o.y); st_off<float>(out_base, off + 8u, o.z); }
         else st_off<float>(out_base, off, o.x);
     }

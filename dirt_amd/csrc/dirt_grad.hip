@@ -799,7 +799,10 @@ __global__ __launch_bounds__(GTHREADS, CSPEC == 6 ? TWO3_WAVES : (AI ? 5 : 4)) v
                 const int ry_ = 2 * k + (lane >> 5), yy = y0 + 8 * wave + ry_;
                 if (!ok[k]) continue;
                 const uint32_t off = (uint32_t)((yy - row0) * W + x0 + cx) * 16u;
-                st_off<float4>(gbk_t, off, fq[k] >= 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : gq[k]);
+                // written through the L2: nothing of the step reads it again, and 16.8 MB of dirty lines are not left for the end of
+                // the launch (K3 step -0.6 us) -- but not by the rows form, whose launches of at most one workgroup
+                // per compute unit have little to write back (K3-384: +0.2 us written through)
+                st_off_if<!ROWS, float4>(gbk_t, off, fq[k] >= 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : gq[k]);
             }
             return;
         }

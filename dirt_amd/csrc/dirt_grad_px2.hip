@@ -487,7 +487,7 @@ __global__ __launch_bounds__(XTHREADS, DIRT_PX2_WAVES(CSPEC, DEBUG)) void grad_k
         const uint32_t off = own_off + (uint32_t)j * pixel_bytes;
         auto gval = [&](int c) { return (c & 1) ? fp[j][c / 2].y : fp[j][c / 2].x; };
         if constexpr (CSPEC == 4) {
-            st_off<float4>(gbk_t, off, covered[j] ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(gval(0), gval(1), gval(2), gval(3)));
+            st_off_wt<float4>(gbk_t, off, covered[j] ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(gval(0), gval(1), gval(2), gval(3)));
         } else if constexpr (CSPEC == 3) {
             st_off<Float3>(gbk_t, off, covered[j] ? Float3{0.f, 0.f, 0.f} : Float3{gval(0), gval(1), gval(2)});
         } else {

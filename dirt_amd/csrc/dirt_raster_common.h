@@ -230,10 +230,12 @@ __device__ __forceinline__ void raster_candidate_pair(const TileRec& t0, const T
 // (encode_bary, dirt_device.h; the face index stands for the index triple) -- or the clear values of
 // csrc/rasterise_grad_egl.cpp:442-445.
 // (plane_a, plane_b: wave-uniform bases; off: the pixel's byte offset in either plane, 8 bytes per pixel)
+// WT: written through the L2 (st_off_wt) -- the one-round 4-channel shape of raster_kernel_v2 only.
+template <bool WT = false>
 __device__ __forceinline__ void store_state(float2* plane_a, float2* plane_b, uint32_t off, bool has, float b0, float b1, float b2, float clip_w, int32_t face)
 {
-    *reinterpret_cast<float2*>(reinterpret_cast<char*>(plane_a) + off) = make_float2(has ? clip_w : INFINITY, __int_as_float(face));
-    *reinterpret_cast<float2*>(reinterpret_cast<char*>(plane_b) + off) = has ? encode_bary(b0, b1, b2) : make_float2(-1.f, -1.f);
+    st_off_if<WT, float2>(plane_a, off, make_float2(has ? clip_w : INFINITY, __int_as_float(face)));
+    st_off_if<WT, float2>(plane_b, off, has ? encode_bary(b0, b1, b2) : make_float2(-1.f, -1.f));
 }
 __device__ __forceinline__ void store_state(const RasterParams& p, size_t pix, bool has, float b0, float b1, float b2, float clip_w, int32_t face)
 {
