@@ -71,6 +71,7 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_shade_scratch_bytes', 'dirt_shade_forward', 'dirt_shade_backward', 'dirt_shade_albedo_forward', 'dirt_shade_albedo_backward',
            'dirt_shade_sh_scratch_bytes', 'dirt_shade_sh_forward', 'dirt_shade_sh_backward',
            'dirt_shade_pbr_scratch_bytes', 'dirt_shade_pbr_forward', 'dirt_shade_pbr_backward',
+           'dirt_shade_pbr_visibility_forward', 'dirt_shade_pbr_visibility_backward',
            'dirt_shade_ibl_scratch_bytes', 'dirt_shade_ibl_forward', 'dirt_shade_ibl_backward',
            'dirt_geometry_scratch_bytes', 'dirt_geometry_forward', 'dirt_geometry_backward',
            'dirt_skin_scratch_bytes', 'dirt_skin_forward', 'dirt_skin_backward',
@@ -199,6 +200,12 @@ def load():
         lib.dirt_shade_pbr_forward.restype = i
         lib.dirt_shade_pbr_backward.argtypes = [fp] * 9 + [vp, sz, ll, ll] + [i] * 10 + [u, f32, f32, f32, f32, u, vp]
         lib.dirt_shade_pbr_backward.restype = i
+    if hasattr(lib, 'dirt_shade_pbr_visibility_forward') or not override:   # ... with a visibility per light (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_shade_pbr_visibility_forward.argtypes = [fp] * 6 + [ll, ll] + [i] * 11 + [u, f32, f32, f32, f32, u, vp]
+        lib.dirt_shade_pbr_visibility_forward.restype = i
+        lib.dirt_shade_pbr_visibility_backward.argtypes = [fp] * 11 + [vp, sz, ll, ll] + [i] * 11 + [u, f32, f32, f32, f32, u, vp]
+        lib.dirt_shade_pbr_visibility_backward.restype = i
     if hasattr(lib, 'dirt_shade_ibl_forward') or not override:   # image-based G-buffer lighting (ABI 4, additive)
         f32 = ctypes.c_float
         lib.dirt_shade_ibl_scratch_bytes.argtypes = [ll, ll, ll]

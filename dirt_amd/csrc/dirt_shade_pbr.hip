@@ -13,11 +13,17 @@
 //                 D   = a2 / (pi den^2),  den = |N x h|^2 + a2 nh^2
 //                 Vis = 0.25 / ((nl (1 - k) + k) (nv (1 - k) + k))
 //                 w = 1 - vh,  F_j = F0_j + (1 - F0_j) ((w w)(w w) w)       kd_j = (1 - F_j)(1 - mu)
-//                 L_i,j = (kd_j c_j / pi + D Vis F_j) k_i,j nl
+//                 L_i,j = (kd_j c_j / pi + D Vis F_j) k_i,j nl          with a visibility s_i (below):  ... ((k_i,j nl) s_i)
 //     out_j = clamp((ambient_j c_j + sum_i L_i,j) m + background_j (1 - m), lo, hi)
 //
 //  Gradients are torch autograd's for that composition: max(x, 0) and the clamps pass the gradient at their edges, the norm
 //  of a zero vector has gradient 0, and max(|x|, 1e-12) passes the gradient to |x| from 1e-12 up.
+//
+// Visibility (VIS; dirt_shade_pbr_visibility_forward / _backward): one factor s_i per light and pixel, the output of
+// dirt_shadow_forward, scales the light's weight: (k_i,j nl) s_i, one more float32 multiplication of a value the kernel has,
+// nothing reordered -- s = 1 gives the bits of the kernels without it.  s is not clamped (a NaN, an inf or a value outside
+// [0, 1] behaves as IEEE says), the ambient term is not shadowed.  With gknl_j = glit_j B_j:  d s_i = sum_j gknl_j (k_i,j nl);
+// the colour's and nl's gradients take gknl_j s_i for gknl_j; gB_j = glit_j ((k_i,j nl) s_i).
 //
 // The parameter block is [scenes or 1, 9 + 8 lights] floats in the layout of dirt_shade.hip's: ambient, background, camera,
 // then per light {vector[3], colour[3], 0, 0}.  The light kinds (one bit per light), the two scalars of the material model,
@@ -30,6 +36,12 @@
 // scene: the forward again, d gbuffer through an LDS tile so that every row leaves whole, the tensors' gradients by one dense
 // store per lane, the parameter sums in registers under compile-time indices (hence the template on the light count), then
 // wave_sum -> fold_waves_to_row -> one row per workgroup in caller scratch -> shade_launch_reduce in a fixed order.  No atomics.
+// VIS is a compile-time parameter of the kernels, one value per translation unit (PBR_VIS): a pixel's factors are `lights`
+// consecutive floats, `vstride` apart from pixel to pixel, read in place; d visibility leaves dense, [scenes, pixels, lights],
+// by a store per lane and light where P.gvis is there.  This file is two translation units of the parallel build: by itself
+// the kernels and entry points without a visibility, and through dirt_shade_pbr_visibility.hip (which defines
+// DIRT_SHADE_PBR_VISIBILITY_UNIT, includes it and holds the two entry points) the VIS = true kernels, lights 1..4, under names
+// of their own.  (As one templated body behind two sets of __global__ wrappers the kernels without VIS took other registers.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dirt_shade_common.h"
@@ -60,6 +72,41 @@ struct ShadePbrParams {
     int clamp;
     float lo, hi, min_roughness, f0;
 };
+
+// with a visibility: what the VIS kernels take (the others' argument stays as it is)
+struct ShadePbrVisParams : ShadePbrParams {
+    const float* vis;      // a pixel's factors: nl floats, vstride apart
+    float* gvis;           // [scenes, pixels, nl] or nullptr
+    int vstride;
+};
+
+#ifdef DIRT_SHADE_PBR_VISIBILITY_UNIT   // this unit's kernels: their names, their argument, whether they take a visibility
+#define PBR_FORWARD_KERNEL shade_visible_pbr_forward_kernel
+#define PBR_BACKWARD_KERNEL shade_visible_pbr_backward_kernel
+typedef ShadePbrVisParams PbrUnitParams;
+constexpr bool PBR_VIS = true;
+#else
+#define PBR_FORWARD_KERNEL shade_pbr_forward_kernel
+#define PBR_BACKWARD_KERNEL shade_pbr_backward_kernel
+typedef ShadePbrParams PbrUnitParams;
+constexpr bool PBR_VIS = false;
+#endif
+
+// light l's factor at a pixel, and where its gradient goes (templates, so that only the VIS unit's argument needs the fields)
+template <bool VIS, class PRM>
+__device__ __forceinline__ float pbr_visibility(const PRM& P, long long pix, int l)
+{
+    if constexpr (VIS) return P.vis[pix * P.vstride + l];
+    else return 1.f;
+}
+
+template <bool VIS, int NL, class PRM>
+__device__ __forceinline__ void pbr_store_grad_visibility(const PRM& P, long long pix, int l, float g)
+{
+    if constexpr (VIS) {
+        if (P.gvis) P.gvis[pix * NL + l] = g;
+    }
+}
 
 // what the lights of a pixel share: the material's, and the GGX terms
 struct PbrPixel : MaterialPixel { float rho2, a2, k, omk, gv; };
@@ -112,7 +159,7 @@ __device__ __forceinline__ void pbr_light(const float* __restrict__ lp, bool poi
 }
 
 // ---- forward: one pixel per lane; the parameters are wave-uniform (scalar loads), the loop over the lights is uniform
-__global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrParams P)
+__global__ __launch_bounds__(PBR_BLOCK) void PBR_FORWARD_KERNEL(PbrUnitParams P)
 {
     const long long i = (long long)blockIdx.x * PBR_BLOCK + threadIdx.x;
     if (i >= P.pixels) return;
@@ -127,8 +174,14 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrPa
         const float* __restrict__ lp = prm + PBR_HEAD + PBR_LIGHT * l;
         PbrLight L;
         pbr_light(lp, (P.kinds >> l) & 1u, px, L);
+        if constexpr (PBR_VIS) {
+            const float sv = pbr_visibility<PBR_VIS>(P, pix, l);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * (lp[3 + j] * L.nl);
+            for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * ((lp[3 + j] * L.nl) * sv);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * (lp[3 + j] * L.nl);
+        }
     }
     const float om = 1.f - px.m;
     float o[3];
@@ -138,9 +191,10 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_forward_kernel(ShadePbrPa
 }
 
 // ---- backward.  NL: the light count; PARAMS: the parameter block wants its gradient; GBUF: the G-buffer does.  The
-// gradients of a colour / material tensor leave by one store per lane where P.gcol / P.gmat is there.
+// gradients of a colour / material tensor leave by one store per lane where P.gcol / P.gmat is there, the visibility's
+// (VIS) by one per lane and light where P.gvis is.
 template <int NL, bool PARAMS, bool GBUF>
-__global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrParams P)
+__global__ __launch_bounds__(PBR_BLOCK) void PBR_BACKWARD_KERNEL(PbrUnitParams P)
 {
     constexpr int NP = PBR_HEAD + PBR_LIGHT * NL;
     constexpr int NA = PARAMS ? NP : 1;
@@ -178,8 +232,14 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                 const float* __restrict__ lp = prm + PBR_HEAD + PBR_LIGHT * l;
                 PbrLight L;
                 pbr_light(lp, (P.kinds >> l) & 1u, px, L);
+                if constexpr (PBR_VIS) {
+                    const float sv = pbr_visibility<PBR_VIS>(P, pix, l);
 #pragma unroll
-                for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * (lp[3 + j] * L.nl);
+                    for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * ((lp[3 + j] * L.nl) * sv);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) lit[j] += L.B[j] * (lp[3 + j] * L.nl);
+                }
             }
             const float om = 1.f - px.m;
             float glit[3], gc[3], gm = 0.f, gmb = 0.f;
@@ -208,10 +268,21 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                 pbr_light(lp, point, px, L);
                 const float S = L.D * L.Vis;
                 float g_nl = 0.f, gS = 0.f, g_w5 = 0.f;
+                [[maybe_unused]] const float sv = pbr_visibility<PBR_VIS>(P, pix, l);
+                [[maybe_unused]] float gsv = 0.f;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const float gB = glit[j] * (lp[3 + j] * L.nl);
-                    const float gknl = glit[j] * L.B[j];
+                    float gB, gknl;
+                    if constexpr (PBR_VIS) {
+                        const float knl = lp[3 + j] * L.nl;
+                        gB = glit[j] * (knl * sv);
+                        gknl = glit[j] * L.B[j];
+                        gsv += gknl * knl;
+                        gknl = gknl * sv;
+                    } else {
+                        gB = glit[j] * (lp[3 + j] * L.nl);
+                        gknl = glit[j] * L.B[j];
+                    }
                     if constexpr (PARAMS) acc[PBR_HEAD + PBR_LIGHT * l + 3 + j] += gknl * L.nl;
                     g_nl += gknl * lp[3 + j];
                     const float gkd = (gB * px.c[j]) * PBR_INV_PI;
@@ -222,6 +293,7 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
                     gF0[j] += gF * (1.f - L.w5);
                     g_w5 += gF * (1.f - px.F0[j]);
                 }
+                if constexpr (PBR_VIS) pbr_store_grad_visibility<PBR_VIS, NL>(P, pix, l, gsv);
                 const float g_vh = -(g_w5 * (5.f * L.w4));
                 const float gD = gS * L.Vis, gVis = gS * L.D;
                 const float t = -(gVis * L.Vis);          // Vis = 0.25 / (gl gv)
@@ -310,12 +382,12 @@ __global__ __launch_bounds__(PBR_BLOCK) void shade_pbr_backward_kernel(ShadePbrP
 }
 
 template <int NL>
-static void shade_pbr_launch_backward(const ShadePbrParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
+static void shade_pbr_launch_backward(const PbrUnitParams& P, bool params, bool gbuf, dim3 grid, hipStream_t s)
 {
-    if (params && gbuf) hipLaunchKernelGGL((shade_pbr_backward_kernel<NL, true, true>), grid, dim3(PBR_BLOCK), 0, s, P);
-    else if (params) hipLaunchKernelGGL((shade_pbr_backward_kernel<NL, true, false>), grid, dim3(PBR_BLOCK), 0, s, P);
-    else if (gbuf) hipLaunchKernelGGL((shade_pbr_backward_kernel<NL, false, true>), grid, dim3(PBR_BLOCK), 0, s, P);
-    else hipLaunchKernelGGL((shade_pbr_backward_kernel<NL, false, false>), grid, dim3(PBR_BLOCK), 0, s, P);
+    if (params && gbuf) hipLaunchKernelGGL((PBR_BACKWARD_KERNEL<NL, true, true>), grid, dim3(PBR_BLOCK), 0, s, P);
+    else if (params) hipLaunchKernelGGL((PBR_BACKWARD_KERNEL<NL, true, false>), grid, dim3(PBR_BLOCK), 0, s, P);
+    else if (gbuf) hipLaunchKernelGGL((PBR_BACKWARD_KERNEL<NL, false, true>), grid, dim3(PBR_BLOCK), 0, s, P);
+    else hipLaunchKernelGGL((PBR_BACKWARD_KERNEL<NL, false, false>), grid, dim3(PBR_BLOCK), 0, s, P);
 }
 
 }  // namespace dirt
@@ -336,6 +408,8 @@ static int shade_pbr_check(const char* who, const dirt::MaterialArgs& a, long lo
     P.nl = lights; P.kinds = light_kinds;
     return DIRT_OK;
 }
+
+#ifndef DIRT_SHADE_PBR_VISIBILITY_UNIT
 
 size_t dirt_shade_pbr_scratch_bytes(long long scenes, long long pixels, int lights)
 {
@@ -402,5 +476,7 @@ int dirt_shade_pbr_backward(const float* gbuffer, const float* colors, const flo
     }
     return dirt::shade_backward_finish(who, scratch, grad_params, scenes, blocks, DIRT_SHADE_PARAM_HEAD + DIRT_SHADE_PARAM_LIGHT * lights, param_scenes, s);
 }
+
+#endif   // (the entry points with a visibility: dirt_shade_pbr_visibility.hip)
 
 }  // extern "C"

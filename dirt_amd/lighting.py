@@ -206,7 +206,7 @@ def cook_torrance_lobes(vertex_positions, vertex_normals, vertex_colors, roughne
 
 
 def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, metalness, camera_position, lights,
-                  min_roughness=0.04, dielectric_f0=0.04):
+                  min_roughness=0.04, dielectric_f0=0.04, visibility=None):
     """Metallic-roughness reflectance under directional and point lights, summed.
     positions, normals, colours (albedo) [*, V, 3]; roughness, metalness [*, V]; camera_position [*, 3];
     lights: records ('directional', direction [*, 3], color [*, 3]) or ('point', position [*, 3], color [*, 3]) -> [*, V, 3]
@@ -220,8 +220,10 @@ def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, me
                     D   = a2 / (pi den^2),  den = |n^ x h|^2 + a2 nh^2
                     Vis = 0.25 / ((nl (1 - k) + k) (nv (1 - k) + k))
                     w = 1 - vh,  F_j = F0_j + (1 - F0_j) ((w w)(w w) w)       kd_j = (1 - F_j)(1 - mu)
-                    L_j = (kd_j c_j / pi + D Vis F_j) color_j nl
+                    L_j = (kd_j c_j / pi + D Vis F_j) color_j nl          with visibility:  ... ((color_j nl) s)
 
+    visibility: None or [*, V, L], one factor s per light (`shadow_visibility`'s output): a plain multiplication of the light's
+    weight, not clamped; all ones give the bits of the call without it.
     `den` is written with the cross product (|n^ x h|^2 = 1 - nh^2 for unit vectors): the subtractive form nh^2 (a2 - 1) + 1
     loses four decimal digits in float32 at low roughness.  `Vis` is the Smith-Schlick term with the 4 nl nv of the
     microfacet denominator cancelled: nothing divides by a cosine.  min_roughness in (0, 1] and dielectric_f0 in [0, 1] are
@@ -230,7 +232,13 @@ def cook_torrance(vertex_positions, vertex_normals, vertex_colors, roughness, me
                                 min_roughness, dielectric_f0)
     p = _as(vertex_positions, torch.zeros((), dtype=torch.float32))
     total = torch.zeros_like(_as(vertex_colors, p) + p)
-    for diffuse, specular, weight, _ in lobes:
+    if visibility is not None:
+        visibility = _as(visibility, p)
+        if visibility.shape[-1] != len(lobes):
+            raise ValueError('visibility has %d channels for %d lights' % (visibility.shape[-1], len(lobes)))
+    for i, (diffuse, specular, weight, _) in enumerate(lobes):
+        if visibility is not None:
+            weight = weight * visibility[..., i:i + 1]
         total = total + (diffuse + specular) * weight
     return total
 

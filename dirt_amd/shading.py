@@ -425,16 +425,24 @@ def pbr_point_light(position, color):
 
 class _ShadeGBufferPBR(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, gbuffer, block, colors, material, meta):
-        """colors / material: None (channels of the G-buffer) or float32 [..., 3] / [..., 2] beside it, read in place under
-        `_stage.rows_in_place`"""
+    def forward(ctx, gbuffer, block, colors, material, visibility, meta):
+        """colors / material: None (channels of the G-buffer) or float32 [..., 3] / [..., 2] beside it, visibility: None or
+        float32 [..., lights]; each read in place under `_stage.rows_in_place`"""
         lib = _lib.load()
         scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = meta
         out, block, csrc, msrc, *strides = _forward_operands(gbuffer, block, colors, material)
-        if scenes * pixels:
+        vsrc = None
+        if visibility is not None:
+            vsrc, vstride = _stage.rows_in_place(visibility, nl)
+            strides = strides + [vstride]
+        if scenes * pixels and vsrc is None:
             _stage.call(lib.dirt_shade_pbr_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), out.data_ptr(),
                         scenes, pixels, cg, *strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
-        ctx.save_for_backward(gbuffer, block, csrc, msrc)
+        elif scenes * pixels:
+            _stage.call(lib.dirt_shade_pbr_visibility_forward, gbuffer.device, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), vsrc.data_ptr(),
+                        block.data_ptr(), out.data_ptr(), scenes, pixels, cg, *strides, *offsets, int(block.shape[0]), nl, kinds, *scalars,
+                        lo, hi, flags)
+        ctx.save_for_backward(gbuffer, block, csrc, msrc, vsrc)
         ctx.meta, ctx.strides = meta, strides
         return out
 
@@ -442,21 +450,29 @@ class _ShadeGBufferPBR(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         lib = _lib.load()
-        gbuffer, block, csrc, msrc = ctx.saved_tensors
+        gbuffer, block, csrc, msrc, vsrc = ctx.saved_tensors
         scenes, pixels, cg, offsets, nl, kinds, scalars, lo, hi, flags = ctx.meta
         dev = gbuffer.device
-        grad_g, grad_p, grad_c, grad_m, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, not scenes * pixels, csrc, msrc)
+        empty = not scenes * pixels
+        (grad_v,) = _stage.dense_grads(grad_out, (nl,), (vsrc is not None and ctx.needs_input_grad[4],), empty)
+        grad_g, grad_p, grad_c, grad_m, grad_out = _backward_operands(ctx.needs_input_grad, grad_out, gbuffer, block, empty, csrc, msrc)
         if grad_out is None:
-            return grad_g, grad_p, grad_c, grad_m, None
+            return grad_g, grad_p, grad_c, grad_m, grad_v, None
         nbytes = lib.dirt_shade_pbr_scratch_bytes(scenes, pixels, nl) if grad_p is not None else 0
-        _stage.call(lib.dirt_shade_pbr_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), grad_out.data_ptr(),
-                    _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg,
-                    *ctx.strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
-        return grad_g, grad_p, grad_c, grad_m, None
+        if vsrc is None:
+            _stage.call(lib.dirt_shade_pbr_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), block.data_ptr(), grad_out.data_ptr(),
+                        _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_p), _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg,
+                        *ctx.strides, *offsets, int(block.shape[0]), nl, kinds, *scalars, lo, hi, flags)
+        else:
+            _stage.call(lib.dirt_shade_pbr_visibility_backward, dev, gbuffer.data_ptr(), _ptr(csrc), _ptr(msrc), vsrc.data_ptr(), block.data_ptr(),
+                        grad_out.data_ptr(), _ptr(grad_g), _ptr(grad_c), _ptr(grad_m), _ptr(grad_v), _ptr(grad_p),
+                        _ptr(_stage.scratch(dev, nbytes)), nbytes, scenes, pixels, cg, *ctx.strides, *offsets, int(block.shape[0]), nl, kinds,
+                        *scalars, lo, hi, flags)
+        return grad_g, grad_p, grad_c, grad_m, grad_v, None
 
 
 def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, camera_position, mask=None, ambient=(0., 0., 0.),
-                      background=(0., 0., 0.), clamp=(0., 1.), min_roughness=0.04, dielectric_f0=0.04):
+                      background=(0., 0., 0.), clamp=(0., 1.), min_roughness=0.04, dielectric_f0=0.04, visibility=None):
     """Lights a G-buffer per pixel with the Cook-Torrance metallic-roughness model in one kernel, differentiably: what
     `lighting.cook_torrance` computes per vertex (GGX distribution, Smith-Schlick visibility, Schlick Fresnel; its docstring
     is the specification), composited and clamped as `shade_gbuffer` does.
@@ -471,6 +487,11 @@ def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, 
         tensors are differentiable.  Directions are normalised by the shader; point lights have no distance fall-off.
     min_roughness (in (0, 1]: the roughness is clamped to [min_roughness, 1]) and dielectric_f0 (in [0, 1]: the Fresnel
         reflectance of a non-metal at normal incidence): python numbers, not differentiable.
+    visibility: None, or a floating-point tensor shaped like the G-buffer with len(lights) channels on its device -- the output
+        of `shadow_visibility`: light i's term is multiplied by visibility[..., i], as it is (no clamp; the ambient term is not
+        shadowed; all ones give the bits of the call without it).  Differentiable, and read in place where its pixels lie a
+        constant stride >= len(lights) floats apart (`shadow_visibility`'s output, a slice `t[..., 1:1 + L]`).  There is no
+        channel-index form: the look-up's output is a tensor of its own, and the G-buffer's gradient tile has no slot for it.
 
     Returns [..., 3]:  clamp((ambient * c + sum of the lights' terms) * m + background * (1 - m), lo, hi).
     Gradients are those of torch's autograd for that composition, including at the kinks (max(x, 0) and the clamps pass the
@@ -483,9 +504,29 @@ def shade_gbuffer_pbr(gbuffer, lights, *, colors, material, normals, positions, 
     offsets, kinds, scalars, lo, hi, flags, const, tensors = _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask,
                                                                                    ambient, camera_position, background, clamp, min_roughness,
                                                                                    dielectric_f0)
+    _check_pbr_visibility(gbuffer, len(lights), visibility)
     block = _splice_block(gbuffer.device, const, tensors)
     meta = (scenes, pixels, cg, tuple(offsets), len(lights), kinds, scalars, lo, hi, flags)
-    return _ShadeGBufferPBR.apply(g, block, _as_input(colors), _as_input(material), meta)
+    return _ShadeGBufferPBR.apply(g, block, _as_input(colors), _as_input(material), _as_input(visibility), meta)
+
+
+def _check_pbr_visibility(gbuffer, n_lights, visibility):
+    """What `shade_gbuffer_pbr` refuses of its `visibility` with a ValueError, on shapes and devices alone (after
+    `_check_pbr_arguments`; None passes)."""
+    if visibility is None:
+        return
+    if not isinstance(visibility, torch.Tensor):
+        raise ValueError('visibility must be a tensor (there is no channel-index form), got %r' % (visibility,))
+    if n_lights == 0:
+        raise ValueError('visibility needs at least one light, got none')
+    want = list(gbuffer.shape[:-1]) + [n_lights]
+    if list(visibility.shape) != want:
+        raise ValueError("visibility must have shape %s (the G-buffer's %s with one channel per light), got %s"
+                         % (want, list(gbuffer.shape), list(visibility.shape)))
+    if not visibility.dtype.is_floating_point:
+        raise ValueError('visibility must be floating-point, got %s' % visibility.dtype)
+    if visibility.device != gbuffer.device:
+        raise ValueError('visibility is on %s, the G-buffer on %s' % (visibility.device, gbuffer.device))
 
 
 def _check_pbr_arguments(gbuffer, lights, colors, material, normals, positions, mask, ambient, camera_position, background, clamp,
@@ -790,9 +831,10 @@ def shadow_visibility(gbuffer, shadow_maps, light_matrices, *, positions, normal
     channel (every other channel gets an exact zero), to `shadow_maps` and to `light_matrices`.  The maps' gradient is summed
     with float atomics: it is not the same bits on every run, everything else is.
 
-    A shadowed light is `shade_gbuffer_pbr(gbuffer, [light_i], ..., ambient=(0, 0, 0), background=(0, 0, 0), clamp=None) *
-    vis[..., i:i + 1]`; sum these over the lights, add the ambient or image-based term (`shade_gbuffer_ibl(..., clamp=None)`)
-    and the background, then apply one clamp."""
+    `shade_gbuffer_pbr(gbuffer, lights, ..., visibility=vis)` takes the result as it is and shadows its lights in the one call.
+    The other shaders have no such operand: there a shadowed light is a call with that light alone (`ambient=(0, 0, 0),
+    background=(0, 0, 0), clamp=None`) times `vis[..., i:i + 1]`, summed over the lights, plus the ambient or image-based term
+    (`shade_gbuffer_ibl(..., clamp=None)`) and the background, under one clamp."""
     g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shadow_visibility')
     offsets, lights, hs, ws, scalars = _check_shadow_arguments(gbuffer, shadow_maps, light_matrices, positions, normals, mask, kernel, bias,
                                                                softness, normal_offset)

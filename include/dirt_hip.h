@@ -480,6 +480,30 @@ int dirt_shade_pbr_backward(const float *gbuffer, const float *colors, const flo
                             int color_stride, int material_stride, int off_colors, int off_material, int off_normals,
                             int off_positions, int off_mask, int param_scenes, int lights, unsigned light_kinds,
                             float min_roughness, float dielectric_f0, float clamp_lo, float clamp_hi, unsigned flags, void *stream);
+/*
+ * The same with a visibility: one factor s_i per light and pixel (the output of dirt_shadow_forward) scales the light's weight,
+ *     L_i,j = (kd_j c_j / pi + D Vis F_j) ((colour_i,j nl) s_i)
+ * a plain float32 multiplication: s is not clamped, the ambient term is not shadowed, and s = 1 everywhere gives the bits of
+ * dirt_shade_pbr_forward / _backward.  visibility: a pixel's `lights` factors are consecutive floats, visibility_stride >=
+ * lights floats from pixel to pixel ([scenes, pixels, visibility_stride], read in place); lights: 1..DIRT_SHADE_PBR_MAX_LIGHTS
+ * (0 is refused: there is nothing to scale).  Backward: grad_visibility [scenes, pixels, lights], dense, or NULL; the other
+ * outputs and the scratch (dirt_shade_pbr_scratch_bytes) as dirt_shade_pbr_backward's -- all five NULL: success, nothing is
+ * launched.  No atomics, the same bits on every run.
+ */
+int dirt_shade_pbr_visibility_forward(const float *gbuffer, const float *colors, const float *material, const float *visibility,
+                                      const float *params, float *out, long long scenes, long long pixels, int Cg,
+                                      int color_stride, int material_stride, int visibility_stride, int off_colors,
+                                      int off_material, int off_normals, int off_positions, int off_mask, int param_scenes,
+                                      int lights, unsigned light_kinds, float min_roughness, float dielectric_f0, float clamp_lo,
+                                      float clamp_hi, unsigned flags, void *stream);
+int dirt_shade_pbr_visibility_backward(const float *gbuffer, const float *colors, const float *material, const float *visibility,
+                                       const float *params, const float *grad_out, float *grad_gbuffer, float *grad_colors,
+                                       float *grad_material, float *grad_visibility, float *grad_params, void *scratch,
+                                       size_t scratch_bytes, long long scenes, long long pixels, int Cg, int color_stride,
+                                       int material_stride, int visibility_stride, int off_colors, int off_material,
+                                       int off_normals, int off_positions, int off_mask, int param_scenes, int lights,
+                                       unsigned light_kinds, float min_roughness, float dielectric_f0, float clamp_lo,
+                                       float clamp_hi, unsigned flags, void *stream);
 
 /*
  * Split-sum image-based lighting of a G-buffer, fused (the specification is DESIGN.md §7b and
