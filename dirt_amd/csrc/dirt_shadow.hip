@@ -334,6 +334,8 @@ static int shadow_check(const char* who, const ShadowArgs& a, dirt::ShadowParams
     if (a.matrix_scenes != 1 && a.matrix_scenes != a.scenes) STAGE_FAIL("%s: matrix_scenes=%d is neither 1 nor scenes=%lld", who, a.matrix_scenes, a.scenes);
     if (a.kernel != 1 && a.kernel != 3 && a.kernel != 5) STAGE_FAIL("%s: kernel=%d is none of 1, 3, 5", who, a.kernel);
     if (!(a.softness > 0.f) || !(a.softness <= 3.4e38f)) STAGE_FAIL("%s: softness=%g is not a finite number > 0", who, a.softness);
+    // inv_softness below: past FLT_MAX it would be Inf, and 0 * Inf where (Z - d) + bias is 0 a NaN in the value and every gradient
+    if (1.0 / (double)a.softness > 3.4028234663852886e38) STAGE_FAIL("%s: softness=%g has no finite float32 reciprocal", who, a.softness);
     if (!(a.bias >= -3.4e38f && a.bias <= 3.4e38f)) STAGE_FAIL("%s: bias=%g is not finite", who, a.bias);
     if (!(a.normal_offset >= -3.4e38f && a.normal_offset <= 3.4e38f)) STAGE_FAIL("%s: normal_offset=%g is not finite", who, a.normal_offset);
     if (a.normal_offset != 0.f && a.off_normals == -1) STAGE_FAIL("%s: normal_offset=%g needs the normals' channels", who, a.normal_offset);

@@ -3,6 +3,7 @@
 Same signatures and conventions as the reference: `vertices` [*, V, 3|4] with any leading batch dimensions and a
 topology `faces` [F, 3] shared by the batch.  Where the reference builds a sparse [F, V, ...] tensor and reduces
 it (dirt/lighting.py:64-79) this uses one `index_add_` over the vertex axis -- same sums, linear memory."""
+import ctypes
 import math
 import numbers
 
@@ -462,7 +463,8 @@ def shadow_visibility(points, normals, shadow_maps, light_matrices, *, mask=None
     or None (needed only with normal_offset != 0), shadow_maps [L, Hs, Ws] (clip-space z of the nearest surface, as
     `shading.render_shadow_map` draws it), light_matrices [L, 4, 4] (world -> the light's clip space, right-multiplying row
     vectors as everything in `matrices`), mask [N] or None -> [N, L], 1 = lit, 0 = in shadow.  kernel (1, 3 or 5), bias,
-    softness (> 0) and normal_offset are python numbers and carry no gradient.  Per point and light:
+    softness (> 0, and no smaller than 2.94e-39: its float32 reciprocal must be finite) and normal_offset are python numbers
+    and carry no gradient.  Per point and light:
 
         q = p + normal_offset n / max(|n|, 1e-12)                    (x, y, z, w) = [q, 1] @ M            d = z
         col = (x / w + 1) Ws / 2 - 0.5          row = (1 - y / w) Hs / 2 - 0.5
@@ -502,7 +504,8 @@ def shadow_visibility(points, normals, shadow_maps, light_matrices, *, mask=None
     for l in range(L):
         M = mats[l]
         x, y, d, w = (((q[:, 0] * M[0, j] + q[:, 1] * M[1, j]) + q[:, 2] * M[2, j]) + M[3, j] for j in range(4))
-        front = finite & (w > 0)
+        # (a finite point that x or y overflow on is off every map; kept out of x / w, whose backward would make 0 * Inf of it)
+        front = finite & (w > 0) & torch.isfinite(x) & torch.isfinite(y)
         ws = torch.where(front, w, one)
         col = (x / ws + 1.) * (0.5 * Ws) - 0.5
         row = (1. - y / ws) * (0.5 * Hs) - 0.5
@@ -536,4 +539,8 @@ def _shadow_scalars(kernel, bias, softness, normal_offset):
             raise ValueError('%s must be a finite number, got %r' % (name, x))
     if not softness > 0:
         raise ValueError('softness must be > 0, got %r' % (softness,))
+    # the kernel multiplies by the float32 reciprocal: below 1 / FLT_MAX (2.94e-39) that is Inf, and 0 * Inf a NaN
+    as_float32 = ctypes.c_float(softness).value
+    if as_float32 == 0. or 1. / as_float32 > (2. - 2.**-23) * 2.**127:
+        raise ValueError('softness must have a finite float32 reciprocal, got %r' % (softness,))
     return int(kernel), float(bias), float(softness), float(normal_offset)

@@ -822,7 +822,8 @@ def shadow_visibility(gbuffer, shadow_maps, light_matrices, *, positions, normal
     With a [B, H, W, Cg] G-buffer either may have a leading B ([B, L, Hs, Ws], [B, L, 4, 4]): an operand shared by the scenes
         has no leading B, one with a leading B has one value per scene.
     kernel: the side of the percentage-closer filter, 1, 3 or 5.  bias: added to the map's depth before the comparison (in
-        clip z).  softness > 0: the width in clip z over which the comparison goes from shadow to light.  normal_offset: the
+        clip z).  softness > 0: the width in clip z over which the comparison goes from shadow to light (one whose float32
+        reciprocal is not finite, below 2.94e-39, is refused: the kernel multiplies by it).  normal_offset: the
         distance in world units the point is moved along its unit normal before it is projected.  Python numbers, no gradient.
 
     Returns [..., L]:  1 - m (1 - v)  with v in [0, 1] the filtered comparison: 1 = lit, 0 = in shadow; an uncovered pixel, one

@@ -781,7 +781,8 @@ int dirt_normal_map_backward(const float *gbuffer, const float *normal_map, cons
  * Refused before any device work, with a sentence in dirt_last_error(): negative sizes, more than 65535 scenes or 2^40
  *   pixels, a channel count outside 1..DIRT_SHADE_MAX_CHANNELS, a light count outside 1..DIRT_SHADOW_MAX_LIGHTS, a map
  *   that is empty or has more than 2^31 - 1 texels, map_scenes or matrix_scenes that is neither 1 nor scenes, a kernel
- *   other than 1, 3, 5, a softness that is not a finite number > 0, a bias or normal_offset that is not finite, a
+ *   other than 1, 3, 5, a softness that is not a finite number > 0 or whose float32 reciprocal is not finite (below
+ *   2.94e-39: the kernels multiply by it), a bias or normal_offset that is not finite, a
  *   normal_offset without normals, attributes that do not fit or overlap, a NULL operand, a pixel grid the backward's
  *   tiles cannot index, a scratch that is missing, too small or misaligned.
  */

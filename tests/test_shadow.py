@@ -18,7 +18,7 @@ from tests import shadow_reference as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # python -m tests.shadow_reference
-F32 = {'out': 5.52e-7, 'd_positions': 5.32e-6, 'd_normals': 1.73e-6, 'd_mask': 9.47e-7, 'd_maps': 8.95e-5, 'd_matrices': 3.64e-7}
+F32 = {'out': 7.56e-7, 'd_positions': 3.90e-5, 'd_normals': 2.93e-6, 'd_mask': 1.20e-6, 'd_maps': 8.95e-5, 'd_matrices': 3.64e-7}
 KERNEL = 4     # the kernel's allowance over the float32 composition
 
 
@@ -59,9 +59,10 @@ def random_case(seed, shape, cg, layout, lights, hs, ws, kernel, normal_offset=0
     return Case(shape, g, maps, mats, layout, kw, seed + 1)
 
 
-def grid_case(seed, shape, hs, ws, rows, cols, kernel, cg=5, layout=(1, None, 0)):
+def grid_case(seed, shape, hs, ws, rows, cols, kernel, cg=5, layout=(1, None, 0), mats=None):
     """Pixels placed at given fractional (row, col) indices of one map under the identity matrix (clip = [p, 1]): every pixel in
-    the penumbra (|Z|, |d| small against the softness 1), so that every texel of every window carries a gradient."""
+    the penumbra (|Z|, |d| small against the softness 1), so that every texel of every window carries a gradient.  `mats`
+    [L, 4, 4]: a map per matrix, each a scale of x and y about the map's centre (the same pixels, a smaller or larger box)."""
     rng = np.random.default_rng(seed)
     n = int(np.prod(shape))
     op, _, om = layout
@@ -72,8 +73,8 @@ def grid_case(seed, shape, hs, ws, rows, cols, kernel, cg=5, layout=(1, None, 0)
     g[:, op + 2] = rng.uniform(-0.05, 0.05, n)
     if om is not None:
         g[:, om] = rng.uniform(0.5, 1., n)
-    maps = rng.uniform(-0.2, 0.2, (1, hs, ws)).astype(np.float32)
-    mats = np.eye(4, dtype=np.float32)[None]
+    mats = np.eye(4, dtype=np.float32)[None] if mats is None else np.asarray(mats, dtype=np.float32)
+    maps = rng.uniform(-0.2, 0.2, (len(mats), hs, ws)).astype(np.float32)
     kw = dict(kernel=kernel, bias=0.01, softness=1., normal_offset=0.)
     case = Case(shape, g, maps, mats, layout, kw, seed + 1)
     assert case.ref['kink'].min() >= R.OFF_KINKS
@@ -140,7 +141,8 @@ SINGLE_CASES = ['flat', 'image'] + LIGHT_CASES + LAYOUT_CASES + ['map-1x1', 'map
 
 
 def tolerance_cases():
-    return [case(name).args for name in SINGLE_CASES]
+    from tests import test_shadow_edges      # (it imports this module: here, not at the top)
+    return [case(name).args for name in SINGLE_CASES] + test_shadow_edges.tolerance_cases()
 
 
 def _check(got, c, what=None):
@@ -320,6 +322,8 @@ def test_every_value_error_of_the_wrapper():
     refused('kernel must be 1, 3 or 5, got 2', g, Z, M, kernel=2, **ok)
     refused('kernel must be 1, 3 or 5, got True', g, Z, M, kernel=True, **ok)
     refused('softness must be > 0, got 0.0', g, Z, M, **dict(ok, softness=0.))
+    refused('softness must have a finite float32 reciprocal, got 1e-40', g, Z, M, **dict(ok, softness=1e-40))
+    refused('softness must have a finite float32 reciprocal, got 1e-50', g, Z, M, **dict(ok, softness=1e-50))
     refused("softness must be a finite number, got 'soft'", g, Z, M, **dict(ok, softness='soft'))
     refused('bias must be a finite number, got nan', g, Z, M, bias=float('nan'), **ok)
     refused('normal_offset must be a finite number, got inf', g, Z, M, normal_offset=float('inf'), **ok)
@@ -387,6 +391,7 @@ REFUSALS = [
     (dict(softness=0.), 'dirt_shadow_forward: softness=0 is not a finite number > 0'),
     (dict(softness=float('nan')), 'dirt_shadow_forward: softness=nan is not a finite number > 0'),
     (dict(softness=float('inf')), 'dirt_shadow_forward: softness=inf is not a finite number > 0'),
+    (dict(softness=1e-40), 'dirt_shadow_forward: softness=9.99995e-41 has no finite float32 reciprocal'),
     (dict(bias=float('inf')), 'dirt_shadow_forward: bias=inf is not finite'),
     (dict(normal_offset=float('nan')), 'dirt_shadow_forward: normal_offset=nan is not finite'),
     (dict(normal_offset=0.5, off_normals=-1), 'dirt_shadow_forward: normal_offset=0.5 needs the normals\' channels'),
@@ -414,6 +419,7 @@ def test_c_refusals_come_before_any_device_work(lib):
                          (dict(rows=1 << 30, cols=1 << 30), 'dirt_shadow_backward: bad pixel grid (rows=1073741824 cols=1073741824)'),
                          (dict(kernel=4), 'dirt_shadow_backward: kernel=4 is none of 1, 3, 5'),
                          (dict(lights=9), 'dirt_shadow_backward: 9 lights, 1..4'),
+                         (dict(softness=1e-40), 'dirt_shadow_backward: softness=9.99995e-41 has no finite float32 reciprocal'),
                          (dict(grad_gbuffer=one), 'dirt_shadow_backward: gbuffer / maps / matrices / grad_out is NULL'),
                          (dict(grad_gbuffer=one, rows=1, cols=1 << 40), 'dirt_shadow_backward: pixel grid too large (rows=1 cols=1099511627776)'),
                          (dict(gbuffer=one, maps=one, matrices=one, grad_out=one, grad_matrices=one),
