@@ -4,7 +4,8 @@ The reference's samples/ and tests/ say `import dirt`, `dirt.rasterise(...)`, `i
 `dirt.matrices`, `dirt.lighting`, `dirt.projection` (and, beyond the reference, `dirt.texture`, `dirt.shading`, `dirt.geometry`, `dirt.skinning`, `dirt.kinematics`, `dirt.blendshapes`); this package re-exports `dirt_amd` under those names so
 such scripts run unchanged apart from TensorFlow -> torch tensors.  `dirt.shading` carries the fused G-buffer shaders
 (`shade_gbuffer`, `shade_gbuffer_sh`, `shade_gbuffer_pbr` with `dirt.lighting.cook_torrance` as its per-vertex form, and
-`shade_gbuffer_ibl` with `dirt.lighting.image_based_lighting` and the table of `dirt.lighting.environment_brdf`);
+`shade_gbuffer_ibl` with `dirt.lighting.image_based_lighting` and the table of `dirt.lighting.environment_brdf`) and
+`environment_background`, the environment seen behind the mesh (`dirt.lighting.environment_background` is its torch form);
 `dirt.texture` the look-ups, by (u, v) (`sample_texture_uv`) and by direction into a cube map (`sample_texture_cube`),
 and the GGX-prefiltered environment pyramid (`prefilter_cube`, looked up by `sample_cube_pyramid`).
 Tangent-space normal mapping is `dirt.geometry.vertex_tangents` (per-vertex frames from the uvs) and

@@ -43,6 +43,8 @@ SHADE_IBL_MAX_TABLE = 128   # the largest environment-BRDF table of dirt_shade_i
 NORMAL_MAP_ENCODED = 1
 SHADOW_MAX_LIGHTS = 4   # = SHADE_PBR_MAX_LIGHTS: the lights of dirt_shadow_forward, one map and one matrix each
 SHADOW_KERNELS = (1, 3, 5)   # the sides of its percentage-closer filter
+BACKGROUND_FILTERS = {'nearest': 0, 'bilinear': 1, 'trilinear': 2}   # the filter of dirt_background_forward
+BACKGROUND_FOOTPRINT = 1   # its flag: the level of detail from the pixel's footprint
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
 GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
@@ -79,7 +81,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_blend_scratch_bytes', 'dirt_blend_forward', 'dirt_blend_backward',
            'dirt_tangent_scratch_bytes', 'dirt_tangent_forward', 'dirt_tangent_backward',
            'dirt_normal_map_forward', 'dirt_normal_map_backward',
-           'dirt_shadow_scratch_bytes', 'dirt_shadow_forward', 'dirt_shadow_backward')
+           'dirt_shadow_scratch_bytes', 'dirt_shadow_forward', 'dirt_shadow_backward',
+           'dirt_background_scratch_bytes', 'dirt_background_forward', 'dirt_background_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -262,6 +265,14 @@ def load():
         lib.dirt_shadow_forward.restype = i
         lib.dirt_shadow_backward.argtypes = [fp] * 7 + [vp, sz, ll, ll, ll] + [i] * 10 + [f32, f32, f32, vp]
         lib.dirt_shadow_backward.restype = i
+    if hasattr(lib, 'dirt_background_forward') or not override:   # the environment behind the mesh (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_background_scratch_bytes.argtypes = [ll, ll, ll]
+        lib.dirt_background_scratch_bytes.restype = sz
+        lib.dirt_background_forward.argtypes = [fp] * 5 + [ll, ll, ll] + [i] * 7 + [f32, f32, u, vp]
+        lib.dirt_background_forward.restype = i
+        lib.dirt_background_backward.argtypes = [fp] * 9 + [vp, sz, ll, ll, ll] + [i] * 7 + [f32, f32, u, vp]
+        lib.dirt_background_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -26,8 +26,8 @@
 // background, camera.
 //
 // Kernels: the tiling, the clamp, MaterialPixel, the channel map and the host checks of dirt_shade_common.h; the look-ups of
-// dirt_texture_cube.h.  Forward one pixel per lane: 16 texels of the pyramid, 4 of the irradiance cube, 4 of the table, read
-// through the cache (the table is 8 KB at S = 32 and every lane of a wave reads neighbouring texels of it).  Backward IBL_ITER
+// dirt_texture_cube.h (cube_sample: a level's three channels with their derivatives).  Forward one pixel per lane: 16 texels
+// of the pyramid, 4 of the irradiance cube, 4 of the table, read through the cache (the table is 8 KB at S = 32 and every lane of a wave reads neighbouring texels of it).  Backward IBL_ITER
 // passes of 256 pixels per workgroup inside one scene: the forward again with the derivative of every look-up by its own index,
 // d gbuffer through an LDS tile, the tensors' gradients by one dense store per lane, the nine parameter sums wave_sum ->
 // fold_waves_to_row -> one row per workgroup -> shade_launch_reduce.  No atomics.  What the two cubes' gradients need it leaves
@@ -67,44 +67,15 @@ struct ShadeIblParams {
     float lo, hi, min_roughness, f0;
 };
 
-// a bilinear look-up of three channels and, per channel, its derivative by sc / a and tc / a (0 where the index is clamped)
-struct IblSample { float v[3], ds[3], dt[3]; };
-
 // everything the forward computes at a pixel; the derivatives only where GRAD
 struct IblEval {
     float R[3], lod, f;
     bool inside;                     // d spec / d lod is the levels' difference here
     CubeLook qr, qn;
-    IblSample s0, s1, e;             // the two levels of the pyramid at R, the irradiance at n
+    CubeSample s0, s1, e;             // the two levels of the pyramid at R, the irradiance at n
     float spec[3], A, B, A_nv, A_rho, B_nv, B_rho;
     float S[3], wd[3], T[3];         // S_j; (1 - S_j)(1 - mu) c_j; the light before the intensity
 };
-
-// one level [n, n, 3] of a face at the look-up q
-template <bool GRAD>
-__device__ __forceinline__ void ibl_sample(const float* __restrict__ lv, int n, const CubeLook& q, IblSample& s)
-{
-    float drow, dcol;
-    const Taps k = cube_taps(q, n, false, drow, dcol);
-    const Four<size_t> o = tap_offsets(k, n, 3, 0);
-    float tl[3], tr[3], bl[3], br[3];
-    load3(lv + o.tl, tl); load3(lv + o.tr, tr); load3(lv + o.bl, bl); load3(lv + o.br, br);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        s.v[j] = bilinear_blend(tl[j], tr[j], bl[j], br[j], k);
-        if constexpr (GRAD) {
-            float e_fr, e_fc;
-            tap_gradients(1.f, {tl[j], tr[j], bl[j], br[j]}, k, e_fr, e_fc);
-            s.ds[j] = e_fc * dcol; s.dt[j] = e_fr * drow;
-        }
-    }
-}
-
-__device__ __forceinline__ void ibl_sample_clear(IblSample& s)
-{
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { s.v[j] = 0.f; s.ds[j] = 0.f; s.dt[j] = 0.f; }
-}
 
 // x S - 0.5 clamped to the table, and d index / d x
 __device__ __forceinline__ float ibl_table_index(float x, int S, float& d)
@@ -141,21 +112,21 @@ __device__ __forceinline__ void ibl_eval(const ShadeIblParams& P, const Material
     mip_split(e.lod, P.L, l, e.f);
     e.inside = e.lod > 0.f && e.lod < (float)(P.L - 1);
     e.qr = cube_look(e.R[0], e.R[1], e.R[2]);
-    ibl_sample_clear(e.s0); ibl_sample_clear(e.s1);
+    cube_sample_clear(e.s0); cube_sample_clear(e.s1);
     if (e.qr.valid) {
         const float* __restrict__ face = P.pyr + (size_t)e.qr.face() * P.face_floats;
         const int n0 = mip_dim(P.N, l);
-        ibl_sample<GRAD>(face + cube_level_offset(P.N, n0, 3), n0, e.qr, e.s0);
+        cube_sample<GRAD>(face + cube_level_offset(P.N, n0, 3), n0, e.qr, e.s0);
         if (e.f != 0.f || (GRAD && e.inside)) {   // the second level: blended in where it carries weight, read for d lod inside
             const int n1 = mip_dim(P.N, l + 1);
-            ibl_sample<GRAD>(face + cube_level_offset(P.N, n1, 3), n1, e.qr, e.s1);
+            cube_sample<GRAD>(face + cube_level_offset(P.N, n1, 3), n1, e.qr, e.s1);
         }
     }
     const float w0 = 1.f - e.f;
     // the irradiance at the raw normal
     e.qn = cube_look(px.n[0], px.n[1], px.n[2]);
-    ibl_sample_clear(e.e);
-    if (e.qn.valid) ibl_sample<GRAD>(P.irr + (size_t)e.qn.face() * ((size_t)P.M * P.M * 3), P.M, e.qn, e.e);
+    cube_sample_clear(e.e);
+    if (e.qn.valid) cube_sample<GRAD>(P.irr + (size_t)e.qn.face() * ((size_t)P.M * P.M * 3), P.M, e.qn, e.e);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         e.spec[j] = e.f != 0.f ? w0 * e.s0.v[j] + e.f * e.s1.v[j] : e.s0.v[j];

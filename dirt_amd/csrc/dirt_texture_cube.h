@@ -1,7 +1,8 @@
 // dirt_texture_cube.h -- the per-look-up arithmetic of a cube map (specification: the head of dirt_texture_cube.hip, spec 2-6), for
-// the two units that look a cube up by a direction: dirt_texture_cube.hip (the look-up itself and its gradient) and
-// dirt_shade_ibl.hip (image-based lighting, which gathers from two cubes per pixel).  One copy of the face rule, the index, the
-// taps and the direction gradient; and the launch of the backward kernels, which dirt_shade_ibl.hip uses for the scatter alone.
+// the units that look a cube up by a direction: dirt_texture_cube.hip (the look-up itself and its gradient), dirt_shade_ibl.hip
+// (image-based lighting, which gathers from two cubes per pixel) and dirt_background.hip (the environment behind the mesh).  One
+// copy of the face rule, the index, the taps, the three-channel sample and the direction gradient; and the launch of the backward
+// kernels, which the last two use for the scatter alone.
 #pragma once
 #include "dirt_texture_common.h"
 
@@ -90,6 +91,36 @@ __device__ __forceinline__ void cube_direction_gradient(const CubeLook& q, float
     if (q.major == 0) { g[0] = g_m; g[1] = -g_tc; g[2] = q.pos ? -g_sc : g_sc; }
     else if (q.major == 1) { g[0] = g_sc; g[1] = g_m; g[2] = q.pos ? g_tc : -g_tc; }
     else { g[0] = q.pos ? g_sc : -g_sc; g[1] = -g_tc; g[2] = g_m; }
+}
+
+// a bilinear look-up of three channels and, per channel, its derivative by sc / a and tc / a (0 where the index is clamped):
+// what the shaders that look an environment up per pixel gather with (dirt_shade_ibl.hip, dirt_background.hip)
+struct CubeSample { float v[3], ds[3], dt[3]; };
+
+// one level [n, n, 3] of a face at the look-up q
+template <bool GRAD>
+__device__ __forceinline__ void cube_sample(const float* __restrict__ lv, int n, const CubeLook& q, CubeSample& s)
+{
+    float drow, dcol;
+    const Taps k = cube_taps(q, n, false, drow, dcol);
+    const Four<size_t> o = tap_offsets(k, n, 3, 0);
+    float tl[3], tr[3], bl[3], br[3];
+    load3(lv + o.tl, tl); load3(lv + o.tr, tr); load3(lv + o.bl, bl); load3(lv + o.br, br);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        s.v[j] = bilinear_blend(tl[j], tr[j], bl[j], br[j], k);
+        if constexpr (GRAD) {
+            float e_fr, e_fc;
+            tap_gradients(1.f, {tl[j], tr[j], bl[j], br[j]}, k, e_fr, e_fc);
+            s.ds[j] = e_fc * dcol; s.dt[j] = e_fr * drow;
+        }
+    }
+}
+
+__device__ __forceinline__ void cube_sample_clear(CubeSample& s)
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { s.v[j] = 0.f; s.ds[j] = 0.f; s.dt[j] = 0.f; }
 }
 
 // dirt_texture_cube.hip: clears p.grad_pyr, then launches the backward kernel (the trilinear one where p.lod is there) on the

@@ -544,3 +544,179 @@ def _shadow_scalars(kernel, bias, softness, normal_offset):
     if as_float32 == 0. or 1. / as_float32 > (2. - 2.**-23) * 2.**127:
         raise ValueError('softness must have a finite float32 reciprocal, got %r' % (softness,))
     return int(kernel), float(bias), float(softness), float(normal_offset)
+
+
+# ---- the environment behind the mesh.  Not in the reference: the pixels a mesh does not cover show the environment cube, looked
+# up along the ray through the pixel's centre, at a level of detail that follows from the camera alone.  This is the specification
+# `shading.environment_background` implements per pixel.
+
+BACKGROUND_FILTERS = ('nearest', 'bilinear', 'trilinear')
+
+
+def _image_size(size):
+    """An image's size as the shadow maps and the background take it: a positive int or (height, width) -> (height, width)."""
+    try:
+        hs, ws = (size, size) if isinstance(size, numbers.Integral) else size
+        ok = all(isinstance(s, numbers.Integral) and not isinstance(s, bool) and s >= 1 for s in (hs, ws))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('size must be a positive int or (height, width), got %r' % (size,))
+    return int(hs), int(ws)
+
+
+def _background_scalars(size, filter, lod, lod_bias, max_level):
+    """The python arguments of `environment_background`, refused outside their ranges -> (height, width, lod or None, lod_bias)."""
+    height, width = _image_size(size)
+    if filter not in BACKGROUND_FILTERS:
+        raise ValueError("environment_background: filter must be 'nearest', 'bilinear' or 'trilinear', got %r" % (filter,))
+    if filter != 'trilinear' and (lod is not None or lod_bias != 0.0 or max_level is not None):
+        raise ValueError("lod, lod_bias and max_level apply to filter='trilinear' only (got filter=%r)" % (filter,))
+    if max_level is not None and (isinstance(max_level, bool) or not isinstance(max_level, int) or max_level < 0):
+        raise ValueError('max_level must be a non-negative int or None, got %r' % (max_level,))
+    for name, x in (('lod', lod), ('lod_bias', lod_bias)):
+        if x is not None and (isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x)):
+            raise ValueError('%s must be a finite number%s, got %r' % (name, ' or None (the footprint of the pixel)' if name == 'lod' else '', x))
+    return height, width, None if lod is None else float(lod), float(lod_bias)
+
+
+def _box_levels(cube, max_level):
+    """The box-filtered levels of a cube [6, N, N, C], as `texture.cube_pyramid` makes them: 2 x 2 means while the size is even."""
+    levels = [cube]
+    while levels[-1].shape[1] % 2 == 0 and (max_level is None or len(levels) <= max_level):
+        t = levels[-1]
+        levels.append(((t[:, 0::2, 0::2] + t[:, 0::2, 1::2]) + (t[:, 1::2, 0::2] + t[:, 1::2, 1::2])) * 0.25)
+    return levels
+
+
+def background_rays(clip_to_world, height, width):
+    """The rays through the pixel centres of a height x width image, one operation per step as `environment_background` states
+    them: clip_to_world [..., 4, 4] -> dict of nx, ny [height, width], h0, hm (lists of four [..., height, width]: the
+    homogeneous world points on the planes z = 0 and z = -1 of clip space)."""
+    M = clip_to_world
+    two = torch.full((), 2., dtype=M.dtype, device=M.device)
+    nx = (two * (torch.arange(width, dtype=M.dtype, device=M.device) + 0.5)) / float(width) - 1.
+    ny = 1. - (two * (torch.arange(height, dtype=M.dtype, device=M.device) + 0.5)) / float(height)
+    nx, ny = nx[None, :].expand(height, width), ny[:, None].expand(height, width)
+    Mb = M[..., None, None, :, :]
+    a = [nx * Mb[..., 0, j] + ny * Mb[..., 1, j] for j in range(4)]
+    return {'nx': nx, 'ny': ny, 'h0': [a[j] + Mb[..., 3, j] for j in range(4)], 'hm': [(a[j] - Mb[..., 2, j]) + Mb[..., 3, j] for j in range(4)]}
+
+
+def _background_footprint(M, rays, start, end, d, size, height, width):
+    """log2 of a pixel's footprint in texels of level 0, from the camera alone (no gradient): the derivative of the ray by the
+    pixel's column and row in closed form, through the face coordinates of d's own face."""
+    x, y, z = d.unbind(-1)
+    ax, ay, az = x.abs(), y.abs(), z.abs()
+    is_x = (ax >= ay) & (ax >= az)
+    is_y = ~is_x & (ay >= az)
+    major = torch.where(is_x, x, torch.where(is_y, y, z))
+    pos = major > 0
+    a = torch.where(is_x, ax, torch.where(is_y, ay, az))
+    a = torch.where(a > 0, a, torch.ones_like(a))
+
+    def picks(v):   # (sc, tc, the major component times its sign) of the vector v on d's face
+        vx, vy, vz = v
+        sc = torch.where(is_x, torch.where(pos, -vz, vz), torch.where(is_y, vx, torch.where(pos, vx, -vx)))
+        tc = torch.where(is_y, torch.where(pos, vz, -vz), -vy)
+        mc = torch.where(is_x, vx, torch.where(is_y, vy, vz))
+        return sc, tc, torch.where(pos, mc, -mc)
+
+    sc, tc, _ = picks((x, y, z))
+    s, t = sc / a, tc / a
+    Mb = M[..., None, None, :, :]
+    h0w, hmw = rays['h0'][3], rays['hm'][3]
+    n2 = []
+    for axis, n in ((0, width), (1, height)):
+        scale = torch.full((), 2., dtype=M.dtype, device=M.device) / float(n)
+        row = [Mb[..., axis, j] for j in range(4)]
+        dd = [scale * ((row[j] - end[..., j] * row[3]) / h0w - (row[j] - start[..., j] * row[3]) / hmw) for j in range(3)]
+        dsc, dtc, dma = picks(dd)
+        ds, dt = (dsc - s * dma) / a, (dtc - t * dma) / a
+        n2.append(ds * ds + dt * dt)
+    big = torch.where(n2[0] > n2[1], n2[0], n2[1])
+    return torch.log2((0.5 * float(size)) * torch.sqrt(big))
+
+
+def environment_background(environment, clip_to_world, size, *, mask=None, intensity=(1., 1., 1.), filter='bilinear', lod=None, lod_bias=0.0,
+                           max_level=None):
+    """The environment as a camera sees it where no mesh covers the pixel.  environment: a cube [6, N, N, 3] (faces +X, -X, +Y,
+    -Y, +Z, -Z as `texture.sample_cube` takes them) or a 3-channel `texture.CubePyramid` (filter='trilinear' only); clip_to_world
+    [4, 4] or [B, 4, 4], what `projection.unproject_pixels_to_rays` takes (row vectors, typically inverse(view @ projection));
+    size: an int or (height, width); mask None or [H, W] / [B, H, W], 1 where the mesh covers the pixel; intensity 3 numbers,
+    [3] or [B, 3] -> [H, W, 3] or [B, H, W, 3].  Per pixel (r, c), one operation per step:
+
+        nx = (2 (c + 0.5)) / W - 1              ny = 1 - (2 (r + 0.5)) / H         (projection._pixel_to_ndc at the pixel centre)
+        a_j = nx M[0][j] + ny M[1][j]           h0_j = a_j + M[3][j]               hm_j = (a_j - M[2][j]) + M[3][j]
+        end = h0.xyz / h0.w                     start = hm.xyz / hm.w              d = end - start
+            (the second result of `unproject_pixels_to_rays` at the pixel centres, not normalised)
+        E = `texture.sample_cube(level, *texture.directions_to_cube_indices(d, n))`: 'nearest', 'bilinear', or 'trilinear':
+            lam = clamp(lambda, 0, L - 1), l = floor(lam), f = lam - l:  E = (1 - f) level_l(d) + f level_{l+1}(d)
+        out_j = ((1 - m) intensity_j) E_j
+
+    lambda is `lod` + `lod_bias`, or with lod=None the pixel's own footprint: with dd_x = (2 / W) d d / d nx and dd_y = (2 / H)
+    d d / d ny in closed form (d end / d nx = (M[0].xyz - end M[0].w) / h0.w, start likewise with hm; ny with M[1]),
+
+        Ds = (sc(dd) - s ma(dd)) / a            Dt = (tc(dd) - t ma(dd)) / a       (d's own face: its picks of dd; s, t, a of d)
+        rho = (N / 2) sqrt(max(Ds_x^2 + Dt_x^2, Ds_y^2 + Dt_y^2))                  lambda = log2 rho + lod_bias
+
+    held constant: no gradient flows through it.  A pixel whose d is not valid (h.w = 0, anything non-finite, all zero) or whose
+    1 - m is exactly 0 gives 0 and takes part in no gradient but the mask's.  With 'trilinear' a cube's levels are its 2 x 2 box
+    means (`texture.cube_pyramid`, capped by max_level).  Differentiable in the environment, the matrix, the intensity and the
+    mask; works in float64 and on any device."""
+    from .texture import CubePyramid, directions_to_cube_indices, sample_cube
+    height, width, lod, lod_bias = _background_scalars(size, filter, lod, lod_bias, max_level)
+    if isinstance(environment, CubePyramid):
+        if filter != 'trilinear':
+            raise ValueError("environment_background: a CubePyramid is looked up with filter='trilinear', got %r" % (filter,))
+        levels = [environment.level(k) for k in range(environment.levels)]
+    else:
+        levels = _box_levels(environment, max_level) if filter == 'trilinear' else [environment]
+    like = levels[0]
+    if like.dim() != 4 or like.shape[0] != 6 or like.shape[1] != like.shape[2] or like.shape[3] != 3:
+        raise ValueError('environment must be a cube [6, size, size, 3], got %s' % (tuple(like.shape),))
+    M, inten = _as(clip_to_world, like), _as(intensity, like)
+    m = None if mask is None else _as(mask, like)
+    if M.dim() not in (2, 3) or tuple(M.shape[-2:]) != (4, 4):
+        raise ValueError('clip_to_world must have shape [4, 4] or [B, 4, 4], got %s' % (tuple(M.shape),))
+    if inten.dim() not in (1, 2) or inten.shape[-1] != 3:
+        raise ValueError('intensity must have shape [3] or [B, 3], got %s' % (tuple(inten.shape),))
+    if m is not None and (m.dim() not in (2, 3) or tuple(m.shape[-2:]) != (height, width)):
+        raise ValueError('mask must have shape [%d, %d] or [B, %d, %d], got %s' % (height, width, height, width, tuple(m.shape)))
+    n = int(like.shape[1])
+    w = None if m is None else 1. - m
+    rays = background_rays(M, height, width)
+    with torch.no_grad():
+        raw = torch.stack([rays['h0'][j] / rays['h0'][3] - rays['hm'][j] / rays['hm'][3] for j in range(3)], -1)
+        valid = torch.isfinite(raw).all(-1) & (raw.abs().amax(-1) > 0)
+        if w is not None:
+            valid = valid & (w != 0)
+    # (selects: a pixel that is not valid keeps 0 / 1 in place of its ray, so that no Inf or NaN meets a zero in a backward)
+    zero, one = torch.zeros_like(rays['h0'][3]), torch.ones_like(rays['h0'][3])
+    valid = valid.expand(torch.broadcast_shapes(valid.shape, zero.shape))
+    h0w, hmw = torch.where(valid, rays['h0'][3], one), torch.where(valid, rays['hm'][3], one)
+    end = torch.stack([torch.where(valid, rays['h0'][j], zero) / h0w for j in range(3)], -1)
+    start = torch.stack([torch.where(valid, rays['hm'][j], zero) / hmw for j in range(3)], -1)
+    d = end - start
+    mode = 'nearest' if filter == 'nearest' else 'bilinear'
+    if filter != 'trilinear':
+        E = sample_cube(like, *directions_to_cube_indices(d, n), mode)
+    else:
+        with torch.no_grad():
+            if lod is None:
+                safe = dict(rays, h0=rays['h0'][:3] + [h0w], hm=rays['hm'][:3] + [hmw])
+                lam = _background_footprint(M, safe, start, end, d, n, height, width) + lod_bias
+            else:
+                lam = (torch.full((), lod, dtype=like.dtype, device=like.device) + lod_bias).expand(d.shape[:-1])
+            top = float(len(levels) - 1)
+            lam = torch.where(lam > 0, torch.where(lam < top, lam, torch.full_like(lam, top)), torch.zeros_like(lam))   # (a NaN: level 0)
+            low = torch.floor(lam)
+            f = (lam - low)[..., None]
+            l0 = low.to(torch.int64)
+            l1 = (l0 + 1).clamp(max=len(levels) - 1)
+        looked = torch.stack([sample_cube(lv, *directions_to_cube_indices(d, int(lv.shape[1]))) for lv in levels])   # [L, ..., H, W, 3]
+        pick = lambda l: torch.gather(looked, 0, l[None, ..., None].expand((1,) + tuple(looked.shape[1:])))[0]   # noqa: E731
+        E = torch.where(f != 0, (1. - f) * pick(l0) + f * pick(l1), pick(l0))
+    scale = inten[..., None, None, :] if w is None else w[..., None] * inten[..., None, None, :]
+    out = scale * E
+    return torch.where(valid[..., None], out, torch.zeros_like(out))

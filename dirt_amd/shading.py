@@ -633,7 +633,9 @@ def shade_gbuffer_ibl(gbuffer, specular, irradiance, brdf, *, colors, material, 
     bits on every run, everything else is.
 
     Direct lights are added by the caller: `shade_gbuffer_pbr(..., clamp=None) + shade_gbuffer_ibl(..., clamp=None)`, then
-    one clamp."""
+    one clamp.  The environment behind the mesh, in place of the flat `background`, likewise:
+    `(shade_gbuffer_ibl(..., background=(0., 0., 0.), clamp=None) + environment_background(specular, clip_to_world, (H, W),
+    mask=gbuffer[..., mask], filter='trilinear')).clamp(0., 1.)` -- `specular`'s level 0 is the environment itself."""
     g, scenes, pixels, cg = _gbuffer_sizes(gbuffer, 'shade_gbuffer_ibl')
     offsets, sizes, scalars, lo, hi, flags, const, tensors = _check_ibl_arguments(gbuffer, specular, irradiance, brdf, colors, material, normals,
                                                                                    positions, mask, intensity, camera_position, background, clamp,
@@ -880,13 +882,8 @@ def _check_shadow_arguments(gbuffer, shadow_maps, light_matrices, positions, nor
 def _shadow_map_operands(vertices, light_matrix, size, far):
     """What `render_shadow_map` hands to the rasteriser, for one scene or a batch: -> (background [..., Hs, Ws, 1] = far, clip
     vertices [..., V, 4] = [v, 1] @ M, vertex colours [..., V, 1] = clip z)."""
-    try:
-        hs, ws = (size, size) if isinstance(size, numbers.Integral) else size
-        ok = all(isinstance(s, numbers.Integral) and not isinstance(s, bool) and s >= 1 for s in (hs, ws))
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError('size must be a positive int or (height, width), got %r' % (size,))
+    from .lighting import _image_size
+    hs, ws = _image_size(size)
     if isinstance(far, bool) or not isinstance(far, numbers.Real) or not math.isfinite(far):
         raise ValueError('far must be a finite number, the clip z of the light\'s far plane, got %r' % (far,))
     v = vertices.to(torch.float32)
@@ -928,3 +925,146 @@ def render_shadow_map_batch(vertices, faces, light_matrices, size, far):
     from .rasterise_ops import rasterise_batch
     background, clip, depth = _shadow_map_operands(vertices, light_matrices, size, far)
     return rasterise_batch(background, clip, depth, faces)[..., 0]
+
+
+# ---- the environment behind the mesh (dirt_background.hip)
+
+class _EnvironmentBackground(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, environment, matrices, intensity, mask, meta):
+        """environment: a cube [6, N, N, 3] or (`packed`) a pyramid [6, floats]; matrices [1 or B, 4, 4], intensity [1 or B, 3]:
+        float32; mask: None or [H, W] / [B, H, W], read in place where its values lie a constant stride apart"""
+        from .texture import _call_entry, _mip_geometry, _scalars_in_place
+        lib = _lib.load()
+        scenes, batched, rows, cols, n, levels, packed, code, flags, lod, lod_bias, max_level = meta
+        dev = environment.device
+        pyr, matrices, intensity = environment.contiguous(), matrices.contiguous(), intensity.contiguous()
+        if not packed and code == _lib.BACKGROUND_FILTERS['trilinear']:   # the box pyramid of the cube, built per call
+            levels, floats, _ = _mip_geometry(n, n, 3, max_level)
+            pyr = torch.empty((6, floats), dtype=torch.float32, device=dev)
+            _call_entry('mip_build', 6, dev, (environment.data_ptr(), pyr.data_ptr()), n, n, 3, levels)
+        msrc, mstride = _scalars_in_place(mask) if mask is not None else (None, 0)
+        out = torch.empty(((scenes,) if batched else ()) + (rows, cols, 3), dtype=torch.float32, device=dev)
+        sizes = (scenes, rows, cols, n, levels, int(matrices.shape[0]), int(intensity.shape[0]), 1 if mask is None or mask.dim() == 2 else scenes,
+                 mstride, code, lod, lod_bias, flags)
+        if scenes * rows * cols:
+            _stage.call(lib.dirt_background_forward, dev, pyr.data_ptr(), matrices.data_ptr(), intensity.data_ptr(), _ptr(msrc), out.data_ptr(), *sizes)
+        ctx.save_for_backward(pyr, matrices, intensity, msrc)
+        ctx.meta, ctx.sizes, ctx.mask_shape = meta, sizes, None if mask is None else tuple(mask.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from .texture import _call_entry
+        lib = _lib.load()
+        pyr, matrices, intensity, msrc = ctx.saved_tensors
+        scenes, batched, rows, cols, n, levels, packed, code, flags, lod, lod_bias, max_level = ctx.meta
+        dev = pyr.device
+        empty = not scenes * rows * cols
+        want_env, want_m, want_i, want_mask = ctx.needs_input_grad[:4]
+        grad_pyr, grad_m, grad_i = _stage.grad_outputs((pyr, matrices, intensity), (want_env, want_m, want_i), empty)   # the pyramid's: cleared by the call
+        grad_mask, = _stage.dense_grads(grad_out.reshape(scenes, rows, cols, 3), (1,), (want_mask and msrc is not None,), empty)   # [scenes, H, W, 1]
+        if not empty:
+            grad_out = grad_out.to(torch.float32).contiguous()
+            nbytes = lib.dirt_background_scratch_bytes(scenes, rows, cols) if want_env or want_m or want_i else 0
+            _stage.call(lib.dirt_background_backward, dev, pyr.data_ptr(), matrices.data_ptr(), intensity.data_ptr(), _ptr(msrc), grad_out.data_ptr(),
+                        _ptr(grad_pyr), _ptr(grad_m), _ptr(grad_i), _ptr(grad_mask), _ptr(_stage.scratch(dev, nbytes)), nbytes, *ctx.sizes)
+        grad_env = grad_pyr
+        if grad_pyr is not None and not packed:   # the operand was a cube: level 0 itself, or the pyramid's collapse
+            if grad_pyr.numel() == 6 * n * n * 3:
+                grad_env = grad_pyr.view(6, n, n, 3)
+            else:
+                grad_env = torch.empty((6, n, n, 3), dtype=torch.float32, device=dev)
+                _call_entry('mip_collapse', 6, dev, (grad_pyr.data_ptr(), grad_env.data_ptr()), n, n, 3, int(ctx.sizes[4]))
+        if grad_mask is not None:   # a mask shared by the scenes: summed over them, in scene order
+            grad_mask = grad_mask[..., 0].sum(0) if len(ctx.mask_shape) == 2 else grad_mask
+            grad_mask = grad_mask.reshape(ctx.mask_shape)
+        return grad_env, grad_m, grad_i, grad_mask, None
+
+
+def environment_background(environment, clip_to_world, size, *, mask=None, intensity=(1., 1., 1.), filter='bilinear', lod=None, lod_bias=0.0,
+                           max_level=None):
+    """The environment seen behind the mesh, in one kernel, differentiably: what `lighting.environment_background` computes
+    per pixel (its docstring is the specification) -- the cube looked up along the ray through each pixel's centre, with no
+    ray image, no pixel grid and no look-up where the mesh covers the pixel.
+
+    environment: a float32 cube [6, N, N, 3] on the GPU, as `sample_texture_cube` takes it (with filter='trilinear' its box
+        pyramid is built per call), or a 3-channel `CubePyramid` (`cube_pyramid`, or the `prefilter_cube` pyramid that
+        `shade_gbuffer_ibl` holds: its level 0 is the environment itself, so one pyramid serves both calls) with
+        filter='trilinear'; the gradient then goes to `environment.packed`.  One environment serves every scene.
+    clip_to_world: [4, 4] or [B, 4, 4], what `projection.unproject_pixels_to_rays` takes (row vectors, typically
+        inverse(view @ projection)); differentiable.
+    size: an int or (height, width), as `render_shadow_map` takes it.
+    mask: None (every pixel is background) or a float tensor [H, W] / [B, H, W], 1 where the mesh covers the pixel; a slice
+        `gbuffer[..., 0]` of a contiguous G-buffer is read in place.  Differentiable: a dense gradient of the mask's shape.
+    intensity: the environment's scale per channel, 3 numbers or a tensor [3] or [B, 3]; differentiable.
+    filter: 'nearest', 'bilinear' or 'trilinear'.  lod: None or a python number, lod_bias, max_level: with 'trilinear' only;
+        lod=None takes the level of detail from the pixel's analytic footprint (held constant: no gradient flows through it).
+    The batch size B comes from clip_to_world, mask or intensity, whichever has a leading B (they must agree); an operand
+    without one is shared by the scenes.
+
+    Returns [H, W, 3] or [B, H, W, 3]:  (1 - m) intensity E(ray), not clamped; a pixel whose ray is not valid (h.w = 0) or
+    whose 1 - m is exactly 0 gives 0.  Behind a lit mesh:
+        (shade_gbuffer_ibl(..., background=(0., 0., 0.), clamp=None) + environment_background(..., mask=g[..., m])).clamp(0., 1.)
+    Gradients are those of torch's autograd for `lighting.environment_background` and go to the environment, clip_to_world,
+    intensity and mask.  The environment's is summed with float atomics: it is not the same bits on every run, everything
+    else is."""
+    from .texture import CubePyramid
+    who = 'environment_background'
+    rows, cols, scenes, batched, n, levels, code, flags, lod, lod_bias, const = _check_background_arguments(
+        environment, clip_to_world, size, mask, intensity, filter, lod, lod_bias, max_level)
+    packed = isinstance(environment, CubePyramid)
+    env = environment.packed if packed else environment
+    _stage.require_gpu(env, 'dirt_amd.shading.%s' % who)
+    matrices = clip_to_world if clip_to_world.dim() == 3 else clip_to_world[None]
+    inten = _const_block(env.device, const) if const is not None else intensity.reshape(-1, 3)
+    meta = (scenes, batched, rows, cols, n, levels, packed, code, flags, lod, lod_bias, max_level)
+    return _EnvironmentBackground.apply(env, matrices, inten, mask, meta)
+
+
+def _check_background_arguments(environment, clip_to_world, size, mask, intensity, filter, lod, lod_bias, max_level):
+    """Everything `environment_background` refuses with a ValueError, on types, shapes and devices alone (no device work): ->
+    (height, width, scenes, whether the output is batched, the environment's size, its levels (1 for a cube: a trilinear
+    call counts them when it builds the pyramid), the filter's code, flags, lod, lod_bias, the intensity as a tuple of python
+    floats or None for a tensor)."""
+    from .lighting import _background_scalars
+    from .texture import CubePyramid, _cube_level
+    who = 'environment_background'
+    rows, cols, lod_value, lod_bias = _background_scalars(size, filter, lod, lod_bias, max_level)
+    if isinstance(environment, CubePyramid):
+        if filter != 'trilinear':
+            raise ValueError("%s: a CubePyramid is looked up with filter='trilinear', got filter=%r" % (who, filter))
+        if max_level is not None:
+            raise ValueError('%s: max_level applies to a cube, whose pyramid the call builds; a CubePyramid has its %d levels' % (who, environment.levels))
+        if environment.channels != 3:
+            raise ValueError('%s: environment has %d channels, an environment has 3' % (who, environment.channels))
+        top, top_size = _cube_level(environment.size, 3, environment.levels - 1)
+        if not isinstance(environment.packed, torch.Tensor) or tuple(environment.packed.shape) != (6, top + top_size * top_size * 3):
+            raise ValueError('%s: environment.packed must be [6, %d], the %d levels of a %d x %d x 3 face, got %s'
+                             % (who, top + top_size * top_size * 3, environment.levels, environment.size, environment.size,
+                                tuple(getattr(environment.packed, 'shape', ()))))
+        env, n, levels = environment.packed, environment.size, environment.levels
+    else:
+        if not isinstance(environment, torch.Tensor) or environment.dim() != 4 or environment.shape[0] != 6 \
+                or environment.shape[1] != environment.shape[2] or 0 in environment.shape:
+            raise ValueError('%s expects environment to be a cube [6, size, size, 3] or a CubePyramid, got %s'
+                             % (who, tuple(getattr(environment, 'shape', ())) if isinstance(environment, torch.Tensor) else type(environment).__name__))
+        if environment.shape[3] != 3:
+            raise ValueError('%s: environment has %d channels, an environment has 3' % (who, environment.shape[3]))
+        env, n, levels = environment, int(environment.shape[1]), 1
+    _stage.check_float32('environment', env)
+    _stage.check_operand('clip_to_world', clip_to_world, (4, 4), env, 'environment')
+    operands = [('clip_to_world', clip_to_world, 3)]
+    if mask is not None:
+        _stage.check_operand('mask', mask, (rows, cols), env, 'environment')
+        operands.append(('mask', mask, 3))
+    const = None
+    if isinstance(intensity, torch.Tensor):
+        _stage.check_operand('intensity', intensity, (3,), env, 'environment')
+        operands.append(('intensity', intensity, 2))
+    else:
+        const = tuple(_value(intensity, 3, 'intensity', env.device, None))
+    scenes, batched = _stage.scene_count(who, *operands)
+    flags = _lib.BACKGROUND_FOOTPRINT if filter == 'trilinear' and lod_value is None else 0
+    return rows, cols, scenes, batched, n, levels, _lib.BACKGROUND_FILTERS[filter], flags, 0.0 if lod_value is None else lod_value, lod_bias, const

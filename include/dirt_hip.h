@@ -799,6 +799,49 @@ int dirt_shadow_backward(const float *gbuffer, const float *maps, const float *m
                          float softness, float normal_offset, void *stream);
 
 /*
+ * The environment seen behind the mesh, fused; specification in dirt_amd/csrc/dirt_background.hip and DESIGN.md §7i
+ * (dirt_amd/lighting.py::environment_background).  Per pixel (r, c) of a rows x cols image, with M = the scene's matrix
+ * (clip -> world, row vectors), I its intensity and m its mask (0 without one):
+ *     nx = 2 (c + 0.5) / cols - 1      ny = 1 - 2 (r + 0.5) / rows      h(z) = [nx, ny, z, 1] @ M
+ *     d = h(0).xyz / h(0).w - h(-1).xyz / h(-1).w          out_j = (1 - m) I_j E_j(d)
+ * E: the look-up of dirt_texture_cube_forward at d -- `filter` DIRT_BACKGROUND_NEAREST, _BILINEAR or _TRILINEAR, the last at
+ * the level of detail lod + lod_bias or, with DIRT_BACKGROUND_FOOTPRINT in `flags`, at log2 of the pixel's analytic footprint
+ * in texels + lod_bias (lod is not read).  A pixel whose d is not valid (h.w = 0, anything non-finite) or whose 1 - m is 0
+ * gives 0, reads no texel and adds to no gradient but grad_mask.
+ *   environment [6, floats]: a packed pyramid per face of `levels` levels of a size x size x 3 cube, as
+ *   dirt_texture_mip_build_batch lays the six faces out (levels = 1: the cube [6, size, size, 3] itself; anything but
+ *   _TRILINEAR takes 1 only); matrices [matrix_scenes, 4, 4], intensity [intensity_scenes, 3]; mask: NULL, or a scene's
+ *   rows * cols values mask_stride >= 1 floats apart, scene after scene (mask_scenes = scenes) or one for all (1);
+ *   out [scenes, rows, cols, 3].  Each ..._scenes is 1 (shared by the scenes) or scenes.
+ * Backward: grad_out like out; grad_environment like environment (cleared, then added into with float atomics by the
+ *   kernels of dirt_texture_cube_backward: not the same bits on every run), grad_matrices like matrices and grad_intensity
+ *   like intensity (per-workgroup sums in `scratch` of dirt_background_scratch_bytes(scenes, rows, cols) bytes -- 0:
+ *   invalid sizes --, added in a fixed order, over the scenes in scene order where shared: the same bits on every run),
+ *   grad_mask [scenes, rows * cols], dense, one value per scene and pixel whatever mask_scenes (needs mask).  Each may be
+ *   NULL and is then not computed -- all four NULL: success, nothing is launched; the scratch is needed unless grad_mask
+ *   alone is asked for.  Zero scenes or pixels: success, the first three are cleared.
+ * Refused before any device work, with a sentence in dirt_last_error(): a scene count outside 0..65535, a pixel grid that
+ *   is negative, has more than 2^31 - 1 rows or columns or 2^40 pixels, an unknown filter or flag, the footprint without
+ *   _TRILINEAR, a size outside 1..32768, levels the size does not have or more than 1 without _TRILINEAR, a ..._scenes that
+ *   is neither 1 nor scenes, mask_stride < 1, a lod or lod_bias that is not finite, a NULL operand, grad_mask without
+ *   mask, a scratch that is missing, too small or misaligned.
+ */
+#define DIRT_BACKGROUND_NEAREST 0
+#define DIRT_BACKGROUND_BILINEAR 1
+#define DIRT_BACKGROUND_TRILINEAR 2
+#define DIRT_BACKGROUND_FOOTPRINT 1u
+size_t dirt_background_scratch_bytes(long long scenes, long long rows, long long cols);
+int dirt_background_forward(const float *environment, const float *matrices, const float *intensity, const float *mask,
+                            float *out, long long scenes, long long rows, long long cols, int size, int levels,
+                            int matrix_scenes, int intensity_scenes, int mask_scenes, int mask_stride, int filter, float lod,
+                            float lod_bias, unsigned flags, void *stream);
+int dirt_background_backward(const float *environment, const float *matrices, const float *intensity, const float *mask,
+                             const float *grad_out, float *grad_environment, float *grad_matrices, float *grad_intensity,
+                             float *grad_mask, void *scratch, size_t scratch_bytes, long long scenes, long long rows,
+                             long long cols, int size, int levels, int matrix_scenes, int intensity_scenes, int mask_scenes,
+                             int mask_stride, int filter, float lod, float lod_bias, unsigned flags, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
