@@ -5,7 +5,8 @@ The reference's samples/ and tests/ say `import dirt`, `dirt.rasterise(...)`, `i
 such scripts run unchanged apart from TensorFlow -> torch tensors.  `dirt.shading` carries the fused G-buffer shaders
 (`shade_gbuffer`, `shade_gbuffer_sh`, `shade_gbuffer_pbr` with `dirt.lighting.cook_torrance` as its per-vertex form, and
 `shade_gbuffer_ibl` with `dirt.lighting.image_based_lighting` and the table of `dirt.lighting.environment_brdf`) and
-`environment_background`, the environment seen behind the mesh (`dirt.lighting.environment_background` is its torch form);
+`environment_background`, the environment seen behind the mesh (`dirt.lighting.environment_background` is its torch form),
+and `resolve_image`, the last stage: supersample resolve, exposure, tone curve and sRGB encode (`dirt.lighting.resolve_image`);
 `dirt.texture` the look-ups, by (u, v) (`sample_texture_uv`) and by direction into a cube map (`sample_texture_cube`),
 and the GGX-prefiltered environment pyramid (`prefilter_cube`, looked up by `sample_cube_pyramid`).
 Tangent-space normal mapping is `dirt.geometry.vertex_tangents` (per-vertex frames from the uvs) and

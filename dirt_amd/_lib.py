@@ -45,6 +45,10 @@ SHADOW_MAX_LIGHTS = 4   # = SHADE_PBR_MAX_LIGHTS: the lights of dirt_shadow_forw
 SHADOW_KERNELS = (1, 3, 5)   # the sides of its percentage-closer filter
 BACKGROUND_FILTERS = {'nearest': 0, 'bilinear': 1, 'trilinear': 2}   # the filter of dirt_background_forward
 BACKGROUND_FOOTPRINT = 1   # its flag: the level of detail from the pixel's footprint
+RESOLVE_MAX_FACTOR, RESOLVE_MAX_CHANNELS = 4, 4   # of dirt_resolve_forward
+RESOLVE_CURVES = {'linear': 0, 'reinhard': 1, 'aces': 2}
+RESOLVE_ENCODINGS = {'linear': 0, 'srgb': 1}
+RESOLVE_CLAMP = 1
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
 GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
@@ -82,7 +86,8 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_tangent_scratch_bytes', 'dirt_tangent_forward', 'dirt_tangent_backward',
            'dirt_normal_map_forward', 'dirt_normal_map_backward',
            'dirt_shadow_scratch_bytes', 'dirt_shadow_forward', 'dirt_shadow_backward',
-           'dirt_background_scratch_bytes', 'dirt_background_forward', 'dirt_background_backward')
+           'dirt_background_scratch_bytes', 'dirt_background_forward', 'dirt_background_backward',
+           'dirt_resolve_scratch_bytes', 'dirt_resolve_forward', 'dirt_resolve_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -273,6 +278,14 @@ def load():
         lib.dirt_background_forward.restype = i
         lib.dirt_background_backward.argtypes = [fp] * 9 + [vp, sz, ll, ll, ll] + [i] * 7 + [f32, f32, u, vp]
         lib.dirt_background_backward.restype = i
+    if hasattr(lib, 'dirt_resolve_forward') or not override:   # resolve, tone map, encode (ABI 4, additive)
+        f32 = ctypes.c_float
+        lib.dirt_resolve_scratch_bytes.argtypes = [ll, ll, ll, i, i]
+        lib.dirt_resolve_scratch_bytes.restype = sz
+        lib.dirt_resolve_forward.argtypes = [fp] * 6 + [ll, ll, ll] + [i] * 10 + [f32, f32, u, vp]
+        lib.dirt_resolve_forward.restype = i
+        lib.dirt_resolve_backward.argtypes = [fp] * 8 + [vp, sz, ll, ll, ll] + [i] * 6 + [f32, f32, u, vp]
+        lib.dirt_resolve_backward.restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

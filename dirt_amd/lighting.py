@@ -720,3 +720,111 @@ def environment_background(environment, clip_to_world, size, *, mask=None, inten
     scale = inten[..., None, None, :] if w is None else w[..., None] * inten[..., None, None, :]
     out = scale * E
     return torch.where(valid[..., None], out, torch.zeros_like(out))
+
+
+# ---- the developed image: supersample resolve, exposure, tone curve, sRGB encode, clamp
+
+RESOLVE_CURVES = ('linear', 'reinhard', 'aces')
+RESOLVE_ENCODINGS = ('linear', 'srgb')
+RESOLVE_MAX_FACTOR, RESOLVE_MAX_CHANNELS = 4, 4
+SRGB_KNEE = 0.0031308   # the linear value where the sRGB transfer function leaves its linear segment
+
+
+def srgb_encode(x):
+    """The sRGB transfer function of a linear value, per element: u = max(x, 0); 12.92 u where u <= 0.0031308, else
+    1.055 u^(1 / 2.4) - 0.055.  (The power is taken of max(u, knee): the branch that is not taken cannot put inf * 0 into a gradient.)"""
+    u = x.clamp_min(0.)
+    return torch.where(u <= SRGB_KNEE, 12.92 * u, 1.055 * u.clamp_min(SRGB_KNEE) ** (1. / 2.4) - 0.055)
+
+
+def srgb_decode(y):
+    """The inverse of `srgb_encode` on [0, 1], which linearises a photograph: y / 12.92 where y <= 12.92 * 0.0031308, else
+    ((y + 0.055) / 1.055)^2.4."""
+    knee = 12.92 * SRGB_KNEE
+    return torch.where(y <= knee, y / 12.92, ((y.clamp_min(knee) + 0.055) / 1.055) ** 2.4)
+
+
+def _resolve_scalars(factor, curve, white, encode, clamp):
+    """The python arguments of `resolve_image`, refused outside their ranges -> (lo, hi) of the clamp or None."""
+    if isinstance(factor, bool) or not isinstance(factor, numbers.Integral) or not 1 <= factor <= RESOLVE_MAX_FACTOR:
+        raise ValueError('resolve_image: factor must be an int in 1..%d, got %r' % (RESOLVE_MAX_FACTOR, factor))
+    if curve not in RESOLVE_CURVES:
+        raise ValueError("resolve_image: curve must be 'linear', 'reinhard' or 'aces', got %r" % (curve,))
+    if encode not in RESOLVE_ENCODINGS:
+        raise ValueError("resolve_image: encode must be 'linear' or 'srgb', got %r" % (encode,))
+    if (curve == 'reinhard') != (white is not None):
+        raise ValueError("resolve_image: white goes with curve='reinhard' and only with it (got curve=%r, white=%r)" % (curve, white))
+    if white is not None and not isinstance(white, torch.Tensor) and (isinstance(white, bool) or not isinstance(white, numbers.Real) or not white > 0):
+        raise ValueError('resolve_image: white must be a positive number or a tensor, got %r' % (white,))
+    if clamp is None:
+        return None
+    try:
+        lo, hi = (float(v) for v in clamp)
+    except (TypeError, ValueError):
+        raise ValueError('clamp must be (lo, hi) or None, got %r' % (clamp,))
+    if not lo <= hi:
+        raise ValueError('clamp needs lo <= hi, got %r' % (clamp,))
+    return lo, hi
+
+
+def _resolve_sizes(image, factor):
+    """Refuses an image that `resolve_image` cannot resolve by its shape -> (H, W, C) of the output."""
+    if not isinstance(image, torch.Tensor) or image.dim() not in (3, 4):
+        raise ValueError('resolve_image expects image [S H, S W, C] or [B, S H, S W, C], got %s' % (tuple(getattr(image, 'shape', ())),))
+    rows, cols, channels = (int(s) for s in image.shape[-3:])
+    if not 1 <= channels <= RESOLVE_MAX_CHANNELS:
+        raise ValueError('resolve_image: image has %d channels, 1..%d' % (channels, RESOLVE_MAX_CHANNELS))
+    if rows % factor or cols % factor:
+        raise ValueError('resolve_image: an image of %d x %d samples is no multiple of factor=%d each way' % (rows, cols, factor))
+    return rows // factor, cols // factor, channels
+
+
+def resolve_image(image, *, add=None, factor=1, exposure=1.0, curve='linear', white=None, encode='linear', clamp=(0., 1.)):
+    """What every rendered image goes through between the shaders and a loss against a photograph: two radiance images added,
+    S x S samples box-filtered into a pixel, exposure, a tone curve, the sRGB transfer function, a clamp.  image
+    [S H, S W, C] or [B, S H, S W, C] with C in 1..4 and S = `factor` (1..4); add: None or a second image of the same shape;
+    exposure: the gain per channel, a number, C numbers or a tensor [C] or [B, C] (exposure and white balance in one);
+    curve 'linear', 'reinhard' (extended Reinhard, with the white point `white`: a positive number or a tensor [] or [B]) or
+    'aces' (the Narkowicz fit); encode 'linear' or 'srgb'; clamp (lo, hi) or None -> [H, W, C] or [B, H, W, C].  Per output
+    pixel (r, c) and channel ch, one operation per step and in this order:
+
+        acc = 0;  for i in 0..S-1, for j in 0..S-1:  acc += image[S r + i, S c + j, ch] + add[S r + i, S c + j, ch]
+        L = acc * (1 / S^2)                     E = exposure[ch] * L
+        'linear':    t = E                      (negatives pass: masks and auxiliary channels resolve with the same call)
+        otherwise    x = max(E, 0), and
+        'reinhard':  t = x * (1 + x / (w * w)) / (1 + x)
+        'aces':      t = x * (2.51 x + 0.03) / (x * (2.43 x + 0.59) + 0.14)
+        'linear':    y = t
+        'srgb':      u = max(t, 0);  y = 12.92 u where u <= 0.0031308, else 1.055 u^(1 / 2.4) - 0.055       (`srgb_encode`)
+        out = clamp(y, lo, hi)
+
+    A NaN stays NaN throughout.  Differentiable in image, add, exposure and white; works in float64 and on any device.  The
+    sums are the explicit i, j loop, so that their order is the one `shading.resolve_image` keeps."""
+    bounds = _resolve_scalars(factor, curve, white, encode, clamp)
+    _resolve_sizes(image, factor)
+    if add is not None and (not isinstance(add, torch.Tensor) or add.shape != image.shape):
+        raise ValueError('resolve_image: add must have the shape of image, %s, got %s' % (tuple(image.shape), tuple(getattr(add, 'shape', ()))))
+    S = int(factor)
+    acc = torch.zeros_like(image[..., 0::S, 0::S, :])
+    for i in range(S):
+        for j in range(S):
+            sample = image[..., i::S, j::S, :]
+            acc = acc + (sample if add is None else sample + add[..., i::S, j::S, :])
+    L = acc * torch.full((), 1. / (S * S), dtype=image.dtype, device=image.device)
+    e = _as(exposure, image)
+    if e.dim() == 2:
+        e = e[:, None, None, :]
+    E = e * L
+    if curve == 'linear':
+        t = E
+    else:
+        x = E.clamp_min(0.)
+        if curve == 'reinhard':
+            w = _as(white, image)
+            if w.dim() == 1:
+                w = w[:, None, None, None]
+            t = x * (1. + x / (w * w)) / (1. + x)
+        else:
+            t = x * (2.51 * x + 0.03) / (x * (2.43 * x + 0.59) + 0.14)
+    y = srgb_encode(t) if encode == 'srgb' else t
+    return y if bounds is None else y.clamp(*bounds)

@@ -1007,6 +1007,8 @@ def environment_background(environment, clip_to_world, size, *, mask=None, inten
     Returns [H, W, 3] or [B, H, W, 3]:  (1 - m) intensity E(ray), not clamped; a pixel whose ray is not valid (h.w = 0) or
     whose 1 - m is exactly 0 gives 0.  Behind a lit mesh:
         (shade_gbuffer_ibl(..., background=(0., 0., 0.), clamp=None) + environment_background(..., mask=g[..., m])).clamp(0., 1.)
+    or, fused with the antialiasing and the development of the image (`resolve_image`):
+        resolve_image(shade_gbuffer_ibl(..., background=(0., 0., 0.), clamp=None), add=environment_background(..., mask=g[..., m]))
     Gradients are those of torch's autograd for `lighting.environment_background` and go to the environment, clip_to_world,
     intensity and mask.  The environment's is summed with float atomics: it is not the same bits on every run, everything
     else is."""
@@ -1068,3 +1070,106 @@ def _check_background_arguments(environment, clip_to_world, size, mask, intensit
     scenes, batched = _stage.scene_count(who, *operands)
     flags = _lib.BACKGROUND_FOOTPRINT if filter == 'trilinear' and lod_value is None else 0
     return rows, cols, scenes, batched, n, levels, _lib.BACKGROUND_FILTERS[filter], flags, 0.0 if lod_value is None else lod_value, lod_bias, const
+
+
+# ---- the developed image: supersample resolve, exposure, tone curve, sRGB encode, clamp (dirt_resolve.hip)
+
+class _ResolveImage(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, add, exposure, white, meta):
+        """image, add (or None): [S H, S W, C] or [B, S H, S W, C], read in place under `_stage.rows_in_place`; exposure
+        [1 or B, C], white [1 or B] or None: float32"""
+        lib = _lib.load()
+        scenes, batched, rows, cols, channels, factor, curve, encode, lo, hi, flags = meta
+        dev = image.device
+        isrc, istride = _stage.rows_in_place(image, channels)
+        asrc, astride = _stage.rows_in_place(add, channels) if add is not None else (None, 0)
+        exposure = exposure.contiguous()
+        white = white.contiguous() if white is not None else None
+        out = torch.empty(((scenes,) if batched else ()) + (rows, cols, channels), dtype=torch.float32, device=dev)
+        linear = torch.empty_like(out) if any(ctx.needs_input_grad[:4]) else None   # L: all a backward pass reads
+        ctx.sizes = (scenes, rows, cols, channels, factor)
+        ctx.tail = (int(exposure.shape[0]), int(white.shape[0]) if white is not None else 1, curve, encode, lo, hi, flags)
+        if scenes * rows * cols:
+            _stage.call(lib.dirt_resolve_forward, dev, isrc.data_ptr(), _ptr(asrc), exposure.data_ptr(), _ptr(white), out.data_ptr(), _ptr(linear),
+                        *ctx.sizes, istride, astride, scenes if image.dim() == 4 else 1, scenes if add is not None and add.dim() == 4 else 1, *ctx.tail)
+        ctx.save_for_backward(linear, exposure, white)
+        ctx.shape = tuple(image.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        linear, exposure, white = ctx.saved_tensors
+        scenes, rows, cols, channels, factor = ctx.sizes
+        dev = grad_out.device
+        empty = not scenes * rows * cols
+        want_image, want_add, want_e, want_w = ctx.needs_input_grad[:4]
+        dense = grad_out.new_empty((scenes, rows * factor, cols * factor, 1))
+        grad_image, grad_add = _stage.dense_grads(dense, (channels, channels), (want_image, want_add), empty)   # two tensors, never one storage
+        grad_e, grad_w = _stage.grad_outputs((exposure, white), (want_e, want_w and white is not None), empty)
+        if not empty:
+            grad_out = grad_out.to(torch.float32).contiguous()
+            nbytes = lib.dirt_resolve_scratch_bytes(*ctx.sizes) if grad_e is not None or grad_w is not None else 0
+            _stage.call(lib.dirt_resolve_backward, dev, linear.data_ptr(), exposure.data_ptr(), _ptr(white), grad_out.data_ptr(), _ptr(grad_image),
+                        _ptr(grad_add), _ptr(grad_e), _ptr(grad_w), _ptr(_stage.scratch(dev, nbytes)), nbytes, *ctx.sizes, *ctx.tail)
+        if len(ctx.shape) == 3:   # an image shared by the scenes: summed over them, in scene order
+            grad_image, grad_add = (None if g is None else (g[0] if scenes == 1 else g.sum(0)) for g in (grad_image, grad_add))
+        return grad_image, grad_add, grad_e, grad_w, None
+
+
+def resolve_image(image, *, add=None, factor=1, exposure=1.0, curve='linear', white=None, encode='linear', clamp=(0., 1.)):
+    """The last stage of the renderer in one kernel, differentiably: what `lighting.resolve_image` computes per pixel (its
+    docstring is the specification) -- `add` summed onto `image` sample by sample, `factor` x `factor` samples box-filtered
+    into a pixel, exposure, a tone curve, the sRGB transfer function and the clamp -- with no image in between.
+
+    image: float32 on the GPU, [S H, S W, C] or [B, S H, S W, C] with C in 1..4 and S = `factor`; read in place where it is
+        `rgba[..., :3]` or another slice of a contiguous G-buffer.
+    add: None, or a second image of exactly image's shape, read in place by the same rule: behind a lit mesh,
+        resolve_image(shade_gbuffer_ibl(..., background=(0., 0., 0.), clamp=None), add=environment_background(..., mask=g[..., m]), ...)
+    factor: a python int in 1..4 that divides both sides of the image; 1 develops every pixel by itself.
+    exposure: the gain per channel (exposure and white balance in one): a number, C numbers, or a tensor [C] or [B, C].
+    curve: 'linear', 'reinhard' (extended Reinhard; needs `white`, a positive number or a tensor [] or [B]) or 'aces' (the
+        Narkowicz fit).  encode: 'linear' or 'srgb'.  clamp: (lo, hi) or None.
+    The batch size B comes from image, add, exposure or white, whichever has a leading B (they must agree); an operand
+    without one is shared by the scenes.
+
+    Returns [H, W, C] or [B, H, W, C] float32.  Gradients are those of torch's autograd for `lighting.resolve_image` and go to
+    image, add (a tensor of its own), exposure and white where they are tensors; the same bits on every run."""
+    from .lighting import _resolve_scalars, _resolve_sizes
+    who = 'resolve_image'
+    bounds = _resolve_scalars(factor, curve, white, encode, clamp)
+    rows, cols, channels = _resolve_sizes(image, factor)
+    _stage.check_float32('image', image)
+    operands = [('image', image, 4)]
+    if add is not None:
+        if not isinstance(add, torch.Tensor) or add.shape != image.shape:
+            raise ValueError('%s: add must have the shape of image, %s, got %s' % (who, tuple(image.shape), tuple(getattr(add, 'shape', ()))))
+        _stage.check_float32('add', add, image, 'image')
+        operands.append(('add', add, 4))
+    dev = image.device
+    if isinstance(exposure, torch.Tensor):
+        _stage.check_operand('exposure', exposure, (channels,), image, 'image')
+        operands.append(('exposure', exposure, 2))
+        gains = exposure.reshape(-1, channels)
+    else:
+        gains = (float(exposure),) * channels if isinstance(exposure, numbers.Real) else tuple(_value(exposure, channels, 'exposure', dev, None))
+    if isinstance(white, torch.Tensor):
+        if white.dim() > 1:
+            raise ValueError('white must have shape [] or [B], got %s' % (tuple(white.shape),))
+        _stage.check_float32('white', white, image, 'image')
+        operands.append(('white', white, 1))
+        point = white.reshape(-1)
+    else:
+        point = None if white is None else (float(white),)
+    scenes, batched = _stage.scene_count(who, *operands)
+    _stage.require_gpu(image, 'dirt_amd.shading.%s' % who)
+    if isinstance(gains, tuple):
+        gains = _const_block(dev, gains)
+    if isinstance(point, tuple):
+        point = _const_block(dev, point).reshape(1)
+    lo, hi = bounds if bounds is not None else (0., 0.)
+    meta = (scenes, batched, rows, cols, channels, int(factor), _lib.RESOLVE_CURVES[curve], _lib.RESOLVE_ENCODINGS[encode], lo, hi,
+            _lib.RESOLVE_CLAMP if bounds is not None else 0)
+    return _ResolveImage.apply(image, add, gains, point, meta)

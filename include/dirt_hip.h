@@ -842,6 +842,50 @@ int dirt_background_backward(const float *environment, const float *matrices, co
                              int mask_stride, int filter, float lod, float lod_bias, unsigned flags, void *stream);
 
 /*
+ * The last stage of the renderer, fused: supersample resolve, exposure, tone curve, sRGB encode and clamp; specification in
+ * dirt_amd/csrc/dirt_resolve.hip and DESIGN.md §7j (dirt_amd/lighting.py::resolve_image).  Per pixel (r, c) and channel ch of
+ * a rows x cols output, with S = factor, e the scene's exposure and w its white point, in float32 and in this order:
+ *     acc = 0;  for i in 0..S-1, for j in 0..S-1:  acc += image[S r + i, S c + j, ch] (+ add[...]);   L = acc * float(1 / S^2)
+ *     E = e[ch] L;   t = E (DIRT_RESOLVE_LINEAR), or with x = max(E, 0):  x (1 + x / (w w)) / (1 + x)  (_REINHARD),
+ *     x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14)  (_ACES);   y = t (DIRT_RESOLVE_ENCODE_LINEAR) or, with u = max(t, 0),
+ *     12.92 u where u <= 0.0031308, else 1.055 powf(u, 1 / 2.4) - 0.055  (_ENCODE_SRGB);   out = clamp(y, clamp_lo, clamp_hi)
+ *     with DIRT_RESOLVE_CLAMP in `flags`.  A NaN stays NaN.
+ *   image, add (NULL: none): a scene's S rows x S cols samples of `channels` floats, image_stride / add_stride >= channels
+ *   floats apart, scene after scene (image_scenes = scenes) or one image for all (1); exposure [exposure_scenes, channels];
+ *   white [white_scenes] with _REINHARD and only with it, else NULL; out and linear (NULL: not written; L, what the backward
+ *   pass reads) [scenes, rows, cols, channels].  Each ..._scenes is 1 (shared by the scenes) or scenes.
+ * Backward: grad_out like out; grad_image and grad_add [scenes, S rows, S cols, channels], dense, one value per scene and
+ *   sample whatever image_scenes; grad_exposure like exposure and grad_white like white (per-workgroup sums in `scratch` of
+ *   dirt_resolve_scratch_bytes(scenes, rows, cols, channels, factor) bytes -- 0: invalid sizes --, added in a fixed order, over
+ *   the scenes in scene order where shared: the same bits on every run).  Each may be NULL and is then not computed -- all
+ *   four NULL: success, nothing is launched; the scratch is needed for grad_exposure and grad_white.  Zero scenes or pixels:
+ *   success, the last two are cleared.
+ * Refused before any device work, with a sentence in dirt_last_error(): a scene count outside 0..65535, channels outside
+ *   1..DIRT_RESOLVE_MAX_CHANNELS, a factor outside 1..DIRT_RESOLVE_MAX_FACTOR, an image that is negative, has more than
+ *   (2^31 - 1) / DIRT_RESOLVE_MAX_FACTOR rows or columns or 2^36 pixels, an unknown curve, encoding or flag, clamp_lo >
+ *   clamp_hi, a ..._scenes that is neither 1 nor scenes, white without _REINHARD or _REINHARD without white, a stride below
+ *   channels, a NULL operand, grad_white without white, a scratch that is missing, too small or misaligned.
+ */
+#define DIRT_RESOLVE_MAX_FACTOR 4
+#define DIRT_RESOLVE_MAX_CHANNELS 4
+#define DIRT_RESOLVE_LINEAR 0
+#define DIRT_RESOLVE_REINHARD 1
+#define DIRT_RESOLVE_ACES 2
+#define DIRT_RESOLVE_ENCODE_LINEAR 0
+#define DIRT_RESOLVE_ENCODE_SRGB 1
+#define DIRT_RESOLVE_CLAMP 1u
+size_t dirt_resolve_scratch_bytes(long long scenes, long long rows, long long cols, int channels, int factor);
+int dirt_resolve_forward(const float *image, const float *add, const float *exposure, const float *white, float *out,
+                         float *linear, long long scenes, long long rows, long long cols, int channels, int factor,
+                         int image_stride, int add_stride, int image_scenes, int add_scenes, int exposure_scenes,
+                         int white_scenes, int curve, int encode, float clamp_lo, float clamp_hi, unsigned flags, void *stream);
+int dirt_resolve_backward(const float *linear, const float *exposure, const float *white, const float *grad_out,
+                          float *grad_image, float *grad_add, float *grad_exposure, float *grad_white, void *scratch,
+                          size_t scratch_bytes, long long scenes, long long rows, long long cols, int channels, int factor,
+                          int exposure_scenes, int white_scenes, int curve, int encode, float clamp_lo, float clamp_hi,
+                          unsigned flags, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
