@@ -8,7 +8,8 @@ such scripts run unchanged apart from TensorFlow -> torch tensors.  `dirt.shadin
 `environment_background`, the environment seen behind the mesh (`dirt.lighting.environment_background` is its torch form),
 and `resolve_image`, the last stage: supersample resolve, exposure, tone curve and sRGB encode (`dirt.lighting.resolve_image`);
 `dirt.texture` the look-ups, by (u, v) (`sample_texture_uv`) and by direction into a cube map (`sample_texture_cube`),
-and the GGX-prefiltered environment pyramid (`prefilter_cube`, looked up by `sample_cube_pyramid`).
+the GGX-prefiltered environment pyramid (`prefilter_cube`, looked up by `sample_cube_pyramid`), and the resamplers between a
+lat-long panorama and a cube map (`panorama_to_cube`, `cube_to_panorama`).
 Tangent-space normal mapping is `dirt.geometry.vertex_tangents` (per-vertex frames from the uvs) and
 `dirt.shading.perturb_normals` (the shading normal, written back into the G-buffer), with `dirt.lighting.vertex_tangents` and
 `dirt.lighting.perturb_normals` as their pure-torch forms.

@@ -49,6 +49,7 @@ RESOLVE_MAX_FACTOR, RESOLVE_MAX_CHANNELS = 4, 4   # of dirt_resolve_forward
 RESOLVE_CURVES = {'linear': 0, 'reinhard': 1, 'aces': 2}
 RESOLVE_ENCODINGS = {'linear': 0, 'srgb': 1}
 RESOLVE_CLAMP = 1
+PANORAMA_MAX_SAMPLES = 4   # of dirt_panorama_to_cube_forward / dirt_cube_to_panorama_forward: samples x samples per texel
 GEOM_PRE_SPLIT = 1
 GEOM_LONG_LIST_SHIFT, GEOM_LONG_LIST_MASK, GEOM_LONG_LIST_DEFAULT = 8, 0xffff00, 64   # lists longer than this are summed by a wave
 GEOM_MAX_VERTICES, GEOM_MAX_FACES = 1 << 28, 1 << 29
@@ -87,7 +88,9 @@ SYMBOLS = ('dirt_abi_version', 'dirt_last_error', 'dirt_workspace_bytes', 'dirt_
            'dirt_normal_map_forward', 'dirt_normal_map_backward',
            'dirt_shadow_scratch_bytes', 'dirt_shadow_forward', 'dirt_shadow_backward',
            'dirt_background_scratch_bytes', 'dirt_background_forward', 'dirt_background_backward',
-           'dirt_resolve_scratch_bytes', 'dirt_resolve_forward', 'dirt_resolve_backward')
+           'dirt_resolve_scratch_bytes', 'dirt_resolve_forward', 'dirt_resolve_backward',
+           'dirt_panorama_scratch_bytes', 'dirt_panorama_to_cube_forward', 'dirt_panorama_to_cube_backward',
+           'dirt_cube_to_panorama_forward', 'dirt_cube_to_panorama_backward')
 
 
 class DirtLibraryError(RuntimeError):
@@ -286,6 +289,14 @@ def load():
         lib.dirt_resolve_forward.restype = i
         lib.dirt_resolve_backward.argtypes = [fp] * 8 + [vp, sz, ll, ll, ll] + [i] * 6 + [f32, f32, u, vp]
         lib.dirt_resolve_backward.restype = i
+    if hasattr(lib, 'dirt_panorama_to_cube_forward') or not override:   # lat-long environment maps (ABI 4, additive)
+        lib.dirt_panorama_scratch_bytes.argtypes = [ll, ll, i, i, i, i]
+        lib.dirt_panorama_scratch_bytes.restype = sz
+        for name in ('dirt_panorama_to_cube', 'dirt_cube_to_panorama'):
+            getattr(lib, name + '_forward').argtypes = [fp] * 3 + [ll, ll, i, i, i, vp]
+            getattr(lib, name + '_forward').restype = i
+            getattr(lib, name + '_backward').argtypes = [fp] * 5 + [vp, sz, ll, ll, i, i, i, vp]
+            getattr(lib, name + '_backward').restype = i
     if lib.dirt_abi_version() != ABI_VERSION and not override:
         raise DirtLibraryError('libdirt_hip.so ABI %d != expected %d' % (lib.dirt_abi_version(), ABI_VERSION))
     _lib = lib

@@ -11,7 +11,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libdirt_hip.so')
 SOURCES = ['dirt_capi.hip', 'dirt_raster.hip', 'dirt_forward.hip', 'dirt_grad.hip', 'dirt_grad_small.hip', 'dirt_grad_px2.hip', 'dirt_texture.hip',
            'dirt_texture_mip.hip', 'dirt_texture_cube.hip', 'dirt_envmap.hip', 'dirt_shade.hip', 'dirt_shade_albedo.hip', 'dirt_shade_sh.hip', 'dirt_shade_pbr.hip', 'dirt_shade_pbr_visibility.hip', 'dirt_shade_ibl.hip', 'dirt_geometry.hip', 'dirt_skin.hip', 'dirt_kinematics.hip', 'dirt_blend.hip',
-           'dirt_tangent.hip', 'dirt_normal_map.hip', 'dirt_shadow.hip', 'dirt_background.hip', 'dirt_resolve.hip']
+           'dirt_tangent.hip', 'dirt_normal_map.hip', 'dirt_shadow.hip', 'dirt_background.hip', 'dirt_resolve.hip', 'dirt_panorama.hip']
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + [os.path.join('..', '..', 'include', 'dirt_hip.h')]
 
 # -ffp-contract=off: the numeric specification is a sequence of IEEE basic operations

@@ -19,7 +19,12 @@ same three filters; `directions_to_cube_indices` and `sample_cube` are its pure-
 `prefilter_cube` makes the GGX-prefiltered pyramid of an environment cube (a `CubePyramid`: level k the cube's box-filtered
 level k convolved with a GGX lobe of roughness r_k; dirt_envmap.hip), `convolve_cube` one such convolution (or the cosine
 one, the irradiance), and `sample_cube_pyramid` is the trilinear cube look-up in a pyramid the caller made -- `cube_pyramid`
-the box-filtered one.  `cube_texel_directions` and `convolve_cube_dense` are the convolution's pure-torch form for small cubes."""
+the box-filtered one.  `cube_texel_directions` and `convolve_cube_dense` are the convolution's pure-torch form for small cubes.
+
+`panorama_to_cube` resamples a lat-long (equirectangular) panorama [H, W, C] into such a cube and `cube_to_panorama` a cube
+into a panorama, supersampled and under an optional rotation, with gradients to the sampled operand and to the rotation
+(dirt_panorama.hip); `panorama_to_cube_dense` and `cube_to_panorama_dense`, over `panorama_texel_directions`,
+`directions_to_panorama_indices` and `sample_panorama`, are their pure-torch form and their specification."""
 import ctypes
 import functools
 import math
@@ -778,3 +783,209 @@ def sample_cube_pyramid(pyramid, directions, lod, *, lod_bias=0.0):
         raise ValueError('lod and directions must be on the same device (%s vs %s)' % (lod.device, directions.device))
     _stage.require_gpu(packed, 'dirt_amd.texture.sample_cube_pyramid')
     return _SampleCubePyramid.apply(packed, directions.to(torch.float32), lod, float(lod_bias), pyramid.size, pyramid.channels, pyramid.levels)
+
+
+# ---- lat-long (equirectangular) panoramas: the environment as it is captured (dirt_panorama.hip; specification in DESIGN.md §7k) ------
+
+_K2, _K1 = 1. / (2. * math.pi), 1. / math.pi   # phi -> u and theta -> v are products with these, rounded to the tensor's dtype
+
+
+def _check_count(who, name, value, most=None):
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1 or (most is not None and value > most):
+        raise ValueError('%s: %s must be %s, got %r' % (who, name, 'a positive int' if most is None else 'an int in 1..%d' % most, value))
+
+
+def panorama_texel_directions(height, width, samples=1, device=None, dtype=torch.float32):
+    """-> (directions [height * samples, width * samples, 3], unit vectors through the centres of the samples x samples
+    sub-samples of a panorama's pixels, and weights [height * samples, width * samples], their solid angles up to a constant:
+    sin theta).  Row 0 is +Y, the middle column looks along -Z, columns grow towards +X.  The inverse of
+    `directions_to_panorama_indices`: with samples = 1, direction [i, j] maps back to index (i, j).  Pure torch."""
+    who = 'panorama_texel_directions'
+    _check_count(who, 'height', height)
+    _check_count(who, 'width', width)
+    _check_count(who, 'samples', samples, _lib.PANORAMA_MAX_SAMPLES)
+
+    def centres(n):
+        k = torch.arange(n * samples, device=device)
+        return (torch.div(k, samples, rounding_mode='floor').to(dtype) + ((k % samples).to(dtype) + 0.5) / samples) / n
+
+    theta, phi = math.pi * centres(height)[:, None], (2. * math.pi) * (centres(width)[None, :] - 0.5)
+    st = torch.sin(theta)
+    d = torch.stack([st * torch.sin(phi), torch.cos(theta).expand(-1, width * samples), -(st * torch.cos(phi))], -1)
+    return d, st.expand(-1, width * samples).contiguous()
+
+
+def directions_to_panorama_indices(directions, height, width):
+    """[..., 3] directions (not normalised) -> (fractional (row, column) indices [..., 2] into a `height` x `width` panorama,
+    valid bool [...]): theta = atan2(sqrt(x^2 + z^2), y) from +Y gives the row, theta / pi * height - 0.5 clamped to
+    [0, height - 1]; phi = atan2(x, -z) gives the column, (phi / (2 pi) + 0.5) * width - 0.5, which is NOT wrapped here (it lies
+    in [-0.5, width - 0.5]; `sample_panorama` wraps its taps).  Straight up or down (x = z = 0) takes phi = 0 and no gradient.
+    A direction that is not finite or is all zero is not valid: index 0, and no gradient.  Pure torch, on any device,
+    differentiable; `sample_panorama(panorama, *directions_to_panorama_indices(directions, H, W))` is a panorama's look-up."""
+    who = 'directions_to_panorama_indices'
+    if not isinstance(directions, torch.Tensor) or directions.dim() < 1 or directions.shape[-1] != 3 or not directions.is_floating_point():
+        raise ValueError('%s expects floating-point directions of shape [..., 3], got %s' % (who, tuple(getattr(directions, 'shape', ()))))
+    _check_count(who, 'height', height)
+    _check_count(who, 'width', width)
+    with torch.no_grad():
+        valid = torch.isfinite(directions).all(-1) & (directions.abs().amax(-1) > 0)
+    up = torch.zeros_like(directions)
+    up[..., 1] = 1.
+    x, y, z = torch.where(valid.unsqueeze(-1), directions, up).unbind(-1)
+    rho2 = x * x + z * z
+    with torch.no_grad():
+        pole = rho2.sqrt() == 0
+    one = torch.ones_like(rho2)
+    rho = torch.where(pole, torch.zeros_like(rho2), torch.where(pole, one, rho2).sqrt())
+    theta = torch.atan2(rho, y)
+    phi = torch.where(pole, torch.zeros_like(rho2), torch.atan2(torch.where(pole, one, x), -torch.where(pole, one, z)))
+    col = (phi * _K2 + 0.5) * float(width) - 0.5
+    row = ((theta * _K1) * float(height) - 0.5).clamp(0., float(height - 1))
+    indices = torch.stack([row, col], -1)
+    return torch.where(valid.unsqueeze(-1), indices, torch.zeros_like(indices)), valid
+
+
+def sample_panorama(panorama, indices, valid):
+    """panorama [H, W, C], and per look-up the fractional (row, column) `indices` [..., 2] and `valid` of
+    `directions_to_panorama_indices` -> [..., C]: the bilinear blend of the four texels around the index, columns wrapping
+    around the panorama and rows clamped to it; 0 where not valid.  Pure torch, differentiable."""
+    h, w = int(panorama.shape[0]), int(panorama.shape[1])
+    floor = torch.floor(indices)
+    frac = indices - floor
+    r, c = floor[..., 0].to(torch.int64).clamp(0, h - 1), torch.remainder(floor[..., 1].to(torch.int64), w)
+    r1, c1 = (r + 1).clamp(max=h - 1), torch.remainder(c + 1, w)
+    fr, fc = frac[..., :1], frac[..., 1:]
+    out = (panorama[r, c] * (1. - fc) * (1. - fr) + panorama[r, c1] * fc * (1. - fr)) + panorama[r1, c] * (1. - fc) * fr + panorama[r1, c1] * fc * fr
+    return torch.where(valid.unsqueeze(-1), out, torch.zeros_like(out))
+
+
+def _box_mean(x, samples):
+    """[..., R * S, C * S, ch] -> [..., R, C, ch]: the S x S samples of a texel added in row-major order, then times 1 / S^2."""
+    acc = None
+    for a in range(samples):
+        for b in range(samples):
+            s = x[..., a::samples, b::samples, :]
+            acc = s if acc is None else acc + s
+    return acc * (1. / (samples * samples))
+
+
+def _check_panorama_arguments(who, source, what, shape_text, rotation, samples, **counts):
+    """The checks `panorama_to_cube` and `cube_to_panorama` share with their dense forms -> the rotation as a tensor (None: the
+    identity)."""
+    ok = isinstance(source, torch.Tensor) and 0 not in source.shape and (
+        source.dim() == 3 if what == 'panorama' else source.dim() == 4 and source.shape[0] == 6 and source.shape[1] == source.shape[2])
+    if not ok:
+        raise ValueError('%s expects %s to be %s, got %s' % (who, what, shape_text, tuple(source.shape) if isinstance(source, torch.Tensor) else type(source).__name__))
+    if not source.is_floating_point():
+        raise ValueError('%s: %s must be a floating-point tensor, got %s' % (who, what, source.dtype))
+    for name, value in counts.items():
+        _check_count(who, name, value)
+    _check_count(who, 'samples', samples, _lib.PANORAMA_MAX_SAMPLES)
+    if rotation is None:
+        return torch.eye(3, dtype=source.dtype, device=source.device)
+    if not isinstance(rotation, torch.Tensor) or tuple(rotation.shape) != (3, 3) or not rotation.is_floating_point():
+        raise ValueError('%s: rotation must be a floating-point tensor [3, 3] or None, got %s' % (
+            who, '%s %s' % (rotation.dtype, tuple(rotation.shape)) if isinstance(rotation, torch.Tensor) else type(rotation).__name__))
+    if rotation.device != source.device:
+        raise ValueError('%s: rotation is on %s, the %s on %s' % (who, rotation.device, what, source.device))
+    return rotation
+
+
+def _cube_sample_directions(size, samples, device, dtype):
+    """The directions (not normalised) through the samples x samples sub-samples of a cube's texels [6, size * samples,
+    size * samples, 3], by the table of `cube_texel_directions`."""
+    k = torch.arange(size * samples, device=device)
+    x = (2. * (torch.div(k, samples, rounding_mode='floor').to(dtype) + ((k % samples).to(dtype) + 0.5) / samples)) / size - 1.
+    tc, sc = torch.meshgrid(x, x, indexing='ij')
+    one = torch.ones_like(sc)
+    return torch.stack([torch.stack(f, -1) for f in ((one, -tc, -sc), (-one, -tc, sc), (sc, one, tc), (sc, -one, -tc), (sc, -tc, one), (-sc, -tc, -one))])
+
+
+def _rotate(d, rotation, transposed):
+    """d @ rotation (or @ rotation^T) with the three products added in order, as the kernels add them"""
+    m = rotation.t() if transposed else rotation
+    return (d[..., 0:1] * m[0] + d[..., 1:2] * m[1]) + d[..., 2:3] * m[2]
+
+
+def panorama_to_cube_dense(panorama, size, samples=1, rotation=None):
+    """The specification of `panorama_to_cube`: pure torch, on any device, in the panorama's dtype, differentiable with respect
+    to the panorama and the rotation.  panorama [H, W, C] (row 0 at +Y, the middle column along -Z, columns growing towards
+    +X) -> cube [6, size, size, C]: every texel the mean of samples x samples look-ups (`sample_panorama`) at
+    e @ rotation^T, e the directions through the sub-samples' places on the face.  `rotation` [3, 3] in row vectors: its
+    rows are the images of the panorama's axes in the cube's frame; None is the identity."""
+    who = 'panorama_to_cube_dense'
+    rotation = _check_panorama_arguments(who, panorama, 'panorama', '3D [height, width, channels]', rotation, samples, size=size)
+    e = _cube_sample_directions(size, samples, panorama.device, panorama.dtype)
+    h, w = int(panorama.shape[0]), int(panorama.shape[1])
+    looked = sample_panorama(panorama, *directions_to_panorama_indices(_rotate(e, rotation.to(panorama.dtype), True), h, w))
+    return _box_mean(looked, samples)
+
+
+def cube_to_panorama_dense(cube, height, width, samples=1, rotation=None):
+    """The specification of `cube_to_panorama`: pure torch, differentiable with respect to the cube and the rotation.  cube
+    [6, N, N, C] -> panorama [height, width, C]: every pixel the mean of samples x samples bilinear cube look-ups
+    (`directions_to_cube_indices`, `sample_cube`) at d @ rotation, d the sub-samples' `panorama_texel_directions`."""
+    who = 'cube_to_panorama_dense'
+    rotation = _check_panorama_arguments(who, cube, 'cube', '4D [6, size, size, channels]', rotation, samples, height=height, width=width)
+    d, _ = panorama_texel_directions(height, width, samples, cube.device, cube.dtype)
+    looked = sample_cube(cube, *directions_to_cube_indices(_rotate(d, rotation.to(cube.dtype), False), int(cube.shape[1])))
+    return _box_mean(looked, samples)
+
+
+class _PanoramaResample(torch.autograd.Function):
+    """source [H, W, C] -> [6, size, size, C] (`to_cube`), or source [6, N, N, C] -> [height, width, C]; rotation [3, 3]."""
+
+    @staticmethod
+    def forward(ctx, source, rotation, to_cube, rows, cols, size, samples):
+        source, rotation = source.contiguous(), rotation.contiguous()
+        ct = int(source.shape[-1])
+        lib = _lib.load()
+        out = torch.empty((6, size, size, ct) if to_cube else (rows, cols, ct), dtype=torch.float32, device=source.device)
+        _call(lib.dirt_panorama_to_cube_forward if to_cube else lib.dirt_cube_to_panorama_forward, source.device, source.data_ptr(), rotation.data_ptr(),
+              out.data_ptr(), rows, cols, size, ct, samples)
+        ctx.save_for_backward(source, rotation)
+        ctx.meta = (to_cube, rows, cols, size, ct, samples)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        source, rotation = ctx.saved_tensors
+        to_cube, rows, cols, size, ct, samples = ctx.meta
+        lib, dev = _lib.load(), source.device
+        grad_out = grad_out.contiguous().to(torch.float32)
+        grad_source = torch.empty_like(source) if ctx.needs_input_grad[0] else None
+        grad_rotation = torch.empty_like(rotation) if ctx.needs_input_grad[1] else None
+        need = to_cube and grad_rotation is not None or not to_cube and (grad_source is not None or grad_rotation is not None)
+        nbytes = lib.dirt_panorama_scratch_bytes(rows, cols, size, ct, samples, int(to_cube)) if need else 0
+        scratch = _stage.scratch(dev, nbytes)
+        _call(lib.dirt_panorama_to_cube_backward if to_cube else lib.dirt_cube_to_panorama_backward, dev, source.data_ptr(), rotation.data_ptr(),
+              grad_out.data_ptr(), _stage.ptr(grad_source), _stage.ptr(grad_rotation), _stage.ptr(scratch), nbytes, rows, cols, size, ct, samples)
+        return grad_source, grad_rotation, None, None, None, None, None
+
+
+def panorama_to_cube(panorama, size, *, samples=1, rotation=None):
+    """Fused `panorama_to_cube_dense`: a lat-long (equirectangular) panorama [H, W, C] float32 -- row 0 at +Y, the middle column
+    along -Z, columns growing towards +X -- resampled into a cube [6, size, size, C] (faces in OpenGL order), what
+    `prefilter_cube`, `shade_gbuffer_ibl` and `environment_background` take.  Every texel is the mean of samples x samples
+    (1..4) bilinear look-ups of the panorama, whose columns wrap and whose rows clamp.  `rotation` [3, 3] in row vectors turns
+    the panorama: its rows are the images of the panorama's axes in the cube's frame (`matrices.rodrigues(w,
+    three_by_three=True)`); None is the identity, to the bit.  Differentiable with respect to the panorama (float atomics) and the
+    rotation (the same bits on every run)."""
+    who = 'panorama_to_cube'
+    rotation = _check_panorama_arguments(who, panorama, 'panorama', '3D [height, width, channels]', rotation, samples, size=size)
+    _stage.require_gpu(panorama, 'dirt_amd.texture.panorama_to_cube')
+    return _PanoramaResample.apply(panorama.to(torch.float32), rotation.to(torch.float32), True, int(panorama.shape[0]), int(panorama.shape[1]),
+                                   size, samples)
+
+
+def cube_to_panorama(cube, height, width, *, samples=1, rotation=None):
+    """Fused `cube_to_panorama_dense`: a cube [6, N, N, C] float32 resampled into a lat-long panorama [height, width, C], the
+    inverse of `panorama_to_cube` up to the two resamplings.  Every pixel is the mean of samples x samples (1..4) bilinear cube
+    look-ups (`sample_texture_cube`'s) at d @ rotation, d the directions of the sub-samples; `rotation` as in
+    `panorama_to_cube` (the same matrix takes a panorama to the cube and back).  Differentiable with respect to the cube (float
+    atomics) and the rotation (the same bits on every run)."""
+    who = 'cube_to_panorama'
+    rotation = _check_panorama_arguments(who, cube, 'cube', '4D [6, size, size, channels]', rotation, samples, height=height, width=width)
+    _stage.require_gpu(cube, 'dirt_amd.texture.cube_to_panorama')
+    return _PanoramaResample.apply(cube.to(torch.float32), rotation.to(torch.float32), False, height, width, int(cube.shape[1]), samples)

@@ -886,6 +886,44 @@ int dirt_resolve_backward(const float *linear, const float *exposure, const floa
                           unsigned flags, void *stream);
 
 /*
+ * Lat-long (equirectangular) environment maps, fused: a panorama resampled into a cube and a cube into a panorama, both
+ * supersampled and under a rotation; specification in dirt_amd/csrc/dirt_panorama.hip and DESIGN.md §7k
+ * (dirt_amd/texture.py::panorama_to_cube_dense, cube_to_panorama_dense).  The panorama [rows, cols, channels] has row 0 at
+ * +Y, its middle column looks along -Z and its columns grow towards +X; its columns wrap, its rows clamp, the look-up is
+ * bilinear.  The cube is [6, size, size, channels], faces in OpenGL order, each face clamped to its own edges.  rotation
+ * [3, 3], row vectors: its rows are the images of the panorama's axes in the cube's frame.
+ *   dirt_panorama_to_cube_forward: cube texel (f, r, c) = the mean of the samples x samples look-ups of the panorama at
+ *   e @ rotation^T, e the direction through the sub-sample's place on the face.
+ *   dirt_cube_to_panorama_forward: panorama pixel (i, j) = the mean of the samples x samples look-ups of the cube (as
+ *   dirt_texture_cube_forward's, bilinear) at d @ rotation, d the direction of the sub-sample's (theta, phi).
+ *   A direction that is not finite or all zero after the rotation adds 0.  The samples are added in row-major order, then
+ *   multiplied by float(1 / samples^2).
+ * Backward: grad_cube / grad_panorama (the incoming one) like the forward's output.  The gradient of the sampled operand
+ *   (grad_panorama of dirt_panorama_to_cube_backward, grad_cube of dirt_cube_to_panorama_backward) is cleared, then added into
+ *   with float atomics (the latter by the kernels of dirt_texture_cube_backward): not the same bits on every run.
+ *   grad_rotation [3, 3]: per-workgroup sums in `scratch`, added in a fixed order: the same bits on every run.  Either may be
+ *   NULL and is then not computed -- both NULL: success, nothing is launched.  scratch: dirt_panorama_scratch_bytes(rows, cols,
+ *   size, channels, samples, to_cube) bytes (0: invalid sizes), to_cube = 1 for dirt_panorama_to_cube_backward, which needs it
+ *   for grad_rotation only, 0 for dirt_cube_to_panorama_backward, which always needs it.
+ * Refused before any device work, with a sentence in dirt_texture_last_error(): rows, cols, size or channels below 1, samples
+ *   outside 1..DIRT_PANORAMA_MAX_SAMPLES, a size above 32768, a panorama of more than 2^20 rows or columns, more than 65536
+ *   channels, a grid of samples of more than 2^31 - 1 tiles (dirt_cube_to_panorama_*), a NULL operand, a scratch that is
+ *   missing, too small or misaligned.
+ */
+#define DIRT_PANORAMA_MAX_SAMPLES 4
+size_t dirt_panorama_scratch_bytes(long long rows, long long cols, int size, int channels, int samples, int to_cube);
+int dirt_panorama_to_cube_forward(const float *panorama, const float *rotation, float *cube, long long rows, long long cols,
+                                  int size, int channels, int samples, void *stream);
+int dirt_panorama_to_cube_backward(const float *panorama, const float *rotation, const float *grad_cube, float *grad_panorama,
+                                   float *grad_rotation, void *scratch, size_t scratch_bytes, long long rows, long long cols,
+                                   int size, int channels, int samples, void *stream);
+int dirt_cube_to_panorama_forward(const float *cube, const float *rotation, float *panorama, long long rows, long long cols,
+                                  int size, int channels, int samples, void *stream);
+int dirt_cube_to_panorama_backward(const float *cube, const float *rotation, const float *grad_panorama, float *grad_cube,
+                                   float *grad_rotation, void *scratch, size_t scratch_bytes, long long rows, long long cols,
+                                   int size, int channels, int samples, void *stream);
+
+/*
  * Per-kernel timing (host-side state only).  Slots are the library's kernels; dirt_profile_count()
  * returns how many there are, dirt_profile_name(i) their names.  dirt_profile_read waits for the
  * recorded events of calls made with DIRT_FLAG_PROFILE on this thread, adds them to the running
