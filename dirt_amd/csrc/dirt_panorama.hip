@@ -7,7 +7,9 @@
 // per step, with K2 = float(1 / (2 pi)), K1 = float(1 / pi), PI = float(pi), PI2 = float(2 pi):
 //
 //  1. The panorama's row 0 is +Y (up), its middle column looks along -Z, its columns grow towards +X.  The look-up L(d) of a
-//     direction d = (x, y, z), valid as a cube look-up's (all finite, not all zero; otherwise 0 and no gradient):
+//     direction d, valid as a cube look-up's (all finite, not all zero; otherwise 0 and no gradient), is that of
+//     (x, y, z) = d 2^-e, e = frexp(max |d_i|)'s exponent: the largest component in [0.5, 1), exactly, a subnormal one included,
+//     so that rho2 neither overflows nor underflows whatever the length of d.  The gradient of d is that of (x, y, z) times 2^-e.
 //       rho2 = x x + z z    rho = sqrt(rho2)    theta = atan2(rho, y)    phi = atan2(x, -z), 0 where rho == 0
 //       u = phi K2 + 0.5    v = theta K1        col = u Wp - 0.5         row = clamp(v Hp - 0.5, 0, Hp - 1)
 //       columns wrap: taps at floor(col) mod Wp and that + 1 mod Wp, weight fc = col - floor(col);
@@ -103,7 +105,8 @@ template <int S> __device__ __forceinline__ void pano_pixel_direction(int r, int
 struct PanoLook {
     bool valid, inside;   // inside: the row is not clamped
     Taps k;
-    float x, y, z, rho, rho2;
+    float x, y, z, rho, rho2;   // of the direction times 2^-e
+    int e;
 };
 __device__ __forceinline__ PanoLook pano_look(float x, float y, float z, int Hp, int Wp)
 {
@@ -111,7 +114,9 @@ __device__ __forceinline__ PanoLook pano_look(float x, float y, float z, int Hp,
     const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
     const float big = fmaxf(ax, fmaxf(ay, az));
     q.valid = ax < INFINITY && ay < INFINITY && az < INFINITY && big > 0.f;   // (a NaN fails its comparison)
-    q.x = q.valid ? x : 0.f; q.y = q.valid ? y : 1.f; q.z = q.valid ? z : 0.f;
+    q.e = 0;
+    if (q.valid) (void)frexpf(big, &q.e);   // big 2^-e lies in [0.5, 1); ldexpf is exact here, for a subnormal `big` too
+    q.x = q.valid ? ldexpf(x, -q.e) : 0.f; q.y = q.valid ? ldexpf(y, -q.e) : 1.f; q.z = q.valid ? ldexpf(z, -q.e) : 0.f;
     q.rho2 = q.x * q.x + q.z * q.z;
     q.rho = sqrtf(q.rho2);
     const float theta = atan2f(q.rho, q.y), phi = q.rho == 0.f ? 0.f : atan2f(q.x, -q.z);
@@ -130,16 +135,16 @@ __device__ __forceinline__ PanoLook pano_look(float x, float y, float z, int Hp,
     return q;
 }
 
-// (g_row, g_col) = dL / d (row, col) of a look-up -> dL / d (x, y, z)
+// (g_row, g_col) = dL / d (row, col) of a look-up -> dL / d d: that of the scaled direction, times 2^-e
 __device__ __forceinline__ void pano_direction_gradient(const PanoLook& q, float g_row, float g_col, int Hp, int Wp, float (&g)[3])
 {
     const float gphi = g_col * ((float)Wp * PANO_K2), gth = q.inside ? g_row * ((float)Hp * PANO_K1) : 0.f;
     const bool pole = !q.valid || q.rho == 0.f;
     const float rho2 = pole ? 1.f : q.rho2, rho = pole ? 1.f : q.rho;
     const float a = gphi / rho2, b = gth / (rho2 + q.y * q.y);
-    g[0] = pole ? 0.f : a * -q.z + b * ((q.x * q.y) / rho);
-    g[1] = pole ? 0.f : b * -rho;
-    g[2] = pole ? 0.f : a * q.x + b * ((q.z * q.y) / rho);
+    g[0] = pole ? 0.f : ldexpf(a * -q.z + b * ((q.x * q.y) / rho), -q.e);
+    g[1] = pole ? 0.f : ldexpf(b * -rho, -q.e);
+    g[2] = pole ? 0.f : ldexpf(a * q.x + b * ((q.z * q.y) / rho), -q.e);
 }
 
 // the bounding box of tap sets whose columns wrap (c1 may be 0 beside c0 = Wp - 1)

@@ -820,6 +820,9 @@ def directions_to_panorama_indices(directions, height, width):
     valid bool [...]): theta = atan2(sqrt(x^2 + z^2), y) from +Y gives the row, theta / pi * height - 0.5 clamped to
     [0, height - 1]; phi = atan2(x, -z) gives the column, (phi / (2 pi) + 0.5) * width - 0.5, which is NOT wrapped here (it lies
     in [-0.5, width - 0.5]; `sample_panorama` wraps its taps).  Straight up or down (x = z = 0) takes phi = 0 and no gradient.
+    The length of a direction does not matter, at either end of the dtype's range: (x, y, z) is the direction times the exact
+    power of two that brings its largest component into [0.5, 1) (`frexp`; a subnormal component included), so x^2 + z^2 neither
+    overflows nor underflows, and the gradient is scaled back by the same power of two.
     A direction that is not finite or is all zero is not valid: index 0, and no gradient.  Pure torch, on any device,
     differentiable; `sample_panorama(panorama, *directions_to_panorama_indices(directions, H, W))` is a panorama's look-up."""
     who = 'directions_to_panorama_indices'
@@ -831,7 +834,13 @@ def directions_to_panorama_indices(directions, height, width):
         valid = torch.isfinite(directions).all(-1) & (directions.abs().amax(-1) > 0)
     up = torch.zeros_like(directions)
     up[..., 1] = 1.
-    x, y, z = torch.where(valid.unsqueeze(-1), directions, up).unbind(-1)
+    d = torch.where(valid.unsqueeze(-1), directions, up)
+    with torch.no_grad():   # 2^-e, e the exponent of the largest component: exact, and in two factors (2^148 is no float32)
+        e = torch.frexp(d.abs().amax(-1, keepdim=True))[1]
+        half = torch.div(-e, 2, rounding_mode='floor')
+        one = torch.ones_like(d[..., :1])
+        s1, s2 = torch.ldexp(one, half), torch.ldexp(one, -e - half)
+    x, y, z = ((d * s1) * s2).unbind(-1)
     rho2 = x * x + z * z
     with torch.no_grad():
         pole = rho2.sqrt() == 0
@@ -970,7 +979,9 @@ def panorama_to_cube(panorama, size, *, samples=1, rotation=None):
     `prefilter_cube`, `shade_gbuffer_ibl` and `environment_background` take.  Every texel is the mean of samples x samples
     (1..4) bilinear look-ups of the panorama, whose columns wrap and whose rows clamp.  `rotation` [3, 3] in row vectors turns
     the panorama: its rows are the images of the panorama's axes in the cube's frame (`matrices.rodrigues(w,
-    three_by_three=True)`); None is the identity, to the bit.  Differentiable with respect to the panorama (float atomics) and the
+    three_by_three=True)`); None is the identity, to the bit.  It need be no rotation, and its scale does not matter: a look-up
+    scales its direction by an exact power of two first (`directions_to_panorama_indices`), subnormal directions included, so
+    2^k times a matrix gives the same cube to the bit.  Differentiable with respect to the panorama (float atomics) and the
     rotation (the same bits on every run)."""
     who = 'panorama_to_cube'
     rotation = _check_panorama_arguments(who, panorama, 'panorama', '3D [height, width, channels]', rotation, samples, size=size)
